@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- joint-triangulations/s + HBM roofline of the fused hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames 10000] [--pool 32] [--repeats 7]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames 10000] [--pool 32] [--repeats 1] [--full]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (snowtri_triangulate_condense: pixel->ray, pairwise
 triangulation + scoring, association/fusion) over one batch of synthetic input per GPU:
@@ -11,9 +12,14 @@ far larger than the 256 MB Infinity Cache) so every launch streams its input fro
 of re-reading a cache-resident 85 MB working set (SURVEY.md §7 hard part 6).
 
 Timed region: barrier + synchronize, K steps, synchronize + barrier; MAX over ranks.  The region is
-repeated --repeats times in one run (the chip's clock follows its power budget and a 20-step region
-lasts half a millisecond: single regions scatter by +-20 %); `value` / `ms_per_step` are the MEDIAN
-region, `repeats` lists min / max / all.
+repeated --repeats times in one run (default 1: a plain run times exactly --steps steps; 7 with --full:
+the chip's clock follows its power budget and a 20-step region lasts half a millisecond, so single
+regions scatter by +-20 %); `value` / `ms_per_step` are the MEDIAN region, `repeats` lists min / max / all.
+
+A plain run sets up, warms up, times the region and prints the headline keys.  Everything else below
+(the all-gather leg, the extra objects of the line, the output check) runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one rank per GPU (torch.distributed, backend nccl = RCCL).  Started WITHOUT a launcher
 (`python bench.py --gpus 8`) the script re-executes itself under `python -m torch.distributed.run`
@@ -25,7 +31,7 @@ are then timed a second time with that all-gather per step (double-buffered on a
 overlapping the next kernels) and reported as `with_track_allgather`.
 `--dry-run` exercises the launch / rendezvous logic alone (gloo, no GPU work): used by the CPU tests.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0; with --full it carries these extra objects:
   roofline          dominant kernel: algorithmic bytes per launch / mean launch duration measured with HIP
                     events on the launch stream (one stream, launches back to back); peak = 8 TB/s HBM3E
   roofline_region   the same bytes / `ms_per_step` of the timed region (--streams streams, launches overlap)
@@ -103,6 +109,29 @@ def free_port():
     port = s.getsockname()[1]
     s.close()
     return port
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: what the timed path hands its caller (the outputs of BatchTriangulator.run_torch) as d/<name>.npy,
+    float32 / float64 (the int32 counts and flags as float64: exact).  Outputs above DUMP_LIMIT_BYTES in all are cut to a
+    fixed, seeded sample of frames, and frame_index.npy names the frames kept."""
+    arrs = {}
+    for k, v in out.items():
+        a = v.cpu().numpy()
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    F = next(iter(arrs.values())).shape[0]
+    per_frame = sum(a.nbytes // max(1, F) for a in arrs.values()) + 8
+    keep = max(1, (DUMP_LIMIT_BYTES - 4096) // per_frame)
+    if keep < F:
+        idx = np.sort(np.random.default_rng(0).choice(F, keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["frame_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def relaunch_under_torchrun(args):
@@ -189,7 +218,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--frames", type=int, default=10000, help="frames per step per GPU (configs[1] = 10000)")
     ap.add_argument("--pool", type=int, default=32, help="distinct HBM-resident input batches cycled through")
-    ap.add_argument("--repeats", type=int, default=7, help="how many times the K-step region is timed (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the K-step region is timed (median reported); default 1, with --full 7")
     ap.add_argument("--large-frames", type=int, default=2000000,
                     help="extra single-launch roofline run (0 = skip); SURVEY §8d asks for >= 2e6 frames")
     ap.add_argument("--streams", type=int, default=2,
@@ -214,7 +244,17 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the multi-person extra workloads")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--dry-run", action="store_true", help="rendezvous only (gloo, no GPU): CPU test of the launcher")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: 7 timed regions, the all-gather leg (N > 1), per-kernel / roofline timings, "
+                         "the device-copy bandwidth, the output check, the large batch, the extra workloads, the CPU baseline, "
+                         "the per-frame API and the summary.  Without it a run sets up, warms up, times --steps steps once and "
+                         "prints the headline keys")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (rank 0's shard) as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of frames if they would exceed 64 MB)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(relaunch_under_torchrun(args))
@@ -264,8 +304,11 @@ def main():
     # (snowtri_ctx_set_overlap, BatchTriangulator(streams=n)): a plain loop of calls on one caller stream, issued by the
     # library round-robin on n internal streams so that the ramp-up / tail of consecutive launches overlap -- what round 3's
     # bench did by hand with twin contexts and its own streams is now what any caller gets.
-    bt = BatchTriangulator(Kc, Rc, tc, params, pout_max=Pout, out_dtype=np.float32, device=local_rank, method=method)
+    # Without --full only `bto` is needed.
     nstreams = max(1, min(4, args.streams))
+    bt = None
+    if args.full or nstreams == 1:
+        bt = BatchTriangulator(Kc, Rc, tc, params, pout_max=Pout, out_dtype=np.float32, device=local_rank, method=method)
     bto = bt if nstreams == 1 else BatchTriangulator(Kc, Rc, tc, params, pout_max=Pout, out_dtype=np.float32, device=local_rank,
                                                      method=method, streams=nstreams)
     # pool of distinct resident batches: exact projections + N(0, 1 px) noise, scores U(3.5, 8)
@@ -280,8 +323,8 @@ def main():
             jitter = torch.zeros_like(base)
             jitter[..., :2] = torch.randn(base.shape[:-1] + (2,), generator=gen, device=dev) * 0.25
             pool.append((base + jitter).contiguous())
-    outs = [bt.alloc_outputs(F, dev) for _ in range(len(pool))]
-    can_gather = dist is not None and not args.no_gather
+    outs = [bto.alloc_outputs(F, dev) for _ in range(len(pool))]
+    can_gather = args.full and dist is not None and not args.no_gather
 
     def timed_region():
         """W warm-up + K timed steps of the path itself (no collective: frames are independent); returns (seconds MAX over
@@ -335,6 +378,8 @@ def main():
     joints_per_step = F * Pout * J * world
     value = joints_per_step * K_steps / elapsed
     ms_per_step = elapsed / K_steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(W_steps + K_steps - 1) % len(pool)])
     # N > 1: the same K steps again WITH the all-gather of the 3D track that north_star names; reported
     # beside `value` (it is xGMI-bandwidth-bound: 16 B/joint over the links vs 64 B/joint over HBM).
     with_gather = None
@@ -361,181 +406,184 @@ def main():
                                 f"(joints, person scores, counts, flags: {(F * Pout * (J * 16 + 4) + 8 * F) / 1e6:.1f} MB per rank per step) "
                                 "packed and all-gathered with one RCCL collective on a side stream under the next piece's kernel")
 
-    # dominant-kernel duration: HIP events bracketing each launch on the launch stream
-    # (snowtri_set_timing records them inside the C ABI around the fused kernel only).
-    # (launches are queued back to back on ONE stream and their event pairs read afterwards: a synchronize
-    # between launches would let the GPU idle and clock down, and stretch every launch by ~10 %)
-    # Two passes of the same launches: (1) the event pair ATTACHED to the dispatch (hipExtLaunchKernelGGL start / stop events:
-    # the kernel's own begin and end, the duration rocprofv3's kernel trace reports -- the figure `roofline` quotes, and the
-    # one profiles/'s average must agree with); (2) the pair BRACKETING the launch (a record before and after: adds the command
-    # processor's hand-over on both sides, ~1 us), kept in the line as `kernel_ms_mean_bracketed`.
-    n_timed = min(max(K_steps, 200), 1000)
-    import snowmocap_amd.batch as _batch
-    trace_index = {}     # [first, last) ordinal of each loop's launches among this process's fused calls (scripts/gpu_event_check.sh)
-    def timed_launches(attach):
-        bt.ctx.set_timing(True, attach=attach)
-        first = _batch.FUSED_CALLS
+    kernel_ms_ranks, step_ms_ranks = None, [own_ms_per_step]
+    large = extra = cpu = per_frame = None
+    if args.full:
+        # dominant-kernel duration: HIP events bracketing each launch on the launch stream
+        # (snowtri_set_timing records them inside the C ABI around the fused kernel only).
+        # (launches are queued back to back on ONE stream and their event pairs read afterwards: a synchronize
+        # between launches would let the GPU idle and clock down, and stretch every launch by ~10 %)
+        # Two passes of the same launches: (1) the event pair ATTACHED to the dispatch (hipExtLaunchKernelGGL start / stop events:
+        # the kernel's own begin and end, the duration rocprofv3's kernel trace reports -- the figure `roofline` quotes, and the
+        # one profiles/'s average must agree with); (2) the pair BRACKETING the launch (a record before and after: adds the command
+        # processor's hand-over on both sides, ~1 us), kept in the line as `kernel_ms_mean_bracketed`.
+        n_timed = min(max(K_steps, 200), 1000)
+        import snowmocap_amd.batch as _batch
+        trace_index = {}     # [first, last) ordinal of each loop's launches among this process's fused calls (scripts/gpu_event_check.sh)
+        def timed_launches(attach):
+            bt.ctx.set_timing(True, attach=attach)
+            first = _batch.FUSED_CALLS
+            for i in range(n_timed):
+                bt.run_torch(pool[i % len(pool)], None, out=outs[i % len(pool)])
+            trace_index["attached" if attach else "bracketed"] = [first, _batch.FUSED_CALLS]
+            k = bt.ctx.timing_collect()
+            bt.ctx.set_timing(False)
+            torch.cuda.synchronize(dev)
+            return k
+        kms_bracketed = timed_launches(False)
+        kms = timed_launches(True)
+        # (1b) the same attached pairs while the launches are issued as the timed region issues them: a plain loop of calls in
+        # the library's overlap mode.  Two consecutive launches then share the chip, each takes longer from its begin to its end,
+        # and a step -- the time per launch of the loop -- is SHORTER than one launch alone: `ms_per_step` < `kernel_ms_mean` is
+        # that overlap, and this figure shows it inside the line (round-4 review).
+        kms_overlapped = None
+        if bto is not bt:
+            bto.ctx.set_timing(True, attach=True)
+            for i in range(n_timed):
+                bto.run_torch(pool[i % len(pool)], None, out=outs[i % len(pool)])
+            bto.join()
+            kms_overlapped = bto.ctx.timing_collect()
+            bto.ctx.set_timing(False)
+            torch.cuda.synchronize(dev)
+        trace_index["step"] = [_batch.FUSED_CALLS, _batch.FUSED_CALLS + n_timed]
+        # (3) the same launches with NO event in between, one pair around the whole loop: the time from one launch's end to the
+        # next one's end on one stream (kernel + the command processor's hand-over to the next dispatch), `kernel_ms_step_one_stream`
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
         for i in range(n_timed):
             bt.run_torch(pool[i % len(pool)], None, out=outs[i % len(pool)])
-        trace_index["attached" if attach else "bracketed"] = [first, _batch.FUSED_CALLS]
-        k = bt.ctx.timing_collect()
-        bt.ctx.set_timing(False)
+        e1.record()
         torch.cuda.synchronize(dev)
-        return k
-    kms_bracketed = timed_launches(False)
-    kms = timed_launches(True)
-    # (1b) the same attached pairs while the launches are issued as the timed region issues them: a plain loop of calls in
-    # the library's overlap mode.  Two consecutive launches then share the chip, each takes longer from its begin to its end,
-    # and a step -- the time per launch of the loop -- is SHORTER than one launch alone: `ms_per_step` < `kernel_ms_mean` is
-    # that overlap, and this figure shows it inside the line (round-4 review).
-    kms_overlapped = None
-    if bto is not bt:
-        bto.ctx.set_timing(True, attach=True)
-        for i in range(n_timed):
-            bto.run_torch(pool[i % len(pool)], None, out=outs[i % len(pool)])
-        bto.join()
-        kms_overlapped = bto.ctx.timing_collect()
-        bto.ctx.set_timing(False)
-        torch.cuda.synchronize(dev)
-    trace_index["step"] = [_batch.FUSED_CALLS, _batch.FUSED_CALLS + n_timed]
-    # (3) the same launches with NO event in between, one pair around the whole loop: the time from one launch's end to the
-    # next one's end on one stream (kernel + the command processor's hand-over to the next dispatch), `kernel_ms_step_one_stream`
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(n_timed):
-        bt.run_torch(pool[i % len(pool)], None, out=outs[i % len(pool)])
-    e1.record()
-    torch.cuda.synchronize(dev)
-    kernel_ms_step = e0.elapsed_time(e1) / n_timed
-    kernel_ms = float(np.mean(kms))
-    kernel_ms_min = float(np.min(kms))
-    kernel_ms_bracketed = float(np.mean(kms_bracketed))
-    # the achieved rate also against a device-copy bandwidth MEASURED on this box (1 GiB read + 1 GiB written per
-    # copy, best of 5 after a warm-up; bytes moved = 2 x the tensor)
-    copy_GBs = None
-    if not args.dry_run:
-        csrc = torch.empty(1 << 28, dtype=torch.float32, device=dev).normal_()
-        cdst = torch.empty_like(csrc)
-        cdst.copy_(csrc)
-        best = float("inf")
-        for _ in range(5):
-            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            c0.record()
+        kernel_ms_step = e0.elapsed_time(e1) / n_timed
+        kernel_ms = float(np.mean(kms))
+        kernel_ms_min = float(np.min(kms))
+        kernel_ms_bracketed = float(np.mean(kms_bracketed))
+        # the achieved rate also against a device-copy bandwidth MEASURED on this device (1 GiB read + 1 GiB written per
+        # copy, best of 5 after a warm-up; bytes moved = 2 x the tensor)
+        copy_GBs = None
+        if not args.dry_run:
+            csrc = torch.empty(1 << 28, dtype=torch.float32, device=dev).normal_()
+            cdst = torch.empty_like(csrc)
             cdst.copy_(csrc)
-            c1.record()
+            best = float("inf")
+            for _ in range(5):
+                c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                c0.record()
+                cdst.copy_(csrc)
+                c1.record()
+                torch.cuda.synchronize(dev)
+                best = min(best, c0.elapsed_time(c1))
+            copy_GBs = 2.0 * csrc.numel() * 4 / (best * 1e-3) / 1e9
+            del csrc, cdst
+        bpf = algorithmic_bytes_per_frame(C, P, Pout)
+        ach = bpf * F / (kernel_ms * 1e-3) / 1e9
+        ach_region = bpf * F / (ms_per_step * 1e-3) / 1e9          # per GPU: every rank streams its own shard
+
+        # correctness guard inside the bench: every frame of every pool batch resolved (count == 1) on the fast path
+        if os.environ.get("SNOWTRI_BENCH_NOCHECK") != "1":       # (timing-only development builds write wrong outputs)
+            for o in outs:
+                cnt = o["count"].cpu().numpy()
+                flg = o["flags"].cpu().numpy()
+                assert (cnt == 1).all() and ((flg & _lib.FLAG_FASTPATH) != 0).all(), "bench output is not the expected fast path"
+
+        kernel_name = bt.ctx.last_kernel_names()      # what the fused call really launched (snowtri_last_kernel_names)
+        # every rank's kernel time (a slow rank would otherwise hide behind rank 0's)
+        kernel_ms_ranks = [kernel_ms]
+        if dist is not None:
+            kdev = dev if backend == "nccl" else "cpu"        # (gloo gathers host tensors)
+            kt = torch.zeros(2 * world, dtype=torch.float64, device=kdev)
+            dist.all_gather_into_tensor(kt, torch.tensor([kernel_ms, own_ms_per_step], dtype=torch.float64, device=kdev))
+            kt = kt.cpu().view(world, 2)
+            kernel_ms_ranks = [float(x) for x in kt[:, 0]]
+            step_ms_ranks = [float(x) for x in kt[:, 1]]
+
+        if args.large_frames and rank == 0 and world == 1:
+            FL = args.large_frames
+            reps = (FL + F - 1) // F
+            big = torch.cat([pool[i % len(pool)] for i in range(reps)], dim=0)[:FL].contiguous()
+            bout = bt.alloc_outputs(FL, dev)
+            bt.ctx.set_timing(True)
+            lms = []
+            for _ in range(6):
+                bt.run_torch(big, None, out=bout)
+                lms.append(bt.ctx.last_kernel_ms()[0])
+            bt.ctx.set_timing(False)
+            lm = float(np.median(lms[1:]))
+            large = {"frames": FL, "kernel": bt.ctx.last_kernel_names(), "kernel_ms": lm, "kernel_ms_all": lms[1:], "joints_per_s": FL * J / (lm * 1e-3),
+                     "achieved_GBs": bpf * FL / (lm * 1e-3) / 1e9, "frac": bpf * FL / (lm * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            del big, bout
+
+        if rank == 0 and world == 1 and not args.no_extra and args.method == "pairwise":
+            extra = extra_workloads(torch, dev, local_rank)
+
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            from oracle import oracle as orc
+            prm = orc.make_params(**params)
+            ncores = usable_cores()
+            sample = wl["kpts"][: min(F, 10000)]
+            nps = wl["n_persons"][: sample.shape[0]]
+            orc.triangulate_condense_batch(Kc, Rc, tc, sample[:256], nps[:256], prm, Pout, nthreads=1)   # warm
+            # Containers often expose more logical CPUs than they may use: try a few team sizes on the
+            # bounded sample and report the best one together with the thread count that achieved it.
+            trials = sorted({1, min(8, ncores), min(32, ncores), ncores})
+            budget = args.cpu_seconds / len(trials)
+            best = None
+            for nt in trials:
+                reps, t_cpu = 0, 0.0
+                c0 = time.perf_counter()
+                while t_cpu < budget:
+                    r = orc.triangulate_condense_batch(Kc, Rc, tc, sample, nps, prm, Pout, nthreads=nt)
+                    reps += 1
+                    t_cpu = time.perf_counter() - c0
+                rate = sample.shape[0] * reps * J / t_cpu
+                if best is None or rate > best[0]:
+                    best = (rate, int(r["threads"]), reps, t_cpu)
+            # the oracle as the checker of this run's GPU output: pool batch 0 is the sample's own batch
+            bt.run_torch(pool[0], None, out=outs[0])
             torch.cuda.synchronize(dev)
-            best = min(best, c0.elapsed_time(c1))
-        copy_GBs = 2.0 * csrc.numel() * 4 / (best * 1e-3) / 1e9
-        del csrc, cdst
-    bpf = algorithmic_bytes_per_frame(C, P, Pout)
-    ach = bpf * F / (kernel_ms * 1e-3) / 1e9
-    ach_region = bpf * F / (ms_per_step * 1e-3) / 1e9          # per GPU: every rank streams its own shard
+            got = outs[0]["xyzs"][: sample.shape[0]].cpu().numpy().astype(np.float64)
+            err_m = float(np.abs(got[..., :3] - r["xyz"]).max())
+            err_s = float((np.abs(got[..., 3] - r["kscore"]) / np.maximum(np.abs(r["kscore"]), 1e-30)).max())
+            assert err_m < 1e-4, f"GPU joints differ from the oracle by {err_m} m"
+            cpu = {"value": best[0], "unit": "joints/s", "cores": best[1], "kind": "port",
+                   "sample": f"cfg2 batch of {sample.shape[0]} frames x {best[2]} repeats ({best[3]:.1f} s) at the best of "
+                             f"{trials} OpenMP threads ({ncores} logical CPUs visible); oracle/snowtri_oracle.c fp64",
+                   "gpu_vs_oracle_max_abs_m": err_m, "gpu_vs_oracle_max_rel_score": err_s}
 
-    # correctness guard inside the bench: every frame of every pool batch resolved (count == 1) on the fast path
-    if os.environ.get("SNOWTRI_BENCH_NOCHECK") != "1":       # (timing-only development builds write wrong outputs)
-        for o in outs:
-            cnt = o["count"].cpu().numpy()
-            flg = o["flags"].cpu().numpy()
-            assert (cnt == 1).all() and ((flg & _lib.FLAG_FASTPATH) != 0).all(), "bench output is not the expected fast path"
-
-    kernel_name = bt.ctx.last_kernel_names()      # what the fused call really launched (snowtri_last_kernel_names)
-    # every rank's kernel time (a slow rank would otherwise hide behind rank 0's)
-    kernel_ms_ranks = [kernel_ms]
-    step_ms_ranks = [own_ms_per_step]
-    if dist is not None:
-        kdev = dev if backend == "nccl" else "cpu"        # (gloo gathers host tensors)
-        kt = torch.zeros(2 * world, dtype=torch.float64, device=kdev)
-        dist.all_gather_into_tensor(kt, torch.tensor([kernel_ms, own_ms_per_step], dtype=torch.float64, device=kdev))
-        kt = kt.cpu().view(world, 2)
-        kernel_ms_ranks = [float(x) for x in kt[:, 0]]
-        step_ms_ranks = [float(x) for x in kt[:, 1]]
-
-    large = None
-    if args.large_frames and rank == 0 and world == 1:
-        FL = args.large_frames
-        reps = (FL + F - 1) // F
-        big = torch.cat([pool[i % len(pool)] for i in range(reps)], dim=0)[:FL].contiguous()
-        bout = bt.alloc_outputs(FL, dev)
-        bt.ctx.set_timing(True)
-        lms = []
-        for _ in range(6):
-            bt.run_torch(big, None, out=bout)
-            lms.append(bt.ctx.last_kernel_ms()[0])
-        bt.ctx.set_timing(False)
-        lm = float(np.median(lms[1:]))
-        large = {"frames": FL, "kernel": bt.ctx.last_kernel_names(), "kernel_ms": lm, "kernel_ms_all": lms[1:], "joints_per_s": FL * J / (lm * 1e-3),
-                 "achieved_GBs": bpf * FL / (lm * 1e-3) / 1e9, "frac": bpf * FL / (lm * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        del big, bout
-
-    extra = None
-    if rank == 0 and world == 1 and not args.no_extra and args.method == "pairwise":
-        extra = extra_workloads(torch, dev, local_rank)
-
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        from oracle import oracle as orc
-        prm = orc.make_params(**params)
-        ncores = usable_cores()
-        sample = wl["kpts"][: min(F, 10000)]
-        nps = wl["n_persons"][: sample.shape[0]]
-        orc.triangulate_condense_batch(Kc, Rc, tc, sample[:256], nps[:256], prm, Pout, nthreads=1)   # warm
-        # Containers often expose more logical CPUs than they may use: try a few team sizes on the
-        # bounded sample and report the best one together with the thread count that achieved it.
-        trials = sorted({1, min(8, ncores), min(32, ncores), ncores})
-        budget = args.cpu_seconds / len(trials)
-        best = None
-        for nt in trials:
-            reps, t_cpu = 0, 0.0
-            c0 = time.perf_counter()
-            while t_cpu < budget:
-                r = orc.triangulate_condense_batch(Kc, Rc, tc, sample, nps, prm, Pout, nthreads=nt)
-                reps += 1
-                t_cpu = time.perf_counter() - c0
-            rate = sample.shape[0] * reps * J / t_cpu
-            if best is None or rate > best[0]:
-                best = (rate, int(r["threads"]), reps, t_cpu)
-        # the oracle as the checker of this run's GPU output: pool batch 0 is the sample's own batch
-        bt.run_torch(pool[0], None, out=outs[0])
-        torch.cuda.synchronize(dev)
-        got = outs[0]["xyzs"][: sample.shape[0]].cpu().numpy().astype(np.float64)
-        err_m = float(np.abs(got[..., :3] - r["xyz"]).max())
-        err_s = float((np.abs(got[..., 3] - r["kscore"]) / np.maximum(np.abs(r["kscore"]), 1e-30)).max())
-        assert err_m < 1e-4, f"GPU joints differ from the oracle by {err_m} m"
-        cpu = {"value": best[0], "unit": "joints/s", "cores": best[1], "kind": "port",
-               "sample": f"cfg2 batch of {sample.shape[0]} frames x {best[2]} repeats ({best[3]:.1f} s) at the best of "
-                         f"{trials} OpenMP threads ({ncores} logical CPUs visible); oracle/snowtri_oracle.c fp64",
-               "gpu_vs_oracle_max_abs_m": err_m, "gpu_vs_oracle_max_rel_score": err_s}
-
-    # HBM bytes per launch from the PMC counters (rocprofv3 FETCH_SIZE / WRITE_SIZE passes, scripts/profile.sh):
-    # only quoted while the kernels are the ones it was measured on.
-    traffic, traffic_note = None, "no PMC measurement on file"
-    valu_per_64, valu_note = None, "no SQ_INSTS_VALU measurement of these kernel sources on file"
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_path) and args.method != "dlt":
-        try:
-            pj = json.load(open(pmc_path))
-            if pj.get("source_sha256") == kernel_source_hash() and pj.get("kernel") == kernel_name:
-                if pj.get("frames_per_launch") == F:
-                    traffic = pj.get("hbm_bytes_per_launch")
-                    traffic_note = "rocprofv3 PMC passes of this kernel source (profiles/pmc_traffic.json: source_sha256 matches)"
+        # HBM bytes per launch from the PMC counters (rocprofv3 FETCH_SIZE / WRITE_SIZE passes, scripts/profile.sh):
+        # only quoted while the kernels are the ones it was measured on.
+        traffic, traffic_note = None, "no PMC measurement on file"
+        valu_per_64, valu_note = None, "no SQ_INSTS_VALU measurement of these kernel sources on file"
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(pmc_path) and args.method != "dlt":
+            try:
+                pj = json.load(open(pmc_path))
+                if pj.get("source_sha256") == kernel_source_hash() and pj.get("kernel") == kernel_name:
+                    if pj.get("frames_per_launch") == F:
+                        traffic = pj.get("hbm_bytes_per_launch")
+                        traffic_note = "rocprofv3 PMC passes of this kernel source (profiles/pmc_traffic.json: source_sha256 matches)"
+                    else:
+                        traffic_note = "profiles/pmc_traffic.json was measured on another launch size: not quoted"
+                    if pj.get("valu", {}).get("per_64_joints"):
+                        valu_per_64 = float(pj["valu"]["per_64_joints"])
+                        valu_note = ("rocprofv3 SQ_INSTS_VALU of this kernel source on a %d-frame launch / wave-items "
+                                     "(profiles/pmc_traffic.json: source_sha256 matches)" % pj["valu"].get("frames", 0))
                 else:
-                    traffic_note = "profiles/pmc_traffic.json was measured on another launch size: not quoted"
-                if pj.get("valu", {}).get("per_64_joints"):
-                    valu_per_64 = float(pj["valu"]["per_64_joints"])
-                    valu_note = ("rocprofv3 SQ_INSTS_VALU of this kernel source on a %d-frame launch / wave-items "
-                                 "(profiles/pmc_traffic.json: source_sha256 matches)" % pj["valu"].get("frames", 0))
-            else:
-                traffic_note = "profiles/pmc_traffic.json was measured on other kernel sources: not quoted"
-        except Exception:
-            pass
+                    traffic_note = "profiles/pmc_traffic.json was measured on other kernel sources: not quoted"
+            except Exception:
+                pass
 
-    per_frame = None
-    if rank == 0 and world == 1 and not args.no_per_frame and args.method == "pairwise":
-        sys.path.insert(0, os.path.join(ROOT, "scripts"))
-        from bench_per_frame import per_frame_api
-        per_frame = per_frame_api(frames=300, warm=20)
+        if rank == 0 and world == 1 and not args.no_per_frame and args.method == "pairwise":
+            sys.path.insert(0, os.path.join(ROOT, "scripts"))
+            from bench_per_frame import per_frame_api
+            per_frame = per_frame_api(frames=300, warm=20)
+    elif dist is not None:
+        kdev = dev if backend == "nccl" else "cpu"
+        kt = torch.zeros(world, dtype=torch.float64, device=kdev)
+        dist.all_gather_into_tensor(kt, torch.tensor([own_ms_per_step], dtype=torch.float64, device=kdev))
+        step_ms_ranks = [float(x) for x in kt.cpu()]
 
-    overrides = bt.ctx.overrides()
+    overrides = bto.ctx.overrides()
     line = None
     if rank == 0:
         line = {
@@ -568,55 +616,58 @@ def main():
                        "build": _lib.build_info(),
                        "parallelism": f"frames sharded x{world}, no data-path collective",
                        "extra_workloads": None if extra is None else [e["workload"] for e in extra]},
-            "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
-                         "kernel": kernel_name, "streams": 1,
-                         "how": "HIP events on the launch stream, launches back to back on one stream; the event pair of a launch is attached "
-                                "to its dispatch (hipExtLaunchKernelGGL start / stop events = the kernel's own begin and end, what a rocprofv3 "
-                                "kernel trace reports; no event record between the launches); kernel_ms_mean_bracketed = the same launches "
-                                "with a pair recorded before and after each (barrier packets between the launches: the interval adds the "
-                                "command processor's hand-over on both sides, and the kernels no longer run back to back); "
-                                "kernel_ms_step_one_stream = the same launches with no event in between, one pair around the loop / launches "
-                                "(kernel + hand-over to the next dispatch: what a rocprofv3 --stats average of a one-stream run lands on)",
-                         "kernel_ms_mean": kernel_ms, "kernel_ms_median": float(np.median(kms)), "kernel_ms_min": kernel_ms_min, "launches": len(kms),
-                         "kernel_ms_mean_overlapped": None if kms_overlapped is None or not len(kms_overlapped) else float(np.mean(kms_overlapped)),
-                         "overlapped_note": f"the same kernel's begin-to-end time while launches are issued as `value` issues them (overlap mode, "
-                                            f"{nstreams} internal streams): two launches share the chip, each lasts longer, and ms_per_step "
-                                            "(time per launch of that loop) is shorter than kernel_ms_mean (one launch alone on the chip)",
-                         "kernel_ms_mean_bracketed": kernel_ms_bracketed,
-                         "frac_bracketed": bpf * F / (kernel_ms_bracketed * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "measured_device_copy_GBs": copy_GBs,
-                         "frac_of_measured_copy": None if not copy_GBs else ach / copy_GBs,
-                         "trace_index": dict(trace_index, total_fused_calls=_batch.FUSED_CALLS),
-                         "kernel_ms_step_one_stream": kernel_ms_step,
-                         "frac_step_one_stream": bpf * F / (kernel_ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_ms_mean_per_rank": kernel_ms_ranks,
-                         "algorithmic_bytes_per_launch": bpf * F, "bytes_per_joint": bpf / (Pout * J)},
-            "roofline_region": {"bound": "hbm", "achieved": ach_region, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                "frac": ach_region / HBM_PEAK_GBS, "streams": nstreams,
-                                "how": "algorithmic bytes per step / ms_per_step of the timed region (per GPU; "
-                                       f"a plain loop of calls in the library's overlap mode over {nstreams} internal streams, so consecutive launches overlap)"},
-            # the roof that actually binds this kernel: fp64 VALU issue.  VALU wave-instructions per 64 joints
-            # MEASURED (rocprofv3 SQ_INSTS_VALU, quoted only while profiles/pmc_traffic.json carries the hash of these kernel
-            # sources), 4 issue cycles each, 1024 SIMDs at the 2.4 GHz peak clock.
-            "fp64_valu_issue": None if args.method != "pairwise" else {
-                "valu_insts_per_64_joints": valu_per_64, "source": valu_note, "simds": 1024, "peak_clock_GHz": 2.4,
-                "frac_this_launch": None if valu_per_64 is None else
-                    (F * Pout * J / 64.0 * valu_per_64 * 4) / (kernel_ms * 1e-3) / (1024 * 2.4e9),
-                "frac_large_batch": None if large is None or valu_per_64 is None else
-                    (large["joints_per_s"] / 64.0 * valu_per_64 * 4) / (1024 * 2.4e9)},
-            "cpu_baseline": cpu,
-            "per_frame_api": per_frame,
-            "with_track_allgather": with_gather,
-            "large_batch": large,
-            "extra_workloads": extra,
             "ray_pair_solves_per_s": value * (C * (C - 1) // 2),
         }
-        # LAST key of the line: the driver keeps `parsed` (the contract keys) and the last 8 KB of stdout, so what survives of
-        # a 40 KB line used to be an accident of ordering (round 5: the float32 8 x 4 line fell out).  Every BASELINE config
-        # and north_star's DLT, one short entry each, in the tail.
-        line["summary"] = summary_of(line)
-    for b_ in {id(bt): bt, id(bto): bto}.values():
+        if args.full:
+            line.update({
+                "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
+                             "kernel": kernel_name, "streams": 1,
+                             "how": "HIP events on the launch stream, launches back to back on one stream; the event pair of a launch is attached "
+                                    "to its dispatch (hipExtLaunchKernelGGL start / stop events = the kernel's own begin and end, what a rocprofv3 "
+                                    "kernel trace reports; no event record between the launches); kernel_ms_mean_bracketed = the same launches "
+                                    "with a pair recorded before and after each (barrier packets between the launches: the interval adds the "
+                                    "command processor's hand-over on both sides, and the kernels no longer run back to back); "
+                                    "kernel_ms_step_one_stream = the same launches with no event in between, one pair around the loop / launches "
+                                    "(kernel + hand-over to the next dispatch: what a rocprofv3 --stats average of a one-stream run lands on)",
+                             "kernel_ms_mean": kernel_ms, "kernel_ms_median": float(np.median(kms)), "kernel_ms_min": kernel_ms_min, "launches": len(kms),
+                             "kernel_ms_mean_overlapped": None if kms_overlapped is None or not len(kms_overlapped) else float(np.mean(kms_overlapped)),
+                             "overlapped_note": f"the same kernel's begin-to-end time while launches are issued as `value` issues them (overlap mode, "
+                                                f"{nstreams} internal streams): two launches share the chip, each lasts longer, and ms_per_step "
+                                                "(time per launch of that loop) is shorter than kernel_ms_mean (one launch alone on the chip)",
+                             "kernel_ms_mean_bracketed": kernel_ms_bracketed,
+                             "frac_bracketed": bpf * F / (kernel_ms_bracketed * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "measured_device_copy_GBs": copy_GBs,
+                             "frac_of_measured_copy": None if not copy_GBs else ach / copy_GBs,
+                             "trace_index": dict(trace_index, total_fused_calls=_batch.FUSED_CALLS),
+                             "kernel_ms_step_one_stream": kernel_ms_step,
+                             "frac_step_one_stream": bpf * F / (kernel_ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "kernel_ms_mean_per_rank": kernel_ms_ranks,
+                             "algorithmic_bytes_per_launch": bpf * F, "bytes_per_joint": bpf / (Pout * J)},
+                "roofline_region": {"bound": "hbm", "achieved": ach_region, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                    "frac": ach_region / HBM_PEAK_GBS, "streams": nstreams,
+                                    "how": "algorithmic bytes per step / ms_per_step of the timed region (per GPU; "
+                                           f"a plain loop of calls in the library's overlap mode over {nstreams} internal streams, so consecutive launches overlap)"},
+                # the roof that actually binds this kernel: fp64 VALU issue.  VALU wave-instructions per 64 joints
+                # MEASURED (rocprofv3 SQ_INSTS_VALU, quoted only while profiles/pmc_traffic.json carries the hash of these kernel
+                # sources), 4 issue cycles each, 1024 SIMDs at the 2.4 GHz peak clock.
+                "fp64_valu_issue": None if args.method != "pairwise" else {
+                    "valu_insts_per_64_joints": valu_per_64, "source": valu_note, "simds": 1024, "peak_clock_GHz": 2.4,
+                    "frac_this_launch": None if valu_per_64 is None else
+                        (F * Pout * J / 64.0 * valu_per_64 * 4) / (kernel_ms * 1e-3) / (1024 * 2.4e9),
+                    "frac_large_batch": None if large is None or valu_per_64 is None else
+                        (large["joints_per_s"] / 64.0 * valu_per_64 * 4) / (1024 * 2.4e9)},
+                "cpu_baseline": cpu,
+                "per_frame_api": per_frame,
+                "with_track_allgather": with_gather,
+                "large_batch": large,
+                "extra_workloads": extra,
+            })
+            # LAST key of the line: a reader may keep only the contract keys and the last 8 KB of stdout, so what survives of
+            # a 40 KB line used to be an accident of ordering (round 5: the float32 8 x 4 line fell out).  Every BASELINE config
+            # and north_star's DLT, one short entry each, in the tail.
+            line["summary"] = summary_of(line)
+    for b_ in {id(b_): b_ for b_ in (bt, bto) if b_ is not None}.values():
         b_.close()
     if dist is not None:
         dist.destroy_process_group()

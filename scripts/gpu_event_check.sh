@@ -3,7 +3,7 @@
 # SAME launches?  One-stream bench under the profiler; the trace's last 2 x N fused launches are the bracketed and the attached
 # timing loops (bench.py runs them last when the other legs are switched off).
 ROOT=$PWD; OUT=$ROOT/gpurun_out/evcheck; mkdir -p $OUT; export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --streams 1 --steps 200 --warmup 20 --repeats 3 --no-cpu-baseline --no-extra --no-per-frame --large-frames 0"
+BENCH="python $ROOT/bench.py --full --streams 1 --steps 200 --warmup 20 --repeats 3 --no-cpu-baseline --no-extra --no-per-frame --large-frames 0"
 cd /tmp
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o stats -- $BENCH > $OUT/bench_under_rocprof.log 2>&1
 cd $ROOT

@@ -7,8 +7,8 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 # the bench commands whose JSON lines the numbers below belong to (configs[1]: 10 000 frames per launch)
-BENCH="python $ROOT/bench.py --streams 1 --steps 200 --warmup 20 --repeats 3 --no-cpu-baseline --no-extra --no-per-frame --large-frames 0"   # one stream: launches do not overlap, so the trace duration is the kernel duration
-LARGE="python $ROOT/bench.py --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-extra --no-per-frame --large-frames 2000000"
+BENCH="python $ROOT/bench.py --full --streams 1 --steps 200 --warmup 20 --repeats 3 --no-cpu-baseline --no-extra --no-per-frame --large-frames 0"   # one stream: launches do not overlap, so the trace duration is the kernel duration
+LARGE="python $ROOT/bench.py --full --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-extra --no-per-frame --large-frames 2000000"
 cd /tmp
 # 1. per-kernel time (no counters)
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o stats -- $BENCH > $OUT/stats_bench.log 2>&1
@@ -42,8 +42,8 @@ PY
 # the bench lines without the profiler: the default run and the driver's command (with this run's PMC summary in place, so
 # that the lines quote the traffic and the VALU count measured on exactly these kernel sources)
 cp $OUT/pmc_traffic.json $ROOT/profiles/pmc_traffic.json
-python bench.py 2>/dev/null | tail -1 > $OUT/bench_default.json
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_steps20.json
+python bench.py --full 2>/dev/null | tail -1 > $OUT/bench_default.json
+python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > $OUT/bench_steps20.json
 # events against the trace of the same launches (one-stream command under the profiler, then without it)
 bash scripts/gpu_event_check.sh > $OUT/event_check.log 2>&1; cp gpurun_out/evcheck/event_check.json $OUT/event_check.json
 # keep the merge small: drop raw traces, keep CSV summaries

@@ -71,12 +71,17 @@ def knobs(monkeypatch):
 
 
 def load_scenarios(name):
-    """tests/golden/<name>.npz -> {scenario: {field: array}} (schema: tests/golden/make_golden.py)."""
-    z = np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """tests/golden/<name>.npz -> {scenario: {field: array}} (schema: tests/golden/make_golden.py).  A fixture above the
+    size limit of a committed file goes on in <stem>_part2.npz, _part3.npz, ... (make_golden.save_scenarios): read as one."""
+    stem = name[:-len(".npz")]
+    parts = sorted((fn for fn in os.listdir(GOLDEN) if fn.startswith(stem + "_part") and fn.endswith(".npz")),
+                   key=lambda fn: int(fn[len(stem + "_part"):-len(".npz")]))
     out = {}
-    for key in z.files:
-        s, f = key.split("/", 1)
-        out.setdefault(s, {})[f] = z[key]
+    for fn in [name] + parts:
+        z = np.load(os.path.join(GOLDEN, fn), allow_pickle=False)
+        for key in z.files:
+            s, f = key.split("/", 1)
+            out.setdefault(s, {})[f] = z[key]
     for sc in out.values():
         sc["params"] = json.loads(str(sc["params"]))
     return out

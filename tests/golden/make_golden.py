@@ -129,14 +129,37 @@ def run_reference(K, R, t, kpts, n_persons, params, cand_frames=()):
     return out
 
 
+PART_LIMIT = 900 * 1024     # a committed file stays below 1 MiB: a larger fixture goes on in <stem>_part2.npz, _part3.npz, ...
+
+
+def _flat(scenarios):
+    return {f"{sname}/{k}": v for sname, sc in scenarios.items() for k, v in sc.items()}
+
+
+def _npz_bytes(scenarios):
+    import io
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **_flat(scenarios))
+    return len(buf.getvalue())
+
+
 def save_scenarios(name, scenarios):
-    flat = {}
+    """Whole scenarios, in order, into name and as many <stem>_part<n>.npz as the size limit needs (conftest.load_scenarios
+    reads them back as one)."""
+    parts = [{}]
     for sname, sc in scenarios.items():
-        for k, v in sc.items():
-            flat[f"{sname}/{k}"] = v
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **flat)
-    print(f"{name}: {os.path.getsize(path) / 1e6:.2f} MB, scenarios: {list(scenarios)}")
+        if parts[-1] and _npz_bytes(dict(parts[-1], **{sname: sc})) > PART_LIMIT:
+            parts.append({})
+        parts[-1][sname] = sc
+    stem = name[:-len(".npz")]
+    for fn in os.listdir(HERE):
+        if fn.startswith(stem + "_part") and fn.endswith(".npz"):
+            os.remove(os.path.join(HERE, fn))
+    for i, part in enumerate(parts):
+        fn = name if i == 0 else f"{stem}_part{i + 1}.npz"
+        path = os.path.join(HERE, fn)
+        np.savez_compressed(path, **_flat(part))
+        print(f"{fn}: {os.path.getsize(path) / 1e6:.2f} MB, scenarios: {list(part)}")
 
 
 # ----------------------------------------------------------------------------------------------

@@ -106,9 +106,13 @@ def test_second_order_dynamic_matches_reference_track():
     assert sod.k2 == pytest.approx(1.0 / (4 * np.pi * 2.0) ** 2 * 4)   # 1/(2 pi f)^2
 
 
-def test_util_helpers(tmp_path):
+def test_util_helpers(tmp_path, monkeypatch):
+    # Check_If_File_Exist splits the name at its one '.' (as the reference does), and the temporary directory's own
+    # path may hold dots: work inside it with a relative name
+    monkeypatch.chdir(tmp_path)
     p = tmp_path / "out.json"
     assert Check_If_File_Exist(str(p)) == (False, str(p))
+    p = p.relative_to(tmp_path)
     p.write_text("{\"a\": 1}")
     assert Load_Config_Json(str(p)) == {"a": 1}
     exists, alt = Check_If_File_Exist(str(p))

@@ -92,3 +92,28 @@ def test_summary_is_the_last_key_and_small():
     assert s["configs2_8x4_no_zero_fill"]["output_MB_written_per_call"] < s["configs2_8x4_no_zero_fill"]["output_MB_written_per_call_default"]
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.index('line["summary"] = summary_of(line)') > src.index('"extra_workloads": extra,')      # appended behind everything else
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs (no GPU): the outputs of a call as <name>.npy in float32 / float64, integer fields exact; above the size
+    limit a seeded sample of frames, the same from run to run, with frame_index.npy naming them."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    F = 50
+    out = dict(xyzs=torch.arange(F * 2 * 4, dtype=torch.float32).view(F, 1, 2, 4), pscore=torch.rand(F, 1, dtype=torch.float32),
+               count=torch.arange(F, dtype=torch.int32), flags=torch.full((F,), 4, dtype=torch.int32))
+    bench.dump_outputs(str(tmp_path / "all"), out)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").glob("*.npy")}
+    assert sorted(got) == ["count", "flags", "pscore", "xyzs"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    for k, v in out.items():
+        assert np.array_equal(got[k], v.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 20 * (32 + 4 + 8 + 8 + 8))     # room for 20 frames (and their index)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    idx = np.load(tmp_path / "s1" / "frame_index.npy")
+    assert len(idx) == 20 and np.array_equal(idx, np.load(tmp_path / "s2" / "frame_index.npy")) and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "s1" / "count.npy"), idx)
+    assert np.array_equal(np.load(tmp_path / "s1" / "xyzs.npy"), out["xyzs"].numpy()[idx.astype(int)])

@@ -16,7 +16,7 @@ def test_two_ranks_on_one_device_print_one_whole_job_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     K, F = 6, 4000
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-device", "--steps", str(K), "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-device", "--full", "--steps", str(K), "--warmup", "2",
                         "--repeats", "3", "--frames", str(F), "--pool", "4", "--large-frames", "0", "--device-warmup-ms", "50",
                         "--no-extra", "--no-cpu-baseline", "--no-per-frame", "--chunks", "auto,2"],
                        env=env, capture_output=True, text=True, timeout=600)
