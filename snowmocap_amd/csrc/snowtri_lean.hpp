@@ -17,7 +17,9 @@
 //     of the stored score); the 1/2000 of triangulation.py:72 is applied once to the score sum; the keypoint
 //     gate (:73) is evaluated once per camera into a lane mask; exact intersection / singular pair / NaN are
 //     detected on the score sum; the per-pair offsets d = t_s - t_m live in scalar registers (one SGPR operand
-//     per v_fma_f64, no LDS read, no VGPR); item -> (frame, joint) uses the compile-time J; loads and stores
+//     per v_fma_f64, no LDS read, no VGPR); k_fused_lean_coop<4, float> holds M and t in VGPRs across its item
+//     loop as well (lean_rig_regs_load: no LDS read of a rig constant per item); item -> (frame, joint) uses the
+//     compile-time J; loads and stores
 //     go through BUFFER instructions whose descriptor covers exactly the wave's tile: the byte offset of item
 //     lane + 64 k inside a tile is the same for every tile, so it comes from a small LDS table (no division, no
 //     64-bit address arithmetic, no clamp), lanes past the end of the tile read zeros and their stores are
@@ -44,6 +46,11 @@ namespace snowtri {
 #endif
 constexpr int kLeanRolledWaves = SNOWTRI_LEAN_ROLLED_WAVES, kLeanRolledRing = SNOWTRI_LEAN_ROLLED_RING;   // (A/B builds override them)
 constexpr int kLeanRolledGroup = SNOWTRI_LEAN_ROLLED_GROUP;   // pairs between two scheduling barriers of the item
+#ifndef SNOWTRI_LEAN_AUTO_RESIDENT
+#define SNOWTRI_LEAN_AUTO_RESIDENT 0
+#endif
+constexpr bool kLeanAutoResident = SNOWTRI_LEAN_AUTO_RESIDENT;   // k_fused_lean holds M, t in VGPRs as k_fused_lean_coop<4, float> does (A/B builds:
+                                                                // off, it spills at 4 cameras and its large launch did not gain)
 // float64 outputs (the reference's own output type) exist on the rolled item only -- cluster_item<..., double> refines 1/dist by a
 // Newton step, lean_item carries the raw v_rsq_f64 of the float32 contract -- so five cameras roll too when they are asked for.
 template <int C, typename TOut = float>
@@ -120,11 +127,23 @@ __device__ __forceinline__ float select_by_mask(float x, unsigned long long mask
     return r;
 }
 
+// The rig constants lean_item reads, Kr[12 C] = M[C][9] then t[C][3] as they lie at the front of the LDS, held in VGPRs by the wave
+// across its item loop: filled once after the barrier that publishes them, so that the item reads none of them from LDS
+// (24 wide LDS reads per 4-camera item, each writing the same values into 64 lanes).
+template <int NK>
+__device__ __forceinline__ void lean_rig_regs_load(double (&Kr)[NK], const double *__restrict__ Mlds) {
+#pragma unroll
+    for (int i = 0; i < NK; i++) Kr[i] = Mlds[i];
+#pragma unroll
+    for (int i = 0; i < NK; i++) asm volatile("" : "+v"(Kr[i]));   // loaded here, once: not re-read from LDS in the loop
+}
+
 // One (frame, joint): C rays, all C(C,2) pair solves, score-weighted fusion (see pairwise_item for the
 // algebra of the fusion regrouped per ray; here the determinants cancel out of it: no reciprocal per pair).  Returns
-// true if the item needs the IEEE-exact routine.
-template <int C, typename TIn>
-__device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds,
+// true if the item needs the IEEE-exact routine.  The rig constants come from the registers of `Kr` (kResident) or from
+// LDS, read by every item (Mlds); the arithmetic, and so every bit of the result, is the same either way.
+template <int C, bool kResident, typename TIn, int NK>
+__device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const double (&Kr)[NK],
                                           const double (&dS)[3 * (C * (C - 1) / 2)],
                                           const Kp3<TIn> (&cur)[C], float kthr_f32, double kthr, double dthr2,
                                           float &ox, float &oy, float &oz, double &os) {
@@ -134,10 +153,18 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds,
 #pragma clang fp contract(off)
     constexpr int NPc = C * (C - 1) / 2;
     double Mp[9 * C];
+    const double *tp;
+    if constexpr (kResident) {
+        static_assert(NK == 12 * C, "Kr: M[C][9], t[C][3]");
 #pragma unroll
-    for (int i = 0; i < 9 * C; i++) Mp[i] = Mlds[i];
-    __builtin_amdgcn_sched_barrier(0);  // one burst of LDS reads, one wait (+2.5 % measured in round 1)
-    const double *tp = Mlds + 9 * C;
+        for (int i = 0; i < 9 * C; i++) Mp[i] = Kr[i];
+        tp = Kr + 9 * C;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9 * C; i++) Mp[i] = Mlds[i];
+        __builtin_amdgcn_sched_barrier(0);  // one burst of LDS reads, one wait (+2.5 % measured in round 1)
+        tp = Mlds + 9 * C;
+    }
     Vec3 h[C];
     double a[C], alpha[C], beta[C];
     unsigned long long okm[C];
@@ -238,9 +265,9 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds,
 }
 
 // The item of a rig: lean_item up to five cameras, cluster_item (float32 outputs: raw v_rsq_f64, the same contract) beyond.
-template <int C, typename TIn, int ND>
-__device__ __forceinline__ bool lean_solve(const double *__restrict__ Mlds, const double (&dS)[ND], const Kp3<TIn> (&cur)[C], float kthr_f32,
-                                           double kthr, double dthr2, float &ox, float &oy, float &oz, double &os) {
+template <int C, bool kResident, typename TIn, int NK, int ND>
+__device__ __forceinline__ bool lean_solve(const double *__restrict__ Mlds, const double (&Kr)[NK], const double (&dS)[ND], const Kp3<TIn> (&cur)[C],
+                                           float kthr_f32, double kthr, double dthr2, float &ox, float &oy, float &oz, double &os) {
     if constexpr (LeanShape<C>::kRolled) {
         double x, y, z;
         asm volatile("" ::: "memory");   // the rig constants are re-read from LDS by every item (hoisted out of the item loop they take hundreds of registers)
@@ -250,19 +277,20 @@ __device__ __forceinline__ bool lean_solve(const double *__restrict__ Mlds, cons
         oz = (float)z;
         return bad;
     } else {
-        return lean_item<C>(Mlds, dS, cur, kthr_f32, kthr, dthr2, ox, oy, oz, os);
+        return lean_item<C, kResident>(Mlds, Kr, dS, cur, kthr_f32, kthr, dthr2, ox, oy, oz, os);
     }
 }
 
 // One item solved, its joint record stored (non-temporal, range-checked by the descriptor) and its score stashed for the frame's
 // mean: float32 records through lean_solve, float64 records (two 16-byte stores) through cluster_item's Newton-refined branch.
-template <int C, typename TIn, typename TOut, int ND>
-__device__ __forceinline__ bool lean_solve_store(const double *__restrict__ Mlds, const double (&dS)[ND], const Kp3<TIn> (&cur)[C], float kthr_f32,
-                                                 double kthr, double dthr2, __amdgpu_buffer_rsrc_t rout, unsigned out_off, TOut *stash_slot) {
+template <int C, bool kResident, typename TIn, typename TOut, int NK, int ND>
+__device__ __forceinline__ bool lean_solve_store(const double *__restrict__ Mlds, const double (&Kr)[NK], const double (&dS)[ND],
+                                                 const Kp3<TIn> (&cur)[C], float kthr_f32, double kthr, double dthr2,
+                                                 __amdgpu_buffer_rsrc_t rout, unsigned out_off, TOut *stash_slot) {
     if constexpr (sizeof(TOut) == 4) {
         float ox, oy, oz;
         double os;
-        const bool bad = lean_solve<C>(Mlds, dS, cur, kthr_f32, kthr, dthr2, ox, oy, oz, os);
+        const bool bad = lean_solve<C, kResident>(Mlds, Kr, dS, cur, kthr_f32, kthr, dthr2, ox, oy, oz, os);
         const float osf = (float)os;
         lean_u4 rec;
         rec.x = __float_as_uint(ox);
@@ -394,6 +422,8 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     const double cD = rig.pairc[tid < 3 * NP ? 6 * (tid / 3) + tid % 3 : 0];
     const int32_t cP = rig.pairs[tid < 2 * NP ? tid : 0];
     double dS[kRolled ? 1 : 3 * NP];  // per-pair d = t_s - t_m, wave-uniform -> scalar registers (cluster_item reads them from LDS)
+    constexpr bool kResident = !kRolled && kLeanAutoResident;
+    double Kr[kResident ? 12 * C : 1];  // M and t in VGPRs across the item loop (kResident), else read from LDS by every item
     if constexpr (!kRolled) {
 #pragma unroll
         for (int i = 0; i < 3 * NP; i++) dS[i] = rig.pairc[6 * (i / 3) + i % 3];
@@ -424,6 +454,7 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     const double kthr = prm.kthr, dthr2 = prm.dthr2;
     const double ctol2_lo = prm.ctol < 0.0 ? -1.0 : prm.ctol * prm.ctol * (1.0 - 1e-12);   // single-cluster check, see there
     __syncthreads();  // constants, table and the cleared slow-frame bits are visible to every wave
+    if constexpr (kResident) lean_rig_regs_load(Kr, Mlds);
 
     for (int ord = 0; tile < ntiles; tile += wstride, ord++) {
         SNOWTRI_DEV_CHECK(f0 >= 0 && nf >= 1 && nf <= kLeanTw && f0 + nf <= F, 1);                 // the tile lies inside the batch
@@ -451,7 +482,7 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
         // item `is` + 64 k of the lane: output record at byte 16 (is + 64 k), stash slot is + 64 k.  Lanes past the
         // tile's last item work on zeros; their store is out of the descriptor's range and their stash slot is padding.
         auto solve_store = [&](const Kp3<TIn>(&buf)[C], unsigned out_off, TOut *stash_slot) {
-            const bool bad = lean_solve_store<C, TIn, TOut>(Mlds, dS, buf, kthr_f32, kthr, dthr2, rout, out_off, stash_slot);
+            const bool bad = lean_solve_store<C, kResident, TIn, TOut>(Mlds, Kr, dS, buf, kthr_f32, kthr, dthr2, rout, out_off, stash_slot);
             if (__ballot(bad)) {  // rare, wave-uniform branch
                 unsigned o = out_off;
                 asm volatile("" : "+v"(o));  // (keeps the bit arithmetic below inside the branch)
@@ -688,6 +719,11 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     const double cD = rig.pairc[tid < 3 * NP ? 6 * (tid / 3) + tid % 3 : 0];
     const int32_t cP = rig.pairs[tid < 2 * NP ? tid : 0];
     double dS[kRolled ? 1 : 3 * NP];
+    // M and t in VGPRs across the item loop where they fit: 4 cameras, float32 keypoints (the bench's shape; 247 VGPRs with the
+    // pair offsets below, two waves per SIMD as the launch bounds allow).  5 cameras and float64 keypoints would spill, 3 cameras
+    // would drop from 4 to 2 waves per SIMD: those, and the rolled item, read the constants from LDS item by item.
+    constexpr bool kResident = !kRolled && C == 4 && sizeof(TIn) == 4;
+    double Kr[kResident ? 12 * C : 1];
     if constexpr (!kRolled) {
 #pragma unroll
         for (int i = 0; i < 3 * NP; i++) dS[i] = rig.pairc[6 * (i / 3) + i % 3];
@@ -712,12 +748,19 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
 #pragma unroll
         for (int i = 0; i < 3 * NP; i++) dS[i] = uniform_f64(dS[i]);
     }
+    if constexpr (kResident) {
+        // with M and t resident, the offsets of the first two pairs go to VGPRs as well (12 of them): 12 scalar registers fewer
+        // to spill (38 -> 29 SGPRs spilled; no spill reload left on the item loop's common path)
+#pragma unroll
+        for (int i = 0; i < 6; i++) asm volatile("" : "+v"(dS[i]));
+    }
     const float kthr_f32 = prm.kthr_f32;
     const double kthr = prm.kthr, dthr2 = prm.dthr2;
     const double ctol2_lo = prm.ctol < 0.0 ? -1.0 : prm.ctol * prm.ctol * (1.0 - 1e-12);
     SNOWTRI_STAMP(1);
     __syncthreads();
     SNOWTRI_STAMP(2);
+    if constexpr (kResident) lean_rig_regs_load(Kr, Mlds);
     {
         const int wl = lane / NP, qq = lane - wl * NP, w = pos * kCheckFrames + wl;
         const bool live = pos < ncheck && wl < kCheckFrames && w < nf;
@@ -727,7 +770,7 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     }
 
     auto solve_store = [&](const Kp3<TIn>(&buf)[C], unsigned out_off, TOut *stash_slot) {
-        const bool bad = lean_solve_store<C, TIn, TOut>(Mlds, dS, buf, kthr_f32, kthr, dthr2, rout, out_off, stash_slot);
+        const bool bad = lean_solve_store<C, kResident, TIn, TOut>(Mlds, Kr, dS, buf, kthr_f32, kthr, dthr2, rout, out_off, stash_slot);
         if (__ballot(bad)) {  // rare, wave-uniform branch
             unsigned o = out_off;
             asm volatile("" : "+v"(o));
