@@ -115,6 +115,13 @@ _SIGNATURES = {
     "snowtri_blender_smooth_shard_local": (ct.c_int, [_c_p, ct.c_int64, ct.c_int64, _c_p, ct.c_int, _c_p, ct.c_double, _c_p, _c_p, _c_p]),
     "snowtri_blender_smooth_shard_combine": (ct.c_int, [_c_p, ct.c_int32, ct.c_int32, ct.c_int64, _c_p, _c_p, ct.c_double, _c_p, _c_p]),
     "snowtri_blender_smooth_shard_fix": (ct.c_int, [_c_p, ct.c_int64, ct.c_int64, ct.c_int, _c_p, _c_p, ct.c_double, _c_p, _c_p]),
+    "snowtri_track_state_bytes": (ct.c_size_t, [ct.c_int32]),
+    "snowtri_track_block_frames": (ct.c_int, []),
+    "snowtri_track_persons": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, _c_p, ct.c_int32, ct.c_int32,
+                                         ct.c_double, ct.c_int32, _c_p, _c_p, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_track_last_ms": (ct.c_int, [_c_p, ct.POINTER(ct.c_float * 2)]),
+    "snowtri_track_gather": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, _c_p,
+                                        ct.c_int, _c_p]),
     "snowtri_ctx_set_distortion": (ct.c_int, [_c_p, _c_p]),
     "snowtri_undistort_keypoints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, _c_p, ct.c_int,
                                                ct.c_int, _c_p]),

@@ -31,6 +31,7 @@
 #include "snowtri_smooth.hpp"
 #include "snowtri_blender.hpp"
 #include "snowtri_undistort.hpp"
+#include "snowtri_track.hpp"
 #include "snowtri_kernels.hpp"
 
 using namespace snowtri;
@@ -210,6 +211,9 @@ struct snowtri_ctx {
     Scratch &desc = sets[0].desc;             // cluster descriptors handed from k_frame_recompute / k_associate to k_cluster_fuse
     Scratch &sums = sets[0].sums;             // candidate sums of k_candidate_sums [frames][Kc] + the frames k_associate left behind
     Scratch in, out, aux;
+    Scratch track;                            // centres [F][Pout_max][4] fp64 of snowtri_track_persons (k_track_centres -> k_track_chain)
+    hipEvent_t track_ev[3] = {nullptr, nullptr, nullptr};   // with timing on: before k_track_centres | between | behind k_track_chain
+    bool track_ev_valid = false;
     PinnedScratch pin_in, pin_out;            // host staging of the per-frame calls
     PinnedScratch pin_done;                   // the completion word of the small host calls (HostDone, snowtri_kernels.hpp)
     unsigned long long done_seq = 0;
@@ -549,6 +553,9 @@ int snowtri_ctx_destroy(snowtri_ctx *ctx) {
     ctx->in.release();
     ctx->out.release();
     ctx->aux.release();
+    ctx->track.release();
+    for (auto &e : ctx->track_ev)
+        if (e) (void)hipEventDestroy(e);
     ctx->cand.release();
     ctx->pin_done.release();
     ctx->pin_probe.release();
@@ -1852,6 +1859,152 @@ int snowtri_blender_smooth(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const
     if (rc) return rc;
     if (memspace == SNOWTRI_HOST) {
         HIP_TRY(hipMemcpyAsync(out, dy, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SNOWTRI_OK;
+}
+
+// ------------------------------------------------------------------------------- person tracking
+static int track_fail(int status, const char *msg) {
+    g_last_error = msg;
+    return status;
+}
+static size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+size_t snowtri_track_state_bytes(int32_t S) { return (S < 1 || S > kTrackMax) ? 0 : track_state_bytes(S); }
+int snowtri_track_block_frames(void) { return kTrackBlockFrames; }
+
+int snowtri_track_persons(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t keypoint_num, const void *xyzs, int xyz_dtype,
+                          const int32_t *count, int32_t S, int32_t center_point_index, double gate, int32_t max_missed, void *state,
+                          int32_t *slot_of, int32_t *person_of, int32_t *track_id, uint32_t *flags, int memspace, void *stream) {
+    if (!ctx) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: null context");
+    if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
+        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: unknown dtype or memory space");
+    if (F < 0 || keypoint_num < 1) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: F < 0 or keypoint_num < 1");
+    if (S < 1 || S > kTrackMax || Pout_max < 1 || Pout_max > kTrackMax)
+        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: S and Pout_max must lie in 1..16");
+    if (!(gate >= 0.0) || !std::isfinite(gate)) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: gate must be finite and >= 0");
+    if (max_missed < 0) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: max_missed must be >= 0");
+    if (center_point_index < 0 || center_point_index >= keypoint_num)
+        return track_fail(SNOWTRI_ERR_BAD_INDEX, "snowtri_track_persons: center_point_index outside [0, keypoint_num)");
+    if (F == 0) return SNOWTRI_OK;
+    if (!xyzs || !count || !slot_of || !person_of || !track_id) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: null array");
+    if (memspace == SNOWTRI_DEVICE && (((uintptr_t)xyzs & 15u) || (state && ((uintptr_t)state & 7u))))
+        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: xyzs must be aligned to 16 bytes, state to 8");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int P = Pout_max;
+    const size_t esz = dtype_size(xyz_dtype);
+    const size_t x_bytes = esz * 4 * (size_t)keypoint_num * P * F, c_bytes = sizeof(int32_t) * (size_t)F;
+    const size_t so_bytes = sizeof(int32_t) * (size_t)F * P, po_bytes = sizeof(int32_t) * (size_t)F * S, st_bytes = track_state_bytes(S);
+    int rc = ctx->track.ensure(sizeof(double) * 4 * (size_t)F * P);
+    if (rc) return rc;
+    const void *dx = xyzs;
+    const int32_t *dc = count;
+    int32_t *d_so = slot_of, *d_po = person_of, *d_id = track_id;
+    uint32_t *d_fl = flags;
+    unsigned char *d_state = (unsigned char *)state;
+    if (memspace == SNOWTRI_HOST) {
+        rc = ctx->in.ensure(pad16(x_bytes) + c_bytes);
+        if (rc) return rc;
+        rc = ctx->out.ensure(pad16(so_bytes) + 2 * pad16(po_bytes) + pad16(c_bytes) + st_bytes);
+        if (rc) return rc;
+        unsigned char *din = (unsigned char *)ctx->in.p, *dout = (unsigned char *)ctx->out.p;
+        HIP_TRY(hipMemcpyAsync(din, xyzs, x_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes), count, c_bytes, hipMemcpyHostToDevice, st));
+        dx = din;
+        dc = (const int32_t *)(din + pad16(x_bytes));
+        d_so = (int32_t *)dout;
+        d_po = (int32_t *)(dout + pad16(so_bytes));
+        d_id = (int32_t *)(dout + pad16(so_bytes) + pad16(po_bytes));
+        d_fl = flags ? (uint32_t *)(dout + pad16(so_bytes) + 2 * pad16(po_bytes)) : nullptr;
+        if (state) {
+            d_state = dout + pad16(so_bytes) + 2 * pad16(po_bytes) + pad16(c_bytes);
+            HIP_TRY(hipMemcpyAsync(d_state, state, st_bytes, hipMemcpyHostToDevice, st));
+        }
+    }
+    double *d_cen = (double *)ctx->track.p;
+    const dim3 grid((unsigned)(((int64_t)F * P + 255) / 256));
+    if ((int64_t)F * P > (int64_t)0x7fffffff * 256) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: too many frames for one call");
+    const bool timed = ctx->timing;
+    ctx->track_ev_valid = false;
+    if (timed) {
+        for (auto &e : ctx->track_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ctx->track_ev[0], st));
+    }
+    if (xyz_dtype == SNOWTRI_F32)
+        hipLaunchKernelGGL(k_track_centres<float>, grid, dim3(256), 0, st, F, P, (int)keypoint_num, (int)center_point_index, (const float *)dx, dc, d_cen);
+    else
+        hipLaunchKernelGGL(k_track_centres<double>, grid, dim3(256), 0, st, F, P, (int)keypoint_num, (int)center_point_index, (const double *)dx, dc, d_cen);
+    if (timed) HIP_TRY(hipEventRecord(ctx->track_ev[1], st));
+    hipLaunchKernelGGL(k_track_chain, dim3(1), dim3(kTrackChainThreads), 0, st, F, P, (int)S, gate * gate, (int)max_missed, (const double *)d_cen, d_state,
+                       d_so, d_po, d_id, d_fl);
+    HIP_TRY(hipGetLastError());
+    if (timed) {
+        HIP_TRY(hipEventRecord(ctx->track_ev[2], st));
+        ctx->track_ev_valid = true;
+    }
+    if (memspace == SNOWTRI_HOST) {
+        HIP_TRY(hipMemcpyAsync(slot_of, d_so, so_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(person_of, d_po, po_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(track_id, d_id, po_bytes, hipMemcpyDeviceToHost, st));
+        if (flags) HIP_TRY(hipMemcpyAsync(flags, d_fl, c_bytes, hipMemcpyDeviceToHost, st));
+        if (state) HIP_TRY(hipMemcpyAsync(state, d_state, st_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SNOWTRI_OK;
+}
+
+int snowtri_track_last_ms(snowtri_ctx *ctx, float kernel_ms[2]) {
+    if (!ctx || !kernel_ms) return SNOWTRI_ERR_BAD_ARG;
+    kernel_ms[0] = kernel_ms[1] = 0.f;
+    if (!ctx->track_ev_valid) return SNOWTRI_ERR_BAD_ARG;
+    ENTER_DEVICE(ctx->device);
+    HIP_TRY(hipEventSynchronize(ctx->track_ev[2]));
+    HIP_TRY(hipEventElapsedTime(&kernel_ms[0], ctx->track_ev[0], ctx->track_ev[1]));
+    HIP_TRY(hipEventElapsedTime(&kernel_ms[1], ctx->track_ev[1], ctx->track_ev[2]));
+    return SNOWTRI_OK;
+}
+
+int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t keypoint_num, const void *xyzs, int xyz_dtype, int32_t S,
+                         const int32_t *person_of, void *xyzs_tracked, int memspace, void *stream) {
+    if (!ctx) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: null context");
+    if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
+        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: unknown dtype or memory space");
+    if (F < 0 || keypoint_num < 1) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: F < 0 or keypoint_num < 1");
+    if (S < 1 || S > kTrackMax || Pout_max < 1 || Pout_max > kTrackMax)
+        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: S and Pout_max must lie in 1..16");
+    if (F == 0) return SNOWTRI_OK;
+    if (!xyzs || !person_of || !xyzs_tracked) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: null array");
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) | ((uintptr_t)xyzs_tracked)) & 15u))
+        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: xyzs and xyzs_tracked must be aligned to 16 bytes");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t person_bytes = dtype_size(xyz_dtype) * 4 * (size_t)keypoint_num;
+    const size_t x_bytes = person_bytes * Pout_max * F, o_bytes = person_bytes * S * F, po_bytes = sizeof(int32_t) * (size_t)F * S;
+    const void *dx = xyzs;
+    const int32_t *d_po = person_of;
+    void *d_out = xyzs_tracked;
+    if (memspace == SNOWTRI_HOST) {
+        int rc = ctx->in.ensure(pad16(x_bytes) + po_bytes);
+        if (rc) return rc;
+        rc = ctx->out.ensure(o_bytes);
+        if (rc) return rc;
+        unsigned char *din = (unsigned char *)ctx->in.p;
+        HIP_TRY(hipMemcpyAsync(din, xyzs, x_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes), person_of, po_bytes, hipMemcpyHostToDevice, st));
+        dx = din;
+        d_po = (const int32_t *)(din + pad16(x_bytes));
+        d_out = ctx->out.p;
+    }
+    const int rec_per_person = (int)(person_bytes / 16);
+    const int64_t total = (int64_t)F * S * rec_per_person;
+    hipLaunchKernelGGL(k_track_gather, dim3(grid_for(total, 256, ctx->num_cus * 16)), dim3(256), 0, st, F, (int)Pout_max, (int)S, rec_per_person,
+                       (const uint4 *)dx, d_po, (uint4 *)d_out);
+    HIP_TRY(hipGetLastError());
+    if (memspace == SNOWTRI_HOST) {
+        HIP_TRY(hipMemcpyAsync(xyzs_tracked, d_out, o_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return SNOWTRI_OK;

@@ -38,7 +38,7 @@ class TrackPipeline:
     def close(self):
         self.bt.close()
 
-    def run(self, kpts, n_persons=None, check=True, ragged="reference"):
+    def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -50,7 +50,13 @@ class TrackPipeline:
         filter over the frames with tracked > i: those are gathered, filtered by the same kernels and scattered back;
         slots at or behind tracked[f] hold zeros.  Frame 0 must fit the slots (count[0] <= n_persons_out).
         ragged="refuse": raise unless every frame resolves to exactly n_persons_out persons (round 4's behaviour).
-        check=False skips the host read of counts and flags and treats every slot of every frame as tracked."""
+        check=False skips the host read of counts and flags and treats every slot of every frame as tracked.
+        ragged="track": persons are matched ACROSS FRAMES instead of by list index (tracking.PersonTracker on the n_persons_out
+        slots: greedy nearest-centre matching within track_gate metres, a slot is given up after track_max_missed frames without
+        its person).  Every array is then indexed by SLOT -- xyzs is the tracked gather of the triangulated persons (their list
+        order is kept in xyzs_listed / slot_of) -- and each track id is filtered over the frames in which it occupies its slot,
+        so a slot that is re-used by a new id starts fresh filters.  Adds present [F, P] (bool) and track_id [F, P]; tracked [F]
+        counts the present slots (they need not be a prefix: pass present= to to_blender_result).  Reads track_id on the host."""
         import torch
         dev = torch.device("cuda", self.device)
         if not torch.is_tensor(kpts):
@@ -67,7 +73,7 @@ class TrackPipeline:
             flg = tri["flags"].cpu().numpy()
             if (flg & _lib.FLAG_SINGULAR).any():    # the reference's np.linalg.inv raises (triangulation.py:26)
                 raise np.linalg.LinAlgError(f"Singular matrix (frame {int(np.argmax((flg & _lib.FLAG_SINGULAR) != 0))})")
-            if not (cnt == self.P).all():
+            if ragged != "track" and not (cnt == self.P).all():
                 if ragged == "refuse":
                     bad = int(np.argmax(cnt != self.P))
                     raise ValueError(f"frame {bad} resolved to {int(cnt[bad])} persons, the track is built for {self.P}")
@@ -84,6 +90,42 @@ class TrackPipeline:
             _lib.check(L.snowtri_blender_points(h, n, self.kn, ct.c_void_p(x.data_ptr()), _lib.F64, ct.c_void_p(p_out.data_ptr()),
                                                 ct.c_void_p(v_out.data_ptr()), _lib.DEVICE, st), "snowtri_blender_points")
 
+        def filter_rows(src, idx, i, sm, pts_s):
+            """slot i over the frames idx (the first of them seeds the filters): gather, N1, N2 points, N2 filters, scatter"""
+            T = int(idx.numel())
+            xi = src[idx, i].contiguous()                                   # [T, kn, 4]
+            si = torch.empty_like(xi)
+            _lib.check(L.snowtri_smooth_joint_track(h, T, self.kn, ct.c_void_p(xi.data_ptr()), *fzrd, ct.c_void_p(si.data_ptr()),
+                                                    _lib.DEVICE, st), "snowtri_smooth_joint_track")
+            pi = torch.empty((T, 1, 24, 4), dtype=torch.float64, device=dev)
+            vi = torch.empty((T, 1, 24), dtype=torch.uint8, device=dev)
+            blender_points(si, T, pi, vi)
+            qi = torch.empty_like(pi)
+            _lib.check(L.snowtri_blender_smooth(h, T, 1, ct.c_void_p(pi.data_ptr()), ct.c_void_p(vi.data_ptr()),
+                                                _lib.ptr(self.fzr), fzrd[3], ct.c_void_p(qi.data_ptr()), _lib.DEVICE, st),
+                       "snowtri_blender_smooth")
+            sm[idx, i] = si
+            pts[idx, i] = pi[:, 0]
+            val[idx, i] = vi[:, 0]
+            pts_s[idx, i] = qi[:, 0]
+
+        if ragged == "track":
+            from .tracking import PersonTracker
+            trk_out = PersonTracker(self.bt.ctx, S=self.P, center_point_index=self.bt.params.center_point_index, gate=track_gate,
+                                    max_missed=track_max_missed).run_torch(xyzs, tri["count"], gather=True, carry=False)
+            listed, xyzs = xyzs, trk_out["xyzs_tracked"]
+            tid = trk_out["track_id"].cpu().numpy()                          # the host decides which frames a track covers
+            sm = torch.zeros_like(xyzs)
+            pts.zero_()
+            val.zero_()
+            pts_s = torch.zeros_like(pts)
+            for i in range(self.P):
+                for one in np.unique(tid[:, i][tid[:, i] >= 0]):
+                    filter_rows(xyzs, torch.from_numpy(np.nonzero(tid[:, i] == one)[0]).to(dev), i, sm, pts_s)
+            present = trk_out["person_of"] >= 0
+            return dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"], flags=tri["flags"],
+                        tracked=present.sum(dim=1).to(torch.int32), present=present, track_id=trk_out["track_id"],
+                        slot_of=trk_out["slot_of"], track_flags=trk_out["flags"], xyzs_listed=listed)
         if tracked is None:
             sm = torch.empty_like(xyzs)                    # only the points are filtered, the scores copied (triangulation.py:169-184)
             _lib.check(L.snowtri_smooth_joint_track(h, F, self.P * self.kn, ct.c_void_p(xyzs.data_ptr()), *fzrd, ct.c_void_p(sm.data_ptr()),
@@ -102,31 +144,16 @@ class TrackPipeline:
             val.zero_()
             pts_s = torch.zeros_like(pts)
             for i in range(int(tracked[0]) if F else 0):
-                idx = torch.nonzero(trk > i).view(-1)
-                T = int(idx.numel())
-                xi = xyzs[idx, i].contiguous()                                  # [T, kn, 4]
-                si = torch.empty_like(xi)
-                _lib.check(L.snowtri_smooth_joint_track(h, T, self.kn, ct.c_void_p(xi.data_ptr()), *fzrd, ct.c_void_p(si.data_ptr()),
-                                                        _lib.DEVICE, st), "snowtri_smooth_joint_track")
-                pi = torch.empty((T, 1, 24, 4), dtype=torch.float64, device=dev)
-                vi = torch.empty((T, 1, 24), dtype=torch.uint8, device=dev)
-                blender_points(si, T, pi, vi)
-                qi = torch.empty_like(pi)
-                _lib.check(L.snowtri_blender_smooth(h, T, 1, ct.c_void_p(pi.data_ptr()), ct.c_void_p(vi.data_ptr()),
-                                                    _lib.ptr(self.fzr), fzrd[3], ct.c_void_p(qi.data_ptr()), _lib.DEVICE, st),
-                           "snowtri_blender_smooth")
-                sm[idx, i] = si
-                pts[idx, i] = pi[:, 0]
-                val[idx, i] = vi[:, 0]
-                pts_s[idx, i] = qi[:, 0]
+                filter_rows(xyzs, torch.nonzero(trk > i).view(-1), i, sm, pts_s)
         return dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"],
                     flags=tri["flags"], tracked=trk)
 
     @staticmethod
-    def to_blender_result(points_smoothed, valid, armature_profile=None, tracked=None):
+    def to_blender_result(points_smoothed, valid, armature_profile=None, tracked=None, present=None):
         """Device (or NumPy) track -> the list the reference dumps with save_blender_result (blender.py:180-187):
         one {'armature': [per person {name: list}], 'score': [per person {name: 0/1}]} per frame.  tracked [F]: persons
-        frame f carries (run()'s "tracked"; default: every slot)."""
+        frame f carries (run()'s "tracked"; default: every slot).  present [F, P] (run(ragged="track")): the slots frame f
+        carries, listed in slot order; it replaces `tracked`."""
         pts = points_smoothed.cpu().numpy() if hasattr(points_smoothed, "cpu") else np.asarray(points_smoothed)
         val = valid.cpu().numpy() if hasattr(valid, "cpu") else np.asarray(valid)
         if tracked is None:
@@ -134,6 +161,8 @@ class TrackPipeline:
         else:
             trk = (tracked.cpu().numpy() if hasattr(tracked, "cpu") else np.asarray(tracked)).astype(np.int64)
         live = np.arange(pts.shape[1])[None, :] < trk[:, None]
+        if present is not None:
+            live = (present.cpu().numpy() if hasattr(present, "cpu") else np.asarray(present)).astype(bool)
         if not val[..., 1][live].all():
             raise np.linalg.LinAlgError("SVD did not converge")     # the reference raises on a NaN pelvis matrix
         names = list(armature_profile.keys()) if armature_profile is not None else list(CONTROL_POINT_NAMES)
@@ -141,8 +170,8 @@ class TrackPipeline:
         frames = []
         for f in range(pts.shape[0]):
             frames.append({
-                "armature": [{n: pts[f, p, slot[n], :_WIDTH[n]].tolist() for n in names} for p in range(int(trk[f]))],
-                "score": [{n: int(val[f, p, slot[n]]) for n in names} for p in range(int(trk[f]))]})
+                "armature": [{n: pts[f, p, slot[n], :_WIDTH[n]].tolist() for n in names} for p in np.nonzero(live[f])[0]],
+                "score": [{n: int(val[f, p, slot[n]]) for n in names} for p in np.nonzero(live[f])[0]]})
         return frames
 
 

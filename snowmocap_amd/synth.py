@@ -191,3 +191,43 @@ def config_workload_device(cfg, F, seed, device, chunk=20000, dtype=None):
             kpts[lo:lo + n, c] = rec.to(kpts.dtype)
     n_persons = torch.full((F, C), P, dtype=torch.int32, device=dev)
     return dict(rig=(K, R, t), params=base["params"], kpts=kpts, n_persons=n_persons)
+
+
+def make_walkers(rng, F, P, step, J=J_WHOLEBODY, circle_radius=1.5, box=(0.6, 0.6, 1.8), phase=0.0):
+    """World joints X[F, P, J, 3] of P walkers and their centres [F, P, 3] (on the floor): every person keeps ONE fixed
+    skeleton (joint offsets uniform in `box`, drawn once) whose centre moves `step` metres per frame along the circle of
+    `circle_radius`, the persons evenly spaced on it -- smooth paths, constant mutual distances."""
+    off = rng.uniform(0.0, 1.0, size=(P, J, 3))
+    off[..., 0] = (off[..., 0] - 0.5) * box[0]
+    off[..., 1] = (off[..., 1] - 0.5) * box[1]
+    off[..., 2] = off[..., 2] * box[2]
+    ang = phase + 2.0 * np.pi * np.arange(P)[None, :] / P + (step / circle_radius) * np.arange(F)[:, None]      # [F, P]
+    centres = np.stack([circle_radius * np.cos(ang), circle_radius * np.sin(ang), np.zeros_like(ang)], axis=-1)
+    return centres[:, :, None, :] + off[None], centres
+
+
+def make_keypoints_visible(rng, K, R, t, X, visible=None, pixel_sigma=1.0, score_range=(3.5, 8.0), permute_persons=True,
+                           dtype=np.float32):
+    """make_keypoints for persons that come and go: visible [F, P] bool (default: everybody) says who is in frame f; every
+    camera lists the visible persons of a frame -- in an independent random order with `permute_persons`, else in person
+    order -- and n_persons[f, c] counts them (slots behind it are zero).  The pixel noise and the scores are drawn per
+    (frame, camera, TRUE person) BEFORE the lists are ordered, so the same generator state gives the same detections with
+    and without the permutation: only the list order differs.  Returns kpts [F, C, P, J, 3], n_persons [F, C]."""
+    F, P, J, _ = X.shape
+    C = K.shape[0]
+    vis = np.ones((F, P), dtype=bool) if visible is None else np.asarray(visible, dtype=bool).reshape(F, P)
+    uv, _ = project(K, R, t, X)
+    uv = np.moveaxis(uv, 0, 1)                       # [F, C, P, J, 2]
+    if pixel_sigma > 0:
+        uv = uv + rng.normal(0.0, pixel_sigma, size=uv.shape)
+    sc = rng.uniform(score_range[0], score_range[1], size=(F, C, P, J))
+    rec = np.concatenate([uv, sc[..., None]], axis=-1)
+    kpts = np.zeros((F, C, P, J, 3), dtype=dtype)
+    n_persons = np.zeros((F, C), dtype=np.int32)
+    for f in range(F):
+        who = np.nonzero(vis[f])[0]
+        for c in range(C):
+            order = rng.permutation(who) if permute_persons else who
+            kpts[f, c, :len(order)] = rec[f, c, order]
+            n_persons[f, c] = len(order)
+    return kpts, n_persons
