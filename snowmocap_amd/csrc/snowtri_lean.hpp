@@ -16,7 +16,9 @@
 //   * A shorter item (lean_item): 1/dist is the raw v_rsq_f64 (measured 2^-24.2 relative, below the float32 rounding
 //     of the stored score); the 1/2000 of triangulation.py:72 is applied once to the score sum; the keypoint
 //     gate (:73) is evaluated once per camera into a lane mask; exact intersection / singular pair / NaN are
-//     detected on the score sum; the per-pair offsets d = t_s - t_m live in scalar registers (one SGPR operand
+//     detected on the score sum; the world origin is moved to camera 0 (t'_c = t_c - t_0: camera 0 drops out of the sums, the
+//     triple product of a pair needs no cross product of its own, t_0 is added to the fused point at the end);
+//     the per-pair offsets d = t_s - t_m live in scalar registers (one SGPR operand
 //     per v_fma_f64, no LDS read, no VGPR); k_fused_lean_coop<4, float> holds M and t in VGPRs across its item
 //     loop as well (lean_rig_regs_load: no LDS read of a rig constant per item); item -> (frame, joint) uses the
 //     compile-time J; loads and stores
@@ -127,13 +129,18 @@ __device__ __forceinline__ float select_by_mask(float x, unsigned long long mask
     return r;
 }
 
-// The rig constants lean_item reads, Kr[12 C] = M[C][9] then t[C][3] as they lie at the front of the LDS, held in VGPRs by the wave
-// across its item loop: filled once after the barrier that publishes them, so that the item reads none of them from LDS
-// (24 wide LDS reads per 4-camera item, each writing the same values into 64 lanes).
+// The rig constants lean_item reads, Kr[12 C] = M[C][9], t_0, then t'_c = t_c - t_0 for c = 1 .. C-1 (the item works in camera 0's
+// coordinates, see there), held in VGPRs by the wave across its item loop: filled once after the barrier that publishes them, so
+// that the item reads none of them from LDS (24 wide LDS reads per 4-camera item, each writing the same values into 64 lanes).
+// M and t_0 lie at the front of the LDS; t'_c is the offset d of pair (0, c), the first C-1 entries of d[NP][3] behind t[C][3]:
+// the very doubles snowtri_ctx_create subtracted for the pair offsets, so d of pair (0, c) and t'_c are the same bits.
 template <int NK>
 __device__ __forceinline__ void lean_rig_regs_load(double (&Kr)[NK], const double *__restrict__ Mlds) {
+    constexpr int C = NK / 12;
 #pragma unroll
-    for (int i = 0; i < NK; i++) Kr[i] = Mlds[i];
+    for (int i = 0; i < 9 * C + 3; i++) Kr[i] = Mlds[i];
+#pragma unroll
+    for (int i = 9 * C + 3; i < NK; i++) Kr[i] = Mlds[i + 3 * C - 3];   // d[c - 1] at 12 C + 3 (c - 1)
 #pragma unroll
     for (int i = 0; i < NK; i++) asm volatile("" : "+v"(Kr[i]));   // loaded here, once: not re-read from LDS in the loop
 }
@@ -142,6 +149,11 @@ __device__ __forceinline__ void lean_rig_regs_load(double (&Kr)[NK], const doubl
 // algebra of the fusion regrouped per ray; here the determinants cancel out of it: no reciprocal per pair).  Returns
 // true if the item needs the IEEE-exact routine.  The rig constants come from the registers of `Kr` (kResident) or from
 // LDS, read by every item (Mlds); the arithmetic, and so every bit of the result, is the same either way.
+//
+// The item works in CAMERA 0's COORDINATES: t'_c = t_c - t_0, so t'_0 = 0 and the pair offsets d = t'_s - t'_m are what they were.
+// t'_c (c >= 1) is the offset of pair (0, c): the first C-1 entries of dS, or the t part of Kr (kResident; those entries of dS
+// are then not read and cost no register).  Camera 0 drops out of the weighted sum of centres, t_0 is added to the fused point
+// at the end, and the triple product n = d . (h_m x h_s) needs no cross product per pair (below).
 template <int C, bool kResident, typename TIn, int NK>
 __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const double (&Kr)[NK],
                                           const double (&dS)[3 * (C * (C - 1) / 2)],
@@ -155,7 +167,7 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
     double Mp[9 * C];
     const double *tp;
     if constexpr (kResident) {
-        static_assert(NK == 12 * C, "Kr: M[C][9], t[C][3]");
+        static_assert(NK == 12 * C, "Kr: M[C][9], t_0, t'[1 .. C-1][3]");
 #pragma unroll
         for (int i = 0; i < 9 * C; i++) Mp[i] = Kr[i];
         tp = Kr + 9 * C;
@@ -165,7 +177,16 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
         __builtin_amdgcn_sched_barrier(0);  // one burst of LDS reads, one wait (+2.5 % measured in round 1)
         tp = Mlds + 9 * C;
     }
-    Vec3 h[C];
+    // tq[3 c ..] = t'_c for c >= 1 (tq[0 .. 2] stays unused: t'_0 = 0); tp[0 .. 2] = t_0 is read where it is added, at the end
+    double tq[3 * C];
+#pragma unroll
+    for (int i = 3; i < 3 * C; i++) {
+        if constexpr (kResident)
+            tq[i] = Kr[9 * C + i];
+        else
+            tq[i] = dS[i - 3];
+    }
+    Vec3 h[C], X[C];
     double a[C], alpha[C], beta[C];
     unsigned long long okm[C];
 #pragma unroll
@@ -181,6 +202,12 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
             okm[c] = __ballot(!((float)cur[c].s < kthr_f32));
         else
             okm[c] = __ballot(!((double)cur[c].s < kthr));
+        // X_c = h_c x t'_c, once per camera (X_0 = 0): the triple product of a pair is h_m . X_s + h_s . X_m
+        if (c >= 1) {
+            X[c].x = fma(h[c].y, tq[3 * c + 2], -(h[c].z * tq[3 * c + 1]));
+            X[c].y = fma(h[c].z, tq[3 * c + 0], -(h[c].x * tq[3 * c + 2]));
+            X[c].z = fma(h[c].x, tq[3 * c + 1], -(h[c].y * tq[3 * c + 0]));
+        }
     }
     // A2 + :72-74 per camera pair WITHOUT a reciprocal of the determinant.  For rays t_m + S0 h_m and t_s - S1 h_s:
     //   S0 = N0 / det, S1 = N1 / det,  N0 = a_s e - b g,  N1 = a_m g - b e,  det = a_m a_s - b^2 = |h_m x h_s|^2,
@@ -188,9 +215,13 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
     // so with rho = rsq(n^2 det):  1 / dist = rho det, and the pair's weight 2000 x score = ssum / dist = (ssum rho) det:
     //   sq S0 = (ssum rho) N0,   sq S1 = (ssum rho) N1,   sq = (ssum rho) det
     // -- the determinant cancels out of the fused point's numerators: one VALU instruction per pair less and no shared
-    // reciprocal (no chain over the pairs, no range of a product to watch).  Conditioning: n cancels to dist |h_m x h_s|
-    // from terms of size |d| |h_m| |h_s|, 1e-16 |d| / dist relative -- the same cancellation as ||Wm - Ws|| from
-    // 5 m coordinates in the reference.  The gate dist > dthr (:74) is taken on n^2 > dthr^2 det (both sides x det > 0).
+    // reciprocal (no chain over the pairs, no range of a product to watch).  n = d . (h_m x h_s) is formed as
+    // h_m . (h_s x t'_s) + h_s . (h_m x t'_m) = h_m . X_s + h_s . X_m (three instructions for the pairs of camera 0, a chain of six
+    // for the others, where a cross product per pair took nine; only n^2 is used).  Conditioning: n cancels to dist |h_m x h_s|
+    // from terms of size |t'| |h_m| |h_s|, 1e-16 (rig diameter) / dist relative -- the same cancellation as ||Wm - Ws|| from
+    // 5 m coordinates in the reference (the cross product per pair cancelled terms of the size of the pair's own baseline |d|:
+    // for two cameras close to each other and far from camera 0 this form is the less exact one, within the same bound;
+    // tests/test_lean_item_algebra.py).  The gate dist > dthr (:74) is taken on n^2 > dthr^2 det (both sides x det > 0).
     // A singular pair (a c == b b in separately rounded products: det = 0 exactly) or an exact intersection (n = 0) give
     // rho = inf, a negative (rounding of nearly parallel rays) or NaN determinant rho = NaN: they reach the score sum,
     // whatever the gates select (0 x inf = NaN).
@@ -200,16 +231,18 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
 #pragma unroll
         for (int sc = mc + 1; sc < C; sc++, q++) {
             const Vec3 &hm = h[mc], &hs = h[sc];
-            const double dx = dS[3 * q], dy = dS[3 * q + 1], dz = dS[3 * q + 2];
+            // d = t'_s - t'_m: t'_s itself for the pairs of camera 0 (q = s - 1)
+            const double dx = mc == 0 ? tq[3 * sc] : dS[3 * q], dy = mc == 0 ? tq[3 * sc + 1] : dS[3 * q + 1],
+                         dz = mc == 0 ? tq[3 * sc + 2] : dS[3 * q + 2];
             const double b = dot3(hm, hs);
             const double det = a[mc] * a[sc] - b * b;   // separately rounded products (contraction off): singular as the reference sees it <=> det == 0 exactly (cluster_item)
             const double e = fma(hm.z, dz, fma(hm.y, dy, hm.x * dx));
             const double g = fma(hs.z, dz, fma(hs.y, dy, hs.x * dx));
             const double N0 = fma(a[sc], e, -(b * g));
             const double N1 = fma(a[mc], g, -(b * e));
-            // n = h_m . (h_s x d)
-            const double cx = fma(hs.y, dz, -(hs.z * dy)), cy = fma(hs.z, dx, -(hs.x * dz)), cz = fma(hs.x, dy, -(hs.y * dx));
-            const double n = fma(hm.z, cz, fma(hm.y, cy, hm.x * cx));
+            // n = h_m . X_s + h_s . X_m
+            double n = fma(hm.z, X[sc].z, fma(hm.y, X[sc].y, hm.x * X[sc].x));
+            if (mc >= 1) n = fma(hs.z, X[mc].z, fma(hs.y, X[mc].y, fma(hs.x, X[mc].x, n)));
             const double n2 = n * n;
             const double rho = __builtin_amdgcn_rsq(n2 * det);
             // :72-74  score = ((sm+ss)/2) / (dist*1000), zeroed by the three gates; w det = 2000 x that score
@@ -241,23 +274,35 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
             }
         }
     }
+    // the weighted sum relative to camera 0 (beta_0 t'_0 = 0)
     double sx = alpha[0] * h[0].x, sy = alpha[0] * h[0].y, sz = alpha[0] * h[0].z, sb = beta[0];
-    sx = fma(beta[0], tp[0], sx);
-    sy = fma(beta[0], tp[1], sy);
-    sz = fma(beta[0], tp[2], sz);
 #pragma unroll
     for (int c = 1; c < C; c++) {
-        sx = fma(alpha[c], h[c].x, fma(beta[c], tp[3 * c + 0], sx));
-        sy = fma(alpha[c], h[c].y, fma(beta[c], tp[3 * c + 1], sy));
-        sz = fma(alpha[c], h[c].z, fma(beta[c], tp[3 * c + 2], sz));
+        sx = fma(alpha[c], h[c].x, fma(beta[c], tq[3 * c + 0], sx));
+        sy = fma(alpha[c], h[c].y, fma(beta[c], tq[3 * c + 1], sy));
+        sz = fma(alpha[c], h[c].z, fma(beta[c], tq[3 * c + 2], sz));
         sb += beta[c];
     }
-    // sb = 2 x 2000 x sum_q s_q (:141).  sum == 0 -> the joint stays (0,0,0)/0 (:142-143): sx = sy = sz = 0 then,
-    // so any finite reciprocal will do: 1 / max(sb, 1e-300) saves the compare-and-select.
-    const double r = rcp_nr1(fmax(sb, 1e-300));
-    ox = (float)(sx * r);  // :144-147 as (sum s (Wm+Ws)) / (2 sum s)
-    oy = (float)(sy * r);
-    oz = (float)(sz * r);
+    // sb = 2 x 2000 x sum_q s_q (:141).  sum == 0 -> the joint stays (0,0,0)/0 (:142-143), NOT t_0: one compare into a lane
+    // mask and a 32-bit select per coordinate (which also cover the reciprocal of 0: no clamp of sb before it; sb < 0 does not occur: the
+    // dispatch sends only kthr >= 0 to these kernels, so every score that passes the gate is >= 0).
+    const double r = rcp_nr1(sb);
+    const unsigned long long scored = __ballot(sb != 0.0);
+    const double px = fma(sx, r, tp[0]), py = fma(sy, r, tp[1]), pz = fma(sz, r, tp[2]);  // :144-147 as t_0 + (sum s (Wm+Ws - 2 t_0)) / (2 sum s)
+    if constexpr (C == 3) {
+        // Three cameras: the select clears the HIGH word of the double -- what is left is below 2^-1042 and converts to +0.0f,
+        // the same bits as the select below.  k_fused_lean<3, float> fits 128 VGPRs this way (125; 129 with the select on the
+        // float, which costs it its fourth wave per SIMD); the other rigs take the select on the float: on the high word
+        // k_fused_lean_coop<4, float> gets six v_mov_b64 more per item and k_fused_lean<5, double> spills.  Both kernels
+        // of a rig take the same form, and both forms give the same bits.
+        ox = (float)__hiloint2double(__float_as_int(select_by_mask(__int_as_float(__double2hiint(px)), scored)), __double2loint(px));
+        oy = (float)__hiloint2double(__float_as_int(select_by_mask(__int_as_float(__double2hiint(py)), scored)), __double2loint(py));
+        oz = (float)__hiloint2double(__float_as_int(select_by_mask(__int_as_float(__double2hiint(pz)), scored)), __double2loint(pz));
+    } else {
+        ox = select_by_mask((float)px, scored);
+        oy = select_by_mask((float)py, scored);
+        oz = select_by_mask((float)pz, scored);
+    }
     os = sb * (0.00025 / (double)NPc);  // :148
     // dist == 0 or a singular pair (rho = inf), a negative determinant or NaN input (rho = NaN) leave sum s inf or NaN:
     // the IEEE-exact routine decides those frames
@@ -719,8 +764,8 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     const double cD = rig.pairc[tid < 3 * NP ? 6 * (tid / 3) + tid % 3 : 0];
     const int32_t cP = rig.pairs[tid < 2 * NP ? tid : 0];
     double dS[kRolled ? 1 : 3 * NP];
-    // M and t in VGPRs across the item loop where they fit: 4 cameras, float32 keypoints (the bench's shape; 247 VGPRs with the
-    // pair offsets below, two waves per SIMD as the launch bounds allow).  5 cameras and float64 keypoints would spill, 3 cameras
+    // M, t_0 and t' in VGPRs across the item loop where they fit: 4 cameras, float32 keypoints (the bench's shape; two waves
+    // per SIMD as the launch bounds allow).  5 cameras and float64 keypoints would spill, 3 cameras
     // would drop from 4 to 2 waves per SIMD: those, and the rolled item, read the constants from LDS item by item.
     constexpr bool kResident = !kRolled && C == 4 && sizeof(TIn) == 4;
     double Kr[kResident ? 12 * C : 1];
@@ -748,12 +793,8 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
 #pragma unroll
         for (int i = 0; i < 3 * NP; i++) dS[i] = uniform_f64(dS[i]);
     }
-    if constexpr (kResident) {
-        // with M and t resident, the offsets of the first two pairs go to VGPRs as well (12 of them): 12 scalar registers fewer
-        // to spill (38 -> 29 SGPRs spilled; no spill reload left on the item loop's common path)
-#pragma unroll
-        for (int i = 0; i < 6; i++) asm volatile("" : "+v"(dS[i]));
-    }
+    // (kResident: the offsets of the pairs of camera 0 are the t' of Kr, the item reads only the other pairs' from dS -- 9 pairs of
+    // scalar registers fewer)
     const float kthr_f32 = prm.kthr_f32;
     const double kthr = prm.kthr, dthr2 = prm.dthr2;
     const double ctol2_lo = prm.ctol < 0.0 ? -1.0 : prm.ctol * prm.ctol * (1.0 - 1e-12);
