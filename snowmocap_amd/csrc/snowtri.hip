@@ -2100,6 +2100,16 @@ int launch_fused_lean(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_
     auto kern = k_fused_lean<C, TIn, kLeanJ, TOut>;
     const int64_t W_small = (int64_t)ctx->num_cus * wg_small * kLeanWaves;
     const int64_t seg_max = (int64_t)kLeanTw * kLeanWaves * 512 * ((int64_t)ctx->num_cus * 6);  // <= 512 tiles per wave
+    // lean_item's lengths in units of lambda = distance_threshold (snowtri_lean.hpp); the rolled item takes none of this
+    LeanUnits<C, TOut> un{};
+    if constexpr (LeanUnits<C, TOut>::kUsed) {
+        un.lam = prm.dthr;
+        un.inv = 1.0 / prm.dthr;
+        un.kos = (0.00025 / (double)NP) / prm.dthr;
+        for (int q = 0; q < NP; q++)
+            for (int i = 0; i < 3; i++)   // d = t_s - t_m as snowtri_ctx_create subtracted them for Rig::pairc, times 1 / lambda
+                un.d[3 * q + i] = (ctx->ht[3 * ctx->hpairs[2 * q + 1] + i] - ctx->ht[3 * ctx->hpairs[2 * q] + i]) * un.inv;
+    }
     // small launch (at most kCoopMaxFrames frames per resident workgroup): workgroup tiles, passes dealt to the waves,
     // cooperative epilogue (k_fused_lean_coop)
     if (ctx->lean_coop != 0 && F <= (int64_t)ctx->num_cus * wg_small * kCoopMaxFrames) {
@@ -2118,11 +2128,11 @@ int launch_fused_lean(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_
             // them (what rocprofv3's kernel trace reads), without the two barrier packets of a bracketing pair in the interval
             const int64_t slot = ctx->ev_count % kTimingRing;
             hipExtLaunchKernelGGL(kc, dim3(grid), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
-                                  F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
+                                  F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, un, d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
             ctx->ev_attached = true;
         } else {
-            hipLaunchKernelGGL(kc, dim3(grid), dim3(kBlock), lds, st, F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl,
-                               (char *)ctx->cur->work.p, per_block);
+            hipLaunchKernelGGL(kc, dim3(grid), dim3(kBlock), lds, st, F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, un, d_xyzs, d_ps, d_cnt,
+                               d_fl, (char *)ctx->cur->work.p, per_block);
         }
         HIP_TRY(hipGetLastError());
         static const std::string cname = std::string("k_fused_lean_coop<") + std::to_string(C) + "," + type_name<TIn>() + "," +
@@ -2172,12 +2182,12 @@ int launch_fused_lean(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_
         if (ctx->timing && ctx->timing_attach && Fs == F) {   // one segment = one kernel: its own begin / end (see k_fused_lean_coop above)
             const int64_t slot = ctx->ev_count % kTimingRing;
             hipExtLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
-                                  Fs, ntiles, base, rem, slow_words, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl,
+                                  Fs, ntiles, base, rem, slow_words, ctx->rig(), d_kpts, d_np, prm, un, d_xyzs, d_ps, d_cnt, d_fl,
                                   (char *)ctx->cur->work.p, per_block);
             ctx->ev_attached = true;
         } else {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, Fs, ntiles, base, rem, slow_words, ctx->rig(),
-                               d_kpts + s0 * (int64_t)(C * kLeanJ * 3), d_np ? d_np + s0 * C : nullptr, prm,
+                               d_kpts + s0 * (int64_t)(C * kLeanJ * 3), d_np ? d_np + s0 * C : nullptr, prm, un,
                                d_xyzs + s0 * (int64_t)(kLeanJ * 4), d_ps ? d_ps + s0 : nullptr, d_cnt + s0,
                                d_fl ? d_fl + s0 : nullptr, (char *)ctx->cur->work.p, per_block);
         }
@@ -2659,8 +2669,11 @@ int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J,
     ctx->ev_attached = false;
     // (float64 outputs -- the reference's own output type -- on the lean kernels from five cameras on: the rolled item's
     // Newton-refined branch; up to four cameras they stay on k_fused_single<C,0,TIn,double>)
+    // (lean_item -- float32 outputs up to five cameras -- measures lengths in units of distance_threshold: a threshold outside
+    // lean_units_ok, i.e. not in [2^-64, 2^64] m or NaN, takes the route below as if there were no lean kernel; the rolled item keeps metres)
+    const bool lean_item_shape = std::is_same<TOut, float>::value && C <= 5;
     const bool lean = method != SNOWTRI_DLT && fast && (std::is_same<TOut, float>::value || C >= 5) && J == kLeanJ && prm.kn == kLeanJ &&
-                      Pout == 1 && ctx->lean_mode != 0;
+                      Pout == 1 && ctx->lean_mode != 0 && (!lean_item_shape || lean_units_ok(prm.dthr));
     // Five cameras and more on any other shape (float64 outputs, keypoint_num < J, other skeletons, several slots): the
     // unrolled pairwise_item of k_fused_single does not fit the register file there (10-28 pairs: 41-1 075 spilled VGPRs, round-4
     // review).  Those calls take the streaming route WITHOUT its candidate pass (launch_frame_recompute: `sumless`): with one

@@ -23,9 +23,18 @@
 //     loop as well (lean_rig_regs_load: no LDS read of a rig constant per item); item -> (frame, joint) uses the
 //     compile-time J; loads and stores
 //     go through BUFFER instructions whose descriptor covers exactly the wave's tile: the byte offset of item
-//     lane + 64 k inside a tile is the same for every tile, so it comes from a small LDS table (no division, no
-//     64-bit address arithmetic, no clamp), lanes past the end of the tile read zeros and their stores are
-//     dropped by the range check of the hardware.
+//     lane + 64 k inside a tile is the same for every tile, so k_fused_lean, whose waves run many tiles, takes it from a
+//     small LDS table (no division, no 64-bit address arithmetic, no clamp), and k_fused_lean_coop, whose waves run ten
+//     passes of one tile, steps it in scalar registers (no table: its build was ~100 VALU per wave for ten reads per lane);
+//     lanes past the end of the tile read zeros and their stores are dropped by the range check of the hardware.
+//   * LENGTHS IN UNITS OF lambda = distance_threshold.  The gate dist > lambda (:74) was n^2 > lambda^2 det: a product per pair
+//     that serves only the comparison.  With the pair offsets divided by lambda (on the host, once per launch: LeanUnits) n comes
+//     out in units of lambda and the gate is n^2 > det.  Rays are not scaled, so det, the exact zero of an exact intersection
+//     and rsq(0) = inf are what they were.  The weights come out times lambda and the sums of length x weight unscaled, so
+//     the fused point is t_0 + (sum / weight) lambda -- one multiply of the reciprocal -- and the joint score takes 1 / lambda
+//     into its constant.  Thresholds outside lean_units_ok (not in [2^-64, 2^64] m: zero, negative, denormal, huge, inf, NaN)
+//     never get here: fused_dispatch routes such a call as if these kernels did not exist (no instruction in the item loop
+//     for them).  The rolled item (cluster_item) keeps metres.
 #pragma once
 #include "snowtri_fused.hpp"
 
@@ -68,7 +77,8 @@ constexpr int kLeanSlowShift = 4;        // slow-frame bit index = (tile ordinal
 
 __host__ __device__ constexpr int lean_items_pad(int JC) { return (kLeanTw * JC + 63) / 64 * 64; }   // item slots of a wave tile, whole passes
 __host__ __device__ constexpr int lean_table_entries(int JC) { return lean_items_pad(JC) + 256; }      // + the prefetch distance past the last pass
-__host__ __device__ constexpr int lean_const_doubles(int C) { return (12 * C + 4 * (C * (C - 1) / 2) + 1) & ~1; }  // M[C][9], t[C][3], d[NP][3], pairs[NP][2] (int32)
+__host__ __device__ constexpr int lean_const_doubles(int C) { return (12 * C + 7 * (C * (C - 1) / 2) + 1) & ~1; }  // M[C][9], t[C][3], d[NP][3], pairs[NP][2] (int32), d / lambda [NP][3]
+__host__ __device__ constexpr int lean_scaled_at(int C) { return 12 * C + 4 * (C * (C - 1) / 2); }                  // first double of d / lambda
 
 __host__ __device__ constexpr size_t lean_lds_bytes(int C, int JC, int slow_words, int score_bytes = 4) {
     const size_t stash = (size_t)kLeanWaves * lean_items_pad(JC) * score_bytes;   // fused joint scores as stored (float32 / float64), per wave
@@ -84,7 +94,26 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t lean_rsrc(const void *base, un
 // cache-policy bits of the buffer instructions (gfx942 / gfx950: 1 = sc0, 2 = nt, 16 = sc1)
 constexpr int kLeanStoreAux = 2;   // non-temporal output stores: the 21 MB a 10 000-frame launch writes leave the L2 while the launch
                                    // runs instead of as one write-back at its end (measured: 32.2 -> 31.3 us per launch)
-constexpr int kLeanLoadAux = 0;
+#ifndef SNOWTRI_LEAN_LOAD_AUX
+#define SNOWTRI_LEAN_LOAD_AUX 0
+#endif
+constexpr int kLeanLoadAux = SNOWTRI_LEAN_LOAD_AUX;   // keypoint loads: 0 measured against 2 (nt), 16 (sc1) and 18 in A/B builds (EXPERIMENTS.md, round 10)
+
+// lean_item measures lengths in units of lambda = distance_threshold (see there).  The host scales what the item reads, per launch,
+// and hands it over as a kernel argument (scalar registers, no instruction of the wave): the pair offsets d / lambda, lambda itself
+// and the constant of the joint score.  fused_dispatch sends a call to these kernels only if lean_units_ok(lambda).
+template <int C, typename TOut = float>
+struct LeanUnits {
+    static constexpr bool kUsed = !(C >= 6 || (C == 5 && sizeof(TOut) == 8));   // = !LeanShape<C, TOut>::kRolled: cluster_item keeps metres
+    double d[kUsed ? 3 * (C * (C - 1) / 2) : 1];   // (t_s - t_m) * inv, pair by pair in loop order
+    double inv;                                    // 1 / lambda, rounded once (the kernel scales its LDS copy of t' with the same multiply)
+    double lam;                                    // lambda: the fused point is t_0 + lambda * (sum / weight)
+    double kos;                                    // (0.00025 / pairs) / lambda: joint score = kos * sum of the scaled weights
+};
+// lambda in [2^-64, 2^64] metres: 1 / lambda and lambda^2 are normal numbers with 10^270 of range to spare on either side, so n^2 det
+// of the scaled item under- or overflows only where the unscaled one is within 10^-38 of doing so.  Zero, negative, denormal,
+// infinite and NaN thresholds are outside.
+__host__ __device__ constexpr bool lean_units_ok(double lam) { return lam >= 0x1p-64 && lam <= 0x1p64; }
 
 typedef unsigned lean_u3 __attribute__((ext_vector_type(3)));
 typedef unsigned lean_u4 __attribute__((ext_vector_type(4)));
@@ -129,18 +158,19 @@ __device__ __forceinline__ float select_by_mask(float x, unsigned long long mask
     return r;
 }
 
-// The rig constants lean_item reads, Kr[12 C] = M[C][9], t_0, then t'_c = t_c - t_0 for c = 1 .. C-1 (the item works in camera 0's
-// coordinates, see there), held in VGPRs by the wave across its item loop: filled once after the barrier that publishes them, so
+// The rig constants lean_item reads, Kr[12 C] = M[C][9], t_0 (metres), then t'_c = (t_c - t_0) / lambda for c = 1 .. C-1 (the item
+// works in camera 0's coordinates and in units of the distance threshold, see there), held in VGPRs by the wave across its item loop: filled once after the barrier that publishes them, so
 // that the item reads none of them from LDS (24 wide LDS reads per 4-camera item, each writing the same values into 64 lanes).
-// M and t_0 lie at the front of the LDS; t'_c is the offset d of pair (0, c), the first C-1 entries of d[NP][3] behind t[C][3]:
-// the very doubles snowtri_ctx_create subtracted for the pair offsets, so d of pair (0, c) and t'_c are the same bits.
+// M and t_0 lie at the front of the LDS; t'_c is the offset d of pair (0, c), the first C-1 entries of the scaled copy d / lambda
+// at lean_scaled_at(C): the doubles snowtri_ctx_create subtracted for the pair offsets times 1 / lambda, the same multiply the host
+// does for LeanUnits::d -- d / lambda of pair (0, c) and t'_c are the same bits wherever an instantiation takes them from.
 template <int NK>
 __device__ __forceinline__ void lean_rig_regs_load(double (&Kr)[NK], const double *__restrict__ Mlds) {
     constexpr int C = NK / 12;
 #pragma unroll
     for (int i = 0; i < 9 * C + 3; i++) Kr[i] = Mlds[i];
 #pragma unroll
-    for (int i = 9 * C + 3; i < NK; i++) Kr[i] = Mlds[i + 3 * C - 3];   // d[c - 1] at 12 C + 3 (c - 1)
+    for (int i = 9 * C + 3; i < NK; i++) Kr[i] = Mlds[lean_scaled_at(C) + i - (9 * C + 3)];   // d[c - 1] / lambda at lean_scaled_at + 3 (c - 1)
 #pragma unroll
     for (int i = 0; i < NK; i++) asm volatile("" : "+v"(Kr[i]));   // loaded here, once: not re-read from LDS in the loop
 }
@@ -150,20 +180,19 @@ __device__ __forceinline__ void lean_rig_regs_load(double (&Kr)[NK], const doubl
 // true if the item needs the IEEE-exact routine.  The rig constants come from the registers of `Kr` (kResident) or from
 // LDS, read by every item (Mlds); the arithmetic, and so every bit of the result, is the same either way.
 //
-// The item works in CAMERA 0's COORDINATES: t'_c = t_c - t_0, so t'_0 = 0 and the pair offsets d = t'_s - t'_m are what they were.
-// t'_c (c >= 1) is the offset of pair (0, c): the first C-1 entries of dS, or the t part of Kr (kResident; those entries of dS
-// are then not read and cost no register).  Camera 0 drops out of the weighted sum of centres, t_0 is added to the fused point
+// The item works in CAMERA 0's COORDINATES: t'_c = t_c - t_0, so t'_0 = 0 and the pair offsets d = t'_s - t'_m are what they were,
+// all of them in units of lambda (dS = LeanUnits::d).  t'_c (c >= 1) is the offset of pair (0, c): the first C-1 entries of dS, or
+// the t part of Kr (kResident; those entries of dS are then not read and cost no register).  Camera 0 drops out of the weighted sum of centres, t_0 is added to the fused point
 // at the end, and the triple product n = d . (h_m x h_s) needs no cross product per pair (below).
 template <int C, bool kResident, typename TIn, int NK>
 __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const double (&Kr)[NK],
                                           const double (&dS)[3 * (C * (C - 1) / 2)],
-                                          const Kp3<TIn> (&cur)[C], float kthr_f32, double kthr, double dthr2,
+                                          const Kp3<TIn> (&cur)[C], float kthr_f32, double kthr, double lam, double kos,
                                           float &ox, float &oy, float &oz, double &os) {
     // Every product-sum below that is meant to be fused is an explicit fma().  Implicit contraction is switched off:
     // the item is inlined three times (the prefetch ring) and the compiler may fuse `beta += x * y` differently in each
     // copy -- a frame's result would then depend (in the last bit) on which ring slot its position in the launch maps to.
 #pragma clang fp contract(off)
-    constexpr int NPc = C * (C - 1) / 2;
     double Mp[9 * C];
     const double *tp;
     if constexpr (kResident) {
@@ -221,7 +250,8 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
     // from terms of size |t'| |h_m| |h_s|, 1e-16 (rig diameter) / dist relative -- the same cancellation as ||Wm - Ws|| from
     // 5 m coordinates in the reference (the cross product per pair cancelled terms of the size of the pair's own baseline |d|:
     // for two cameras close to each other and far from camera 0 this form is the less exact one, within the same bound;
-    // tests/test_lean_item_algebra.py).  The gate dist > dthr (:74) is taken on n^2 > dthr^2 det (both sides x det > 0).
+    // tests/test_lean_item_algebra.py).  The gate dist > dthr (:74) is taken on n^2 > det (both sides x det > 0; n in units of
+    // dthr, see the top of this file: tq and dS hold t' / dthr and d / dthr).
     // A singular pair (a c == b b in separately rounded products: det = 0 exactly) or an exact intersection (n = 0) give
     // rho = inf, a negative (rounding of nearly parallel rays) or NaN determinant rho = NaN: they reach the score sum,
     // whatever the gates select (0 x inf = NaN).
@@ -246,7 +276,7 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
             const double n2 = n * n;
             const double rho = __builtin_amdgcn_rsq(n2 * det);
             // :72-74  score = ((sm+ss)/2) / (dist*1000), zeroed by the three gates; w det = 2000 x that score
-            const unsigned long long keep = okm[mc] & okm[sc] & __ballot(!(n2 > dthr2 * det));
+            const unsigned long long keep = okm[mc] & okm[sc] & __ballot(!(n2 > det));
             double w;
             if constexpr (sizeof(TIn) == 4) {
                 w = (double)select_by_mask((float)cur[mc].s + (float)cur[sc].s, keep) * rho;  // float32 sum as NumPy
@@ -286,7 +316,7 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
     // sb = 2 x 2000 x sum_q s_q (:141).  sum == 0 -> the joint stays (0,0,0)/0 (:142-143), NOT t_0: one compare into a lane
     // mask and a 32-bit select per coordinate (which also cover the reciprocal of 0: no clamp of sb before it; sb < 0 does not occur: the
     // dispatch sends only kthr >= 0 to these kernels, so every score that passes the gate is >= 0).
-    const double r = rcp_nr1(sb);
+    const double r = rcp_nr1(sb) * lam;   // sums of length / weight come out in units of 1 / lambda: back to metres here
     const unsigned long long scored = __ballot(sb != 0.0);
     const double px = fma(sx, r, tp[0]), py = fma(sy, r, tp[1]), pz = fma(sz, r, tp[2]);  // :144-147 as t_0 + (sum s (Wm+Ws - 2 t_0)) / (2 sum s)
     if constexpr (C == 3) {
@@ -303,7 +333,7 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
         oy = select_by_mask((float)py, scored);
         oz = select_by_mask((float)pz, scored);
     }
-    os = sb * (0.00025 / (double)NPc);  // :148
+    os = sb * kos;  // :148, kos = (0.00025 / pairs) / lambda
     // dist == 0 or a singular pair (rho = inf), a negative determinant or NaN input (rho = NaN) leave sum s inf or NaN:
     // the IEEE-exact routine decides those frames
     return !(sb < 1e300);
@@ -312,7 +342,8 @@ __device__ __forceinline__ bool lean_item(const double *__restrict__ Mlds, const
 // The item of a rig: lean_item up to five cameras, cluster_item (float32 outputs: raw v_rsq_f64, the same contract) beyond.
 template <int C, bool kResident, typename TIn, int NK, int ND>
 __device__ __forceinline__ bool lean_solve(const double *__restrict__ Mlds, const double (&Kr)[NK], const double (&dS)[ND], const Kp3<TIn> (&cur)[C],
-                                           float kthr_f32, double kthr, double dthr2, float &ox, float &oy, float &oz, double &os) {
+                                           float kthr_f32, double kthr, double dthr2, double lam, double kos, float &ox, float &oy, float &oz,
+                                           double &os) {
     if constexpr (LeanShape<C>::kRolled) {
         double x, y, z;
         asm volatile("" ::: "memory");   // the rig constants are re-read from LDS by every item (hoisted out of the item loop they take hundreds of registers)
@@ -322,7 +353,7 @@ __device__ __forceinline__ bool lean_solve(const double *__restrict__ Mlds, cons
         oz = (float)z;
         return bad;
     } else {
-        return lean_item<C, kResident>(Mlds, Kr, dS, cur, kthr_f32, kthr, dthr2, ox, oy, oz, os);
+        return lean_item<C, kResident>(Mlds, Kr, dS, cur, kthr_f32, kthr, lam, kos, ox, oy, oz, os);
     }
 }
 
@@ -330,12 +361,12 @@ __device__ __forceinline__ bool lean_solve(const double *__restrict__ Mlds, cons
 // mean: float32 records through lean_solve, float64 records (two 16-byte stores) through cluster_item's Newton-refined branch.
 template <int C, bool kResident, typename TIn, typename TOut, int NK, int ND>
 __device__ __forceinline__ bool lean_solve_store(const double *__restrict__ Mlds, const double (&Kr)[NK], const double (&dS)[ND],
-                                                 const Kp3<TIn> (&cur)[C], float kthr_f32, double kthr, double dthr2,
+                                                 const Kp3<TIn> (&cur)[C], float kthr_f32, double kthr, double dthr2, double lam, double kos,
                                                  __amdgpu_buffer_rsrc_t rout, unsigned out_off, TOut *stash_slot) {
     if constexpr (sizeof(TOut) == 4) {
         float ox, oy, oz;
         double os;
-        const bool bad = lean_solve<C, kResident>(Mlds, Kr, dS, cur, kthr_f32, kthr, dthr2, ox, oy, oz, os);
+        const bool bad = lean_solve<C, kResident>(Mlds, Kr, dS, cur, kthr_f32, kthr, dthr2, lam, kos, ox, oy, oz, os);
         const float osf = (float)os;
         lean_u4 rec;
         rec.x = __float_as_uint(ox);
@@ -423,7 +454,7 @@ __device__ __forceinline__ void lean_tile_range(int64_t t, int base, int64_t rem
 template <int C, typename TIn, int JC, typename TOut = float>
 __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_lean(
     int64_t F, int64_t ntiles, int tile_base, int64_t tile_rem, int slow_words, Rig rig, const TIn *__restrict__ kpts,
-    const int32_t *__restrict__ n_persons, Params prm, TOut *__restrict__ out4, TOut *__restrict__ out_ps,
+    const int32_t *__restrict__ n_persons, Params prm, LeanUnits<C, TOut> un, TOut *__restrict__ out4, TOut *__restrict__ out_ps,
     int32_t *__restrict__ out_count, uint32_t *__restrict__ out_flags, char *scratch, size_t scratch_per_block) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NP = C * (C - 1) / 2;
@@ -471,7 +502,7 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     double Kr[kResident ? 12 * C : 1];  // M and t in VGPRs across the item loop (kResident), else read from LDS by every item
     if constexpr (!kRolled) {
 #pragma unroll
-        for (int i = 0; i < 3 * NP; i++) dS[i] = rig.pairc[6 * (i / 3) + i % 3];
+        for (int i = 0; i < 3 * NP; i++) dS[i] = un.d[i];   // in units of lambda, from the kernel argument: scalar as they come
     }
     int64_t tile = (int64_t)blockIdx.x * kLeanWaves + wave;
     int64_t f0 = 0;
@@ -489,12 +520,11 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     if (tid < 9 * C) Mlds[tid] = cM;
     if (tid < 3 * C) Mlds[9 * C + tid] = cT;
     if (tid < 3 * NP) Mlds[12 * C + tid] = cD;
+    if constexpr (!kRolled) {   // the same offsets in units of lambda: the one multiply the host did for un.d (the same bits)
+        if (tid < 3 * NP) Mlds[lean_scaled_at(C) + tid] = cD * un.inv;
+    }
     int32_t *pairs_lds = reinterpret_cast<int32_t *>(Mlds + 12 * C + 3 * NP);
     if (tid < 2 * NP) pairs_lds[tid] = cP;
-    if constexpr (!kRolled) {
-#pragma unroll
-        for (int i = 0; i < 3 * NP; i++) dS[i] = uniform_f64(dS[i]);
-    }
     const float kthr_f32 = prm.kthr_f32;
     const double kthr = prm.kthr, dthr2 = prm.dthr2;
     const double ctol2_lo = prm.ctol < 0.0 ? -1.0 : prm.ctol * prm.ctol * (1.0 - 1e-12);   // single-cluster check, see there
@@ -527,7 +557,7 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
         // item `is` + 64 k of the lane: output record at byte 16 (is + 64 k), stash slot is + 64 k.  Lanes past the
         // tile's last item work on zeros; their store is out of the descriptor's range and their stash slot is padding.
         auto solve_store = [&](const Kp3<TIn>(&buf)[C], unsigned out_off, TOut *stash_slot) {
-            const bool bad = lean_solve_store<C, kResident, TIn, TOut>(Mlds, Kr, dS, buf, kthr_f32, kthr, dthr2, rout, out_off, stash_slot);
+            const bool bad = lean_solve_store<C, kResident, TIn, TOut>(Mlds, Kr, dS, buf, kthr_f32, kthr, dthr2, un.lam, un.kos, rout, out_off, stash_slot);
             if (__ballot(bad)) {  // rare, wave-uniform branch
                 unsigned o = out_off;
                 asm volatile("" : "+v"(o));  // (keeps the bit arithmetic below inside the branch)
@@ -692,16 +722,15 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
 constexpr int kCoopMaxFrames = 32;   // frames per workgroup tile (one bit word of slow frames)
 __host__ __device__ constexpr int lean_coop_items_pad(int JC, int nf_max) { return (nf_max * JC + 63) / 64 * 64; }
 __host__ __device__ constexpr size_t lean_coop_lds_bytes(int C, int JC, int nf_max, int score_bytes = 4) {
-    // [rig constants | item -> input offset table (+ 256 entries of prefetch distance) | stash | mean per frame | slow bits]
-    return (((size_t)8 * lean_const_doubles(C) + (size_t)4 * (lean_coop_items_pad(JC, nf_max) + 256) + (size_t)score_bytes * lean_coop_items_pad(JC, nf_max) +
-             (size_t)8 * kCoopMaxFrames + 16) + 15) & ~(size_t)15;
+    // [rig constants | stash | mean per frame | slow bits]
+    return (((size_t)8 * lean_const_doubles(C) + (size_t)score_bytes * lean_coop_items_pad(JC, nf_max) + (size_t)8 * kCoopMaxFrames + 16) + 15) & ~(size_t)15;
 }
 
 template <int C, typename TIn, int JC, typename TOut = float>
 __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_lean_coop(
     int64_t F, int tile_base, int64_t tile_rem, int nf_max, Rig rig, const TIn *__restrict__ kpts, const int32_t *__restrict__ n_persons,
-    Params prm, TOut *__restrict__ out4, TOut *__restrict__ out_ps, int32_t *__restrict__ out_count, uint32_t *__restrict__ out_flags,
-    char *scratch, size_t scratch_per_block) {
+    Params prm, LeanUnits<C, TOut> un, TOut *__restrict__ out4, TOut *__restrict__ out_ps, int32_t *__restrict__ out_count,
+    uint32_t *__restrict__ out_flags, char *scratch, size_t scratch_per_block) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NP = C * (C - 1) / 2;
     constexpr int kConstDoubles = lean_const_doubles(C);
@@ -709,10 +738,9 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     constexpr unsigned kCamStride = (unsigned)JC * kRec;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int items_pad = lean_coop_items_pad(JC, nf_max), ntable = items_pad + 256;
+    const int items_pad = lean_coop_items_pad(JC, nf_max);
     double *Mlds = reinterpret_cast<double *>(smem);
-    uint32_t *table = reinterpret_cast<uint32_t *>(Mlds + kConstDoubles);
-    TOut *stash = reinterpret_cast<TOut *>(table + ntable);
+    TOut *stash = reinterpret_cast<TOut *>(Mlds + kConstDoubles);
     double *favg = reinterpret_cast<double *>(stash + items_pad);          // [kCoopMaxFrames] mean fused score of a frame
     uint32_t *slowbits = reinterpret_cast<uint32_t *>(favg + kCoopMaxFrames);   // one word: bit = frame of the tile
     const Kp3<TIn> *kp3 = reinterpret_cast<const Kp3<TIn> *>(kpts);
@@ -755,7 +783,28 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
         for (int c = 0; c < C; c++)
             dst[c] = lean_load_kp3<TIn>(rin, voff + (unsigned)(c & 1) * kCamStride, (unsigned)(c & ~1) * kCamStride);
     };
-    auto item_offset = [&](unsigned i) { return (i + (i / (unsigned)JC) * (unsigned)((C - 1) * JC)) * kRec; };
+    // The wave fetches items i0 + lane + 64 k, k = 0, 1, ... in that order.  Item i is joint i % JC of the tile's frame i / JC and
+    // its camera-0 record sits at byte (i + (i / JC) (C-1) JC) kRec of the tile.  i0 + 64 k is wave-uniform, so the stream lives in
+    // SCALAR registers: (joint, byte offset) of the pass's first item, stepped by 64 joints and, past the frame's last joint
+    // (once at most: JC > 64), over the records of the frame's other cameras.  A lane adds 12 or 24 bytes per lane index and,
+    // if it lies behind the frame boundary inside the pass, the other cameras' records once more: a compare, a select and an
+    // add per fetch.  No table in LDS, no LDS read per fetch, one scalar division per wave.  A pass the wave does not own gets
+    // kNoItem in place of the scalar offset.
+    static_assert(JC > 64, "one frame boundary per pass of 64 joints");
+    constexpr unsigned kNoItem = 0x40000000u;   // beyond every descriptor (and no wrap-around with the lane and camera offsets): the load returns zeros without touching memory
+    constexpr unsigned kFrameSkip = (unsigned)((C - 1) * JC) * kRec;
+    unsigned sj = i0 % (unsigned)JC, sbase = (i0 + (i0 / (unsigned)JC) * (unsigned)((C - 1) * JC)) * kRec;
+    const unsigned lane_off = (unsigned)lane * kRec;
+    auto next_offset = [&](bool own) {   // byte offset of the lane's next fetch; steps the stream by one pass
+        const unsigned o = lane_off + (own ? sbase : kNoItem) + ((unsigned)lane >= (unsigned)JC - sj ? kFrameSkip : 0u);
+        sj += 64u;
+        sbase += 64u * kRec;
+        if (sj >= (unsigned)JC) {
+            sj -= (unsigned)JC;
+            sbase += kFrameSkip;
+        }
+        return o;
+    };
     // The rig constants are requested BEFORE the first keypoints: the vector-memory counter returns in order, so waiting for
     // a constant that was requested behind the keypoints would wait for the keypoints' trip to HBM (cold TLB: ~3 us) too
     // -- measured with wall-clock stamps per wave (-DSNOWTRI_LEAN_TRACE): 4.5 us from entry to the first item that way.
@@ -771,28 +820,25 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     double Kr[kResident ? 12 * C : 1];
     if constexpr (!kRolled) {
 #pragma unroll
-        for (int i = 0; i < 3 * NP; i++) dS[i] = rig.pairc[6 * (i / 3) + i % 3];
+        for (int i = 0; i < 3 * NP; i++) dS[i] = un.d[i];   // in units of lambda, from the kernel argument: scalar as they come
     }
-    // the wave's first two items (offsets computed: the table is not there yet); a pass the wave does not own reads nothing
-    constexpr unsigned kNoItem = 0x40000000u;   // beyond every descriptor (and no wrap-around with the camera offsets): the load returns zeros without touching memory
-    fetch(bufA, npass > 0 ? item_offset(i0 + (unsigned)lane) : kNoItem);
-    if constexpr (kRing >= 3) fetch(bufB, npass > 1 ? item_offset(i0 + 64u + (unsigned)lane) : kNoItem);
+    // the wave's first two items; a pass the wave does not own reads nothing
+    fetch(bufA, next_offset(npass > 0));
+    if constexpr (kRing >= 3) fetch(bufB, next_offset(npass > 1));
     // centre-joint keypoints of the check pass this wave will run after the barrier (pass `pos`: frames 10 pos ...)
     constexpr int kCheckFrames = 64 / NP;
     const int ncheck = (nf + kCheckFrames - 1) / kCheckFrames;
     Kp3<TIn> ckm, cks;
     int32_t *pairs_lds = reinterpret_cast<int32_t *>(Mlds + 12 * C + 3 * NP);
     // (the first keypoints are in flight while the constants are set up)
-    for (unsigned i = (unsigned)tid; i < (unsigned)ntable; i += kBlock) table[i] = item_offset(i);
     if (tid == 0) slowbits[0] = 0u;
     if (tid < 9 * C) Mlds[tid] = cM;
     if (tid < 3 * C) Mlds[9 * C + tid] = cT;
     if (tid < 3 * NP) Mlds[12 * C + tid] = cD;
-    if (tid < 2 * NP) pairs_lds[tid] = cP;
-    if constexpr (!kRolled) {
-#pragma unroll
-        for (int i = 0; i < 3 * NP; i++) dS[i] = uniform_f64(dS[i]);
+    if constexpr (!kRolled) {   // the same offsets in units of lambda: the one multiply the host did for un.d (the same bits)
+        if (tid < 3 * NP) Mlds[lean_scaled_at(C) + tid] = cD * un.inv;
     }
+    if (tid < 2 * NP) pairs_lds[tid] = cP;
     // (kResident: the offsets of the pairs of camera 0 are the t' of Kr, the item reads only the other pairs' from dS -- 9 pairs of
     // scalar registers fewer)
     const float kthr_f32 = prm.kthr_f32;
@@ -811,7 +857,7 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     }
 
     auto solve_store = [&](const Kp3<TIn>(&buf)[C], unsigned out_off, TOut *stash_slot) {
-        const bool bad = lean_solve_store<C, kResident, TIn, TOut>(Mlds, Kr, dS, buf, kthr_f32, kthr, dthr2, rout, out_off, stash_slot);
+        const bool bad = lean_solve_store<C, kResident, TIn, TOut>(Mlds, Kr, dS, buf, kthr_f32, kthr, dthr2, un.lam, un.kos, rout, out_off, stash_slot);
         if (__ballot(bad)) {  // rare, wave-uniform branch
             unsigned o = out_off;
             asm volatile("" : "+v"(o));
@@ -824,34 +870,30 @@ __global__ __launch_bounds__(kBlock, (LeanShape<C, TOut>::kWaves)) void k_fused_
     {
         unsigned out_off = (i0 + (unsigned)lane) * kOutRec;
         TOut *sp = stash + i0 + lane;
-        const uint32_t *tp = table + i0 + lane;
         if constexpr (kRing >= 3) {
             for (int k = 0; k < npass; k += 3) {
-                fetch(bufC, k + 2 < npass ? tp[128] : kNoItem);
+                fetch(bufC, next_offset(k + 2 < npass));
                 solve_store(bufA, out_off, sp);
-                fetch(bufA, k + 3 < npass ? tp[192] : kNoItem);
+                fetch(bufA, next_offset(k + 3 < npass));
                 if (k + 1 < npass) solve_store(bufB, out_off + 64u * kOutRec, sp + 64);
-                fetch(bufB, k + 4 < npass ? tp[256] : kNoItem);
+                fetch(bufB, next_offset(k + 4 < npass));
                 if (k + 2 < npass) solve_store(bufC, out_off + 128u * kOutRec, sp + 128);
-                tp += 192;
                 out_off += 192u * kOutRec;
                 sp += 192;
             }
         } else if constexpr (kRing == 2) {
             for (int k = 0; k < npass; k += 2) {
-                fetch(bufB, k + 1 < npass ? tp[64] : kNoItem);
+                fetch(bufB, next_offset(k + 1 < npass));
                 solve_store(bufA, out_off, sp);
-                fetch(bufA, k + 2 < npass ? tp[128] : kNoItem);
+                fetch(bufA, next_offset(k + 2 < npass));
                 if (k + 1 < npass) solve_store(bufB, out_off + 64u * kOutRec, sp + 64);
-                tp += 128;
                 out_off += 128u * kOutRec;
                 sp += 128;
             }
         } else {
             for (int k = 0; k < npass; k++) {
                 solve_store(bufA, out_off, sp);
-                fetch(bufA, k + 1 < npass ? tp[64] : kNoItem);
-                tp += 64;
+                fetch(bufA, next_offset(k + 1 < npass));
                 out_off += 64u * kOutRec;
                 sp += 64;
             }
