@@ -66,7 +66,7 @@ typedef enum snowtri_dtype { SNOWTRI_F32 = 0, SNOWTRI_F64 = 1 } snowtri_dtype;
 typedef enum snowtri_memspace { SNOWTRI_HOST = 0, SNOWTRI_DEVICE = 1 } snowtri_memspace;
 typedef enum snowtri_method {
     SNOWTRI_PAIRWISE = 0, /* the reference's algorithm: pairwise skew-ray midpoints, score-weighted */
-    SNOWTRI_DLT = 1       /* N-view DLT (A^T A smallest eigenvector; NOT reference behaviour).  One detection
+    SNOWTRI_DLT = 1,      /* N-view DLT (A^T A smallest eigenvector; NOT reference behaviour).  One detection
                            * per camera: no association.  Several: the reference's association (candidates +
                            * greedy clustering: the streaming kernels of the pairwise method), then one DLT per
                            * cluster over its distinct observations (k_cluster_dlt; with condense_score_tol > 0,
@@ -76,6 +76,10 @@ typedef enum snowtri_method {
                            * beyond them snowtri_triangulate_condense returns SNOWTRI_ERR_BAD_ARG and
                            * snowtri_last_error() says why.  SNOWTRI_PAIRWISE has no such limit (larger rigs
                            * fall back to the kernel that spills its candidates to HBM). */
+    SNOWTRI_DLT_ROBUST = 2 /* SNOWTRI_DLT with a leave-one-out gate on the reprojection residual (NOT reference behaviour): the
+                            * rule is stated at snowtri_triangulate_robust below.  One detection per camera (Pmax == 1) on 2 to 8
+                            * cameras; anything else is SNOWTRI_ERR_BAD_ARG and snowtri_last_error() names the limit.  Through
+                            * snowtri_triangulate_condense[_ex] it runs with the context's settings (snowtri_ctx_set_robust). */
 } snowtri_method;
 
 /* per-frame flag bits written to out_flags */
@@ -137,6 +141,13 @@ const char *snowtri_ctx_overrides(const snowtri_ctx *ctx);
  * freely with overlapped calls in flight; only the OUTPUTS of an overlapped call need the join before they are read. */
 int snowtri_ctx_set_overlap(snowtri_ctx *ctx, int n_streams);
 int snowtri_ctx_join(snowtri_ctx *ctx, void *stream);
+/* Settings of method = SNOWTRI_DLT_ROBUST through snowtri_triangulate_condense[_ex]: the residual gate in pixels and the number of
+ * views one joint may lose.  A fresh context has 6.0 px and 1 drop.  THOSE DEFAULTS COME FROM A SYNTHETIC CHECK, NOT FROM RECORDED
+ * FOOTAGE: the project's generator (ring rigs and the floor rig, 1 px of pixel noise, one camera shifted by 20-150 px on 10 % of
+ * the joints), where 6 px removed every shifted view and no clean one; a detector with heavier tails wants its own value.
+ * A negative or NaN threshold is SNOWTRI_ERR_BAD_ARG, +infinity is allowed (nothing is dropped: the result is SNOWTRI_DLT's);
+ * max_drops outside [0, 6] is SNOWTRI_ERR_BAD_ARG (0: SNOWTRI_DLT's result). */
+int snowtri_ctx_set_robust(snowtri_ctx *ctx, double reproj_threshold_px, int32_t max_drops);
 /* THE SPLIT of one multi-person call (several detections per camera, the streaming route).  By default a call whose batch fills
  * the chip at least twice (a segment holds >= 4 frames per CU) runs as two segments that alternate between the caller's stream
  * and ONE internal stream (fork / join events inside the call, results ordered behind `stream` as always): the latency-bound
@@ -243,6 +254,36 @@ int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int32_t Pmax, i
                                     const snowtri_params *params, int method, int32_t Pout_max,
                                     void *out_xyzs, void *out_pscore, int out_dtype, int32_t *out_count,
                                     uint32_t *out_flags, int memspace, void *stream, uint32_t call_flags);
+
+/* Outlier-robust N-view triangulation (no reference counterpart; SURVEY.md 8f N3 "robust variants"): SNOWTRI_DLT for one detection per
+ * camera, except that a view whose reprojection residual shows it to be wrong about a joint is left out of that joint.  Per frame f
+ * and joint j < keypoint_num, on inputs converted to fp64, with P[c] = K_c [R_c^T | -R_c^T t_c] and tau = reproj_threshold_px:
+ *   1. S = { c : (n_persons == NULL or n_persons[f][c] > 0) and not (s_c < keypoint_score_threshold) }.  |S| < 2: the record is
+ *      (0, 0, 0, 0), views = 0, resid = 0.
+ *   2. solve(S): X = the DLT solution over the views in S exactly as SNOWTRI_DLT defines it (rows u P[c][2] - P[c][0],
+ *      v P[c][2] - P[c][1]; smallest right singular vector, dehomogenised); for c in S, p = P[c] (X, 1) and
+ *      r_c^2 = (p0 / p2 - u_c)^2 + (p1 / p2 - v_c)^2;  m(S) = max_c r_c^2 (NaN if any r_c^2 is).
+ *   3. d = 0.  While |S| >= 3 and d < max_drops and m(S) > tau^2:  for every c in S in increasing c, m_c = m(S \ {c});  drop
+ *      c* = argmin m_c -- the lowest c starts as the best, a later candidate replaces it only if its m_c is strictly smaller (ties go
+ *      to the lowest c) or if the best so far is NaN and m_c is not (a NaN never wins against a number);  S = S \ {c*}, d += 1.
+ *      The comparisons are exactly these, so a NaN m(S) ends the loop.
+ *   4. The joint is X(S); its score the mean of s_c over the final S; views = bit mask of S (bit c); resid = sqrt(mean_{c in S} r_c^2)
+ *      in pixels.  Person score = mean of the keypoint_num joint scores; count = 1; flags as SNOWTRI_DLT writes them (FASTPATH).
+ * With max_drops = 0 or tau = +infinity this is SNOWTRI_DLT.  Leave-one-out instead of "drop the largest residual": the algebraic
+ * solve spreads one view's error over all views, and on 3-4 cameras the largest residual sits on a wrong view about one time in four.
+ * snowmocap_amd/robust.py::triangulate_robust_reference is this rule in NumPy (SVD); the kernel (k_dlt_robust,
+ * snowmocap_amd/csrc/snowtri_robust.hpp) takes the same decisions wherever they are not within rounding of a tie.
+ *   kpts [F][C][1][J][3] of in_dtype, n_persons [F][C] or NULL, out_xyzs [F][Pout_max][kn][4], out_pscore [F][Pout_max] (may be NULL),
+ *   out_count [F], out_flags [F] (may be NULL): as snowtri_triangulate_condense, same validation and alignment rules; slots >= 1 are
+ *   zero-filled;
+ *   out_views [F][kn] uint32 (may be NULL), out_resid [F][kn] of out_dtype (may be NULL): the two diagnostics; a NULL one costs nothing.
+ * reproj_threshold_px and max_drops as snowtri_ctx_set_robust takes them (the context's settings are not read).  F == 0 is SNOWTRI_OK
+ * and touches nothing.  SNOWTRI_DEVICE: asynchronous on `stream`, no host read, no internal stream (the overlap mode does not apply).
+ * snowtri_last_kernel_names reports k_dlt_robust<...> after the call. */
+int snowtri_triangulate_robust(snowtri_ctx *ctx, int64_t F, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
+                               const snowtri_params *params, double reproj_threshold_px, int32_t max_drops, int32_t Pout_max,
+                               void *out_xyzs, void *out_pscore, int out_dtype, int32_t *out_count, uint32_t *out_flags,
+                               uint32_t *out_views, void *out_resid, int memspace, void *stream);
 
 /* N1  Human_Triangulation_Smooth / SecondOrderDynamic (triangulation.py:4-22,164-186) over a whole track.
  * x[T][n] fp64, frame-major, n = persons * joints * 3 lanes (persons matched by index, as the reference does)
@@ -422,7 +463,7 @@ int snowtri_timing_collect(snowtri_ctx *ctx, float *kernel_ms, int32_t cap);
 /* Toggle per-call event timing (off by default: it adds two event records per launch).  enabled = 1: the ring's pair
  * BRACKETS the call (an event record before its first and after its last kernel: the interval includes the command
  * processor's hand-over from the begin event to the dispatch and from the kernel's end to the end event, ~1 us).
- * enabled = 2: when the call is ONE kernel (the single-detection fast kernels) the pair is ATTACHED to that dispatch
+ * enabled = 2: when the call is ONE kernel (the single-detection fast kernels, and k_dlt_coop / k_dlt_robust of the DLT methods) the pair is ATTACHED to that dispatch
  * (hipExtLaunchKernelGGL's start / stop events): the kernel's own begin and end, the duration a rocprofv3 kernel
  * trace reports, and no event record -- a barrier packet -- sits between consecutive launches, so a timing loop stays
  * back to back (snowtri_last_kernel_ms is not available for such a call); calls of several kernels are bracketed as with 1. */

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("SNOWTRI_LIB") or os.path.join(_HERE, "libsnowtri.so")
 OK, ERR_BAD_ARG, ERR_BAD_INDEX, ERR_HIP, ERR_SINGULAR, ERR_OVERFLOW, ERR_NO_DEVICE = range(7)
 F32, F64 = 0, 1
 HOST, DEVICE = 0, 1
-PAIRWISE, DLT = 0, 1
+PAIRWISE, DLT, DLT_ROBUST = 0, 1, 2
 FLAG_SINGULAR, FLAG_OVERFLOW, FLAG_FASTPATH = 1, 2, 4
 CALL_NO_ZERO_FILL = 1          # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
 TEST_LIB_PATH = os.path.join(_HERE, "libsnowtri_dbg.so")   # -DSNOWTRI_DEBUG_BOUNDS -DSNOWTRI_TEST_KNOBS (tests only: use_library)
@@ -65,6 +65,9 @@ _SIGNATURES = {
     "snowtri_ctx_set_overlap": (ct.c_int, [_c_p, ct.c_int]),
     "snowtri_ctx_join": (ct.c_int, [_c_p, _c_p]),
     "snowtri_ctx_set_split": (ct.c_int, [_c_p, ct.c_int]),
+    "snowtri_ctx_set_robust": (ct.c_int, [_c_p, ct.c_double, ct.c_int32]),
+    "snowtri_triangulate_robust": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, _c_p, ct.c_int, _c_p, ct.POINTER(Params), ct.c_double,
+                                              ct.c_int32, ct.c_int32, _c_p, _c_p, ct.c_int, _c_p, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_last_stream_counts": (ct.c_int, [_c_p, ct.POINTER(ct.c_int64 * 3)]),
     "snowtri_ctx_stream_probes": (ct.c_int, [_c_p, ct.POINTER(ct.c_int64 * 3)]),
     "snowtri_ctx_create": (ct.c_int, [ct.c_int32, _c_p, _c_p, _c_p, ct.c_int, ct.POINTER(_c_p)]),
@@ -313,6 +316,10 @@ class Context:
     def set_split(self, segments):
         """Segments of one multi-person call (snowtri_ctx_set_split): 1 = the caller's stream only, >= 2 forced, 0 = the default policy."""
         check(self.L.snowtri_ctx_set_split(self.handle, int(segments)), "snowtri_ctx_set_split")
+
+    def set_robust(self, reproj_threshold_px=6.0, max_drops=1):
+        """Settings of method = DLT_ROBUST through the fused call (snowtri_ctx_set_robust): residual gate in pixels, views a joint may lose."""
+        check(self.L.snowtri_ctx_set_robust(self.handle, float(reproj_threshold_px), int(max_drops)), "snowtri_ctx_set_robust")
 
     def join(self, stream=None):
         """`stream` (a HIP stream handle, default the null stream) waits for every overlapped call issued since the last join."""

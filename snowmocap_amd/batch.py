@@ -15,7 +15,7 @@ FUSED_CALLS = 0   # fused device calls issued through run_torch by this process 
 
 class BatchTriangulator:
     def __init__(self, K, R, t, params, pout_max=1, out_dtype=np.float32, device=0, method=_lib.PAIRWISE, D=None, streams=1,
-                 zero_fill=True):
+                 zero_fill=True, reproj_threshold_px=6.0, max_drops=1, diagnostics=False):
         """D (optional, [C, 5] lens coefficients): the keypoints handed to run_* were detected on RAW frames and
         are undistorted on the GPU first (row N4, snowtri_undistort_keypoints).
         streams (1..4): OVERLAP MODE of the library (snowtri_ctx_set_overlap) -- consecutive run_torch calls are issued
@@ -24,7 +24,18 @@ class BatchTriangulator:
         reads them) on the caller's stream.
         zero_fill=False: run_torch leaves the slots behind count[f] as the output buffers hold them (SNOWTRI_CALL_NO_ZERO_FILL:
         the reference returns lists of count[f] persons, the padding is this ABI's; on a multi-person batch with a generous
-        pout_max the zeros are most of what a call writes).  Read count[f] before a slot."""
+        pout_max the zeros are most of what a call writes).  Read count[f] before a slot.
+        method=_lib.DLT_ROBUST (one detection per camera, 2..8 cameras): the DLT with a leave-one-out gate on the reprojection
+        residual -- a view further than reproj_threshold_px from the joint the other views agree on is left out of that joint,
+        at most max_drops views per joint (the rule: robust.triangulate_robust_reference).  diagnostics=True: the results also
+        carry `views` [F, kn] (bit c = camera c was used; uint32, int32 in torch) and `resid` [F, kn] (RMS reprojection
+        residual in pixels over the views used) and the calls go through snowtri_triangulate_robust; otherwise through the
+        fused call with the context's settings.  The three arguments are ignored by the other methods.  snowtri_triangulate_robust
+        takes no call flags and always runs on the caller's stream, so diagnostics=True cannot be combined with zero_fill=False or
+        streams > 1 (ValueError)."""
+        if diagnostics and method == _lib.DLT_ROBUST and (not zero_fill or int(streams) > 1):
+            raise ValueError("diagnostics=True goes through snowtri_triangulate_robust, which always zero-fills and runs on the caller's "
+                             "stream: it cannot be combined with zero_fill=False or streams > 1")
         self.ctx = _lib.Context(K, R, t, device=device)
         self.call_flags = 0 if zero_fill else _lib.CALL_NO_ZERO_FILL
         self.streams = int(streams)
@@ -40,6 +51,12 @@ class BatchTriangulator:
         self.out_dtype = np.dtype(out_dtype)
         self.method = method
         self.device = device
+        self.robust = method == _lib.DLT_ROBUST
+        self.diagnostics = bool(diagnostics) and self.robust
+        self.reproj_threshold_px = float(reproj_threshold_px)
+        self.max_drops = int(max_drops)
+        if self.robust:
+            self.ctx.set_robust(self.reproj_threshold_px, self.max_drops)
 
     # -- host buffers ---------------------------------------------------------------------------
     def run_host(self, kpts, n_persons=None):
@@ -55,15 +72,26 @@ class BatchTriangulator:
         pscore = np.empty((F, self.pout_max), dtype=self.out_dtype)
         count = np.zeros(F, dtype=np.int32)
         flags = np.zeros(F, dtype=np.uint32)
-        rc = self.ctx.L.snowtri_triangulate_condense(
-            self.ctx.handle, F, Pmax, J, _lib.ptr(kpts), _lib.dtype_code(kpts.dtype), _lib.ptr(n_persons),
-            self.params, self.method, self.pout_max, _lib.ptr(xyzs), _lib.ptr(pscore),
-            _lib.dtype_code(self.out_dtype), _lib.ptr(count), _lib.ptr(flags), _lib.HOST, None)
+        extra = {}
+        if self.diagnostics:
+            if Pmax != 1:
+                raise _lib.SnowtriError(_lib.ERR_BAD_ARG, "snowtri_triangulate_robust (one detection per camera)")
+            extra = dict(views=np.zeros((F, max(kn, 0)), dtype=np.uint32), resid=np.zeros((F, max(kn, 0)), dtype=self.out_dtype))
+            rc = self.ctx.L.snowtri_triangulate_robust(
+                self.ctx.handle, F, J, _lib.ptr(kpts), _lib.dtype_code(kpts.dtype), _lib.ptr(n_persons), self.params,
+                self.reproj_threshold_px, self.max_drops, self.pout_max, _lib.ptr(xyzs), _lib.ptr(pscore),
+                _lib.dtype_code(self.out_dtype), _lib.ptr(count), _lib.ptr(flags), _lib.ptr(extra["views"]), _lib.ptr(extra["resid"]),
+                _lib.HOST, None)
+        else:
+            rc = self.ctx.L.snowtri_triangulate_condense(
+                self.ctx.handle, F, Pmax, J, _lib.ptr(kpts), _lib.dtype_code(kpts.dtype), _lib.ptr(n_persons),
+                self.params, self.method, self.pout_max, _lib.ptr(xyzs), _lib.ptr(pscore),
+                _lib.dtype_code(self.out_dtype), _lib.ptr(count), _lib.ptr(flags), _lib.HOST, None)
         if rc not in (_lib.OK, _lib.ERR_SINGULAR, _lib.ERR_OVERFLOW):
             if rc == _lib.ERR_BAD_INDEX:
                 raise IndexError("center_point_index / keypoint_num out of range")
-            _lib.check(rc, "snowtri_triangulate_condense")
-        return dict(xyzs=xyzs, pscore=pscore, count=count, flags=flags, status=rc)
+            _lib.check(rc, "snowtri_triangulate_robust" if self.diagnostics else "snowtri_triangulate_condense")
+        return dict(xyzs=xyzs, pscore=pscore, count=count, flags=flags, status=rc, **extra)
 
     # -- device buffers (torch tensors) ------------------------------------------------------------
     def alloc_outputs(self, F, torch_device=None):
@@ -71,10 +99,14 @@ class BatchTriangulator:
         dev = torch_device or torch.device("cuda", self.device)
         tdt = torch.float32 if self.out_dtype == np.float32 else torch.float64
         kn = self.params.keypoint_num
-        return dict(xyzs=torch.empty((F, self.pout_max, kn, 4), dtype=tdt, device=dev),
-                    pscore=torch.empty((F, self.pout_max), dtype=tdt, device=dev),
-                    count=torch.empty((F,), dtype=torch.int32, device=dev),
-                    flags=torch.empty((F,), dtype=torch.int32, device=dev))
+        out = dict(xyzs=torch.empty((F, self.pout_max, kn, 4), dtype=tdt, device=dev),
+                   pscore=torch.empty((F, self.pout_max), dtype=tdt, device=dev),
+                   count=torch.empty((F,), dtype=torch.int32, device=dev),
+                   flags=torch.empty((F,), dtype=torch.int32, device=dev))
+        if self.diagnostics:
+            out["views"] = torch.empty((F, kn), dtype=torch.int32, device=dev)
+            out["resid"] = torch.empty((F, kn), dtype=tdt, device=dev)
+        return out
 
     def run_torch(self, kpts, n_persons=None, out=None, stream=None):
         """kpts: CUDA tensor [F,C,Pmax,J,3] float32/float64 (contiguous).  Launches on `stream`
@@ -106,6 +138,19 @@ class BatchTriangulator:
             kpts = self._ukpts
         global FUSED_CALLS
         FUSED_CALLS += 1
+        if self.diagnostics:
+            if Pmax != 1:
+                raise _lib.SnowtriError(_lib.ERR_BAD_ARG, "snowtri_triangulate_robust (one detection per camera)")
+            rc = self.ctx.L.snowtri_triangulate_robust(
+                self.ctx.handle, F, J, ct.c_void_p(kpts.data_ptr()), in_code,
+                ct.c_void_p(n_persons.data_ptr()) if n_persons is not None else None, self.params, self.reproj_threshold_px,
+                self.max_drops, self.pout_max, ct.c_void_p(out["xyzs"].data_ptr()), ct.c_void_p(out["pscore"].data_ptr()),
+                _lib.dtype_code(self.out_dtype), ct.c_void_p(out["count"].data_ptr()), ct.c_void_p(out["flags"].data_ptr()),
+                ct.c_void_p(out["views"].data_ptr()), ct.c_void_p(out["resid"].data_ptr()), _lib.DEVICE, ct.c_void_p(stream))
+            if rc == _lib.ERR_BAD_INDEX:
+                raise IndexError("center_point_index / keypoint_num out of range")
+            _lib.check(rc, "snowtri_triangulate_robust")
+            return out
         rc = self.ctx.L.snowtri_triangulate_condense_ex(
             self.ctx.handle, F, Pmax, J, ct.c_void_p(kpts.data_ptr()), in_code,
             ct.c_void_p(n_persons.data_ptr()) if n_persons is not None else None, self.params, self.method,

@@ -28,6 +28,7 @@
 #include "snowtri_general.hpp"
 #include "snowtri_assoc.hpp"
 #include "snowtri_dlt_lean.hpp"
+#include "snowtri_robust.hpp"
 #include "snowtri_smooth.hpp"
 #include "snowtri_blender.hpp"
 #include "snowtri_undistort.hpp"
@@ -343,6 +344,9 @@ struct snowtri_ctx {
     int lean_tiles_per_wave = 0; // SNOWTRI_LEAN_TILES_PER_WAVE
     int debug = 0;               // SNOWTRI_DEBUG: launch shapes on stderr
     std::string overrides;
+    // method = SNOWTRI_DLT_ROBUST through the fused call (snowtri_ctx_set_robust)
+    double robust_threshold_px = 6.0;
+    int32_t robust_max_drops = 1;
     static constexpr int assoc_wg_per_cu = 4 * kAssocWaves, lean_wg_per_cu = 2, lean_scratch_mb = 256;   // (settled by measurement: EXPERIMENTS.md)
     struct OccCache {
         size_t lds = 0;
@@ -601,6 +605,21 @@ int snowtri_ctx_set_split(snowtri_ctx *ctx, int segments) {
     if (!ctx || segments < 0 || segments > 64) return SNOWTRI_ERR_BAD_ARG;
     ctx->split_segments = segments == 0 ? 2 : segments;
     ctx->split_forced = segments >= 2;
+    return SNOWTRI_OK;
+}
+
+int snowtri_ctx_set_robust(snowtri_ctx *ctx, double reproj_threshold_px, int32_t max_drops) {
+    if (!ctx) return SNOWTRI_ERR_BAD_ARG;
+    if (!(reproj_threshold_px >= 0.0)) {   // (negative or NaN; +inf is allowed: nothing is ever dropped)
+        g_last_error = "reproj_threshold_px must be >= 0 (+inf allowed), not negative or NaN";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    if (max_drops < 0 || max_drops > kRobustMaxDrops) {
+        g_last_error = "max_drops must be in [0, 6]";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    ctx->robust_threshold_px = reproj_threshold_px;
+    ctx->robust_max_drops = max_drops;
     return SNOWTRI_OK;
 }
 
@@ -2245,7 +2264,14 @@ int launch_dlt_coop(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_kp
     const size_t lds = dlt_coop_lds_bytes(C, kLeanJ, nf_max, (int)sizeof(TOut));
     auto kern = k_dlt_coop<C, TIn, kLeanJ, TOut>;
     if (lds > 48 * 1024 && ctx->raise_lds((const void *)kern, (int)lds)) return SNOWTRI_ERR_HIP;
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);
+    if (ctx->timing && ctx->timing_attach) {   // one kernel: the ring's event pair rides on its dispatch (see launch_fused_lean)
+        const int64_t slot = ctx->ev_count % kTimingRing;
+        hipExtLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
+                              F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);
+        ctx->ev_attached = true;
+    } else {
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);
+    }
     HIP_TRY(hipGetLastError());
     static const std::string name = std::string("k_dlt_coop<") + std::to_string(C) + "," + type_name<TIn>() + ",133," + type_name<TOut>() + ">";
     ctx->last_kernels = name.c_str();
@@ -2654,10 +2680,56 @@ int launch_frame_recompute(snowtri_ctx *ctx, hipStream_t st_call, int64_t F, int
     return SNOWTRI_OK;
 }
 
+// What method = SNOWTRI_DLT_ROBUST needs beyond the fused call's arguments: the settings (the context's, or the explicit ones of
+// snowtri_triangulate_robust) and the two optional per-joint diagnostics (device pointers by the time the launcher sees them).
+struct RobustCall {
+    double threshold_px = 6.0;
+    int32_t max_drops = 1;
+    uint32_t *views = nullptr;   // [F][kn]
+    void *resid = nullptr;       // [F][kn] of the output type
+};
+
+// method = SNOWTRI_DLT_ROBUST: k_dlt_robust (snowtri_robust.hpp), one workgroup per tile of T frames.  T fills the chip for a small
+// batch and is capped by kRobustMaxTile and by the LDS stash of the tile's joint scores; results do not depend on it.
+template <int C, typename TIn, typename TOut>
+int launch_dlt_robust(snowtri_ctx *ctx, hipStream_t st, int64_t F, int J, const TIn *d_kpts, const int32_t *d_np, const Params &prm,
+                      const RobustCall &rb, int Pout, TOut *d_xyzs, TOut *d_ps, int32_t *d_cnt, uint32_t *d_fl) {
+    const int kn = std::max(1, prm.kn);
+    const int64_t resident = (int64_t)ctx->num_cus * kRobustWaves;
+    int64_t T = std::min<int64_t>(kRobustMaxTile, (F + resident - 1) / resident);
+    T = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(32 * 1024) / (8 * (int64_t)kn)));
+    const int64_t tiles = (F + T - 1) / T;
+    const size_t lds = robust_lds_bytes(C, (int)T, prm.kn);
+    if (lds > (size_t)160 * 1024 || tiles > 0x7fffffffll) {
+        g_last_error = "SNOWTRI_DLT_ROBUST: keypoint_num too large for the LDS stash of one frame (or more than 2^31 tiles)";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    auto kern = k_dlt_robust<C, TIn, TOut>;
+    if (lds > 48 * 1024 && ctx->raise_lds((const void *)kern, (int)lds)) {
+        g_last_error = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
+        return SNOWTRI_ERR_HIP;
+    }
+    const double tau2 = rb.threshold_px * rb.threshold_px;
+    if (ctx->timing && ctx->timing_attach) {   // one kernel: the ring's event pair rides on its dispatch (see launch_fused_lean)
+        const int64_t slot = ctx->ev_count % kTimingRing;
+        hipExtLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
+                              F, J, (int)T, ctx->rig(), d_kpts, d_np, prm, tau2, (int)rb.max_drops, Pout, d_xyzs, d_ps, d_cnt, d_fl, rb.views,
+                              (TOut *)rb.resid);
+        ctx->ev_attached = true;
+    } else {
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, F, J, (int)T, ctx->rig(), d_kpts, d_np, prm, tau2,
+                           (int)rb.max_drops, Pout, d_xyzs, d_ps, d_cnt, d_fl, rb.views, (TOut *)rb.resid);
+    }
+    HIP_TRY(hipGetLastError());
+    static const std::string name = std::string("k_dlt_robust<") + std::to_string(C) + "," + type_name<TIn>() + "," + type_name<TOut>() + ">";
+    ctx->last_kernels = name.c_str();
+    return SNOWTRI_OK;
+}
+
 template <typename TIn, typename TOut>
 int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J, const void *kpts,
                    const int32_t *d_np, const Params &prm, int Pout, void *xyzs, void *ps, int32_t *d_cnt,
-                   uint32_t *d_fl, int method) {
+                   uint32_t *d_fl, int method, const RobustCall &rb) {
     const TIn *d_kpts = (const TIn *)kpts;
     TOut *d_xyzs = (TOut *)xyzs, *d_ps = (TOut *)ps;
     const int C = ctx->C;
@@ -2684,13 +2756,33 @@ int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J,
     // attached timing of a fast-kernel call: NO event record around the dispatch (a record is a barrier packet: the launches of a
     // timing loop would no longer be back to back); launch_fused_lean attaches the ring's pair to the kernel, or brackets a
     // call of several segments itself
-    const bool attach = ctx->timing && ctx->timing_attach && lean;
+    const bool dlt_coop = method == SNOWTRI_DLT && Pmax == 1 && C <= 8 && J == kLeanJ && prm.kn == kLeanJ && Pout == 1 && ctx->lean_mode != 0;
+    const bool attach = ctx->timing && ctx->timing_attach && (lean || dlt_coop || method == SNOWTRI_DLT_ROBUST);
     if (ctx->timing && !attach) {
         HIP_TRY(hipEventRecord(ctx->ev[0], st));
         HIP_TRY(hipEventRecord(ctx->ev_ring[2 * ring_slot], st));
     }
     int rc;
-    if (method == SNOWTRI_DLT && (Pmax > 1 || C > 8)) {
+    if (method == SNOWTRI_DLT_ROBUST) {
+        // one detection per camera, two to eight cameras (checked by the entry point)
+        switch (C) {
+#define SNOWTRI_CASE(CC)                                                                                                          \
+    case CC:                                                                                                                      \
+        rc = launch_dlt_robust<CC, TIn, TOut>(ctx, st, F, J, d_kpts, d_np, prm, rb, Pout, d_xyzs, d_ps, d_cnt, d_fl);             \
+        break;
+#ifndef SNOWTRI_DEV_MIN
+            SNOWTRI_CASE(2)
+            SNOWTRI_CASE(3)
+            SNOWTRI_CASE(5)
+            SNOWTRI_CASE(6)
+            SNOWTRI_CASE(7)
+            SNOWTRI_CASE(8)
+#endif
+            SNOWTRI_CASE(4)
+#undef SNOWTRI_CASE
+            default: rc = SNOWTRI_ERR_BAD_ARG;
+        }
+    } else if (method == SNOWTRI_DLT && (Pmax > 1 || C > 8)) {
         // several detections per camera: the reference's association (phases 1-2), then DLT per cluster
         if (prm.kn > kRecomputeMaxKn || !recompute_shape_ok(C, Pmax, J, ctx->npairs, (int)sizeof(TIn))) {
             g_last_error = "SNOWTRI_DLT with several detections per camera (or more than 8 cameras) supports at most 16 cameras, "
@@ -2701,7 +2793,7 @@ int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J,
         rc = launch_frame_recompute<1, TIn, TOut>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl);
     } else if (method == SNOWTRI_DLT) {
         // one detection per camera: no association needed.  The Wholebody skeleton with every joint asked for and one slot: k_dlt_coop
-        const bool dlt_lean = J == kLeanJ && prm.kn == kLeanJ && Pout == 1 && ctx->lean_mode != 0;
+        const bool dlt_lean = dlt_coop;
         switch (C) {
 #define SNOWTRI_CASE(CC)                                                                                      \
     case CC:                                                                                                  \
@@ -2801,23 +2893,75 @@ extern "C" int snowtri_triangulate_condense(snowtri_ctx *ctx, int64_t F, int32_t
                                            out_dtype, out_count, out_flags, memspace, stream, 0u);
 }
 
+namespace {
+int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
+               const snowtri_params *params, int method, int32_t Pout_max, void *out_xyzs, void *out_pscore, int out_dtype,
+               int32_t *out_count, uint32_t *out_flags, int memspace, void *stream, uint32_t call_flags, const RobustCall *explicit_rb);
+}
+
 extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J,
                                                const void *kpts, int in_dtype, const int32_t *n_persons,
                                                const snowtri_params *params, int method, int32_t Pout_max,
                                                void *out_xyzs, void *out_pscore, int out_dtype,
                                                int32_t *out_count, uint32_t *out_flags, int memspace,
                                                void *stream, uint32_t call_flags) {
+    return fused_call(ctx, F, Pmax, J, kpts, in_dtype, n_persons, params, method, Pout_max, out_xyzs, out_pscore, out_dtype, out_count,
+                      out_flags, memspace, stream, call_flags, nullptr);
+}
+
+extern "C" int snowtri_triangulate_robust(snowtri_ctx *ctx, int64_t F, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
+                                          const snowtri_params *params, double reproj_threshold_px, int32_t max_drops, int32_t Pout_max,
+                                          void *out_xyzs, void *out_pscore, int out_dtype, int32_t *out_count, uint32_t *out_flags,
+                                          uint32_t *out_views, void *out_resid, int memspace, void *stream) {
+    if (!ctx) return SNOWTRI_ERR_BAD_ARG;
+    if (!(reproj_threshold_px >= 0.0)) {
+        g_last_error = "reproj_threshold_px must be >= 0 (+inf allowed), not negative or NaN";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    if (max_drops < 0 || max_drops > kRobustMaxDrops) {
+        g_last_error = "max_drops must be in [0, 6]";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    RobustCall rb;
+    rb.threshold_px = reproj_threshold_px;
+    rb.max_drops = max_drops;
+    rb.views = out_views;
+    rb.resid = out_resid;
+    return fused_call(ctx, F, 1, J, kpts, in_dtype, n_persons, params, SNOWTRI_DLT_ROBUST, Pout_max, out_xyzs, out_pscore, out_dtype,
+                      out_count, out_flags, memspace, stream, 0u, &rb);
+}
+
+namespace {
+// The fused call.  explicit_rb: snowtri_triangulate_robust (its own settings and diagnostics; always on the caller's stream);
+// nullptr: snowtri_triangulate_condense[_ex], where method = SNOWTRI_DLT_ROBUST takes the context's settings and no diagnostics.
+int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
+               const snowtri_params *params, int method, int32_t Pout_max, void *out_xyzs, void *out_pscore, int out_dtype,
+               int32_t *out_count, uint32_t *out_flags, int memspace, void *stream, uint32_t call_flags, const RobustCall *explicit_rb) {
     if (!ctx || ctx->C < 1 || F < 0 || Pmax < 1 || J < 1 || Pout_max < 1 || !params) return SNOWTRI_ERR_BAD_ARG;
     if (call_flags & ~(uint32_t)SNOWTRI_CALL_NO_ZERO_FILL) return SNOWTRI_ERR_BAD_ARG;   // (an unknown flag is refused, not ignored)
     if ((in_dtype != SNOWTRI_F32 && in_dtype != SNOWTRI_F64) || (out_dtype != SNOWTRI_F32 && out_dtype != SNOWTRI_F64))
         return SNOWTRI_ERR_BAD_ARG;
     if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return SNOWTRI_ERR_BAD_ARG;
-    if (method != SNOWTRI_PAIRWISE && method != SNOWTRI_DLT) return SNOWTRI_ERR_BAD_ARG;
+    if (method != SNOWTRI_PAIRWISE && method != SNOWTRI_DLT && method != SNOWTRI_DLT_ROBUST) return SNOWTRI_ERR_BAD_ARG;
     if (method == SNOWTRI_DLT && ctx->C < 2) return SNOWTRI_ERR_BAD_ARG;
+    if (method == SNOWTRI_DLT_ROBUST && (Pmax != 1 || ctx->C < 2 || ctx->C > kRobustMaxCams)) {
+        g_last_error = "SNOWTRI_DLT_ROBUST takes one detection per camera (Pmax == 1) on 2 to 8 cameras (include/snowtri.h)";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    RobustCall rb;
+    if (explicit_rb) {
+        rb = *explicit_rb;
+    } else {
+        rb.threshold_px = ctx->robust_threshold_px;
+        rb.max_drops = ctx->robust_max_drops;
+    }
     if (F == 0) return SNOWTRI_OK;
     if (!kpts || !out_xyzs || !out_count) return SNOWTRI_ERR_BAD_ARG;
     // device buffers: keypoints aligned to their element, joint records [x, y, z, s] to 16 bytes (vector stores)
     if (memspace == SNOWTRI_DEVICE && (((uintptr_t)kpts & (dtype_size(in_dtype) - 1)) != 0 || ((uintptr_t)out_xyzs & 15) != 0))
+        return SNOWTRI_ERR_BAD_ARG;
+    // ... and the diagnostics of snowtri_triangulate_robust to their elements
+    if (memspace == SNOWTRI_DEVICE && ((rb.views && ((uintptr_t)rb.views & 3) != 0) || (rb.resid && ((uintptr_t)rb.resid & (dtype_size(out_dtype) - 1)) != 0)))
         return SNOWTRI_ERR_BAD_ARG;
     Params prm;
     int rc = validate_params(params, J, &prm, true);
@@ -2829,7 +2973,7 @@ extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int3
     ctx->last_set = &ctx->sets[0];
     ctx->last_stream = false;
     StreamSet *oset = nullptr;
-    if (memspace == SNOWTRI_DEVICE && ctx->overlap >= 2) {
+    if (memspace == SNOWTRI_DEVICE && ctx->overlap >= 2 && !explicit_rb) {
         // overlap mode: this call runs on the next internal stream behind everything `stream` holds now; the caller's
         // stream sees its results after snowtri_ctx_join
         // (sets 1 .. n: set 0 -- scratch, lists, counters -- stays with the caller's stream, where the host calls, the per-frame
@@ -2862,7 +3006,12 @@ extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int3
     uint32_t *d_fl = out_flags;
     const size_t np_off = (in_bytes + 15) & ~(size_t)15;
     const size_t ps_off = (o4 + 15) & ~(size_t)15, cnt_off = ps_off + ((ops + 15) & ~(size_t)15);
-    const size_t out_total = cnt_off + 8 * (size_t)F;
+    // the diagnostics of snowtri_triangulate_robust behind the flags (host calls: staged like everything else)
+    uint32_t *const h_views = rb.views;
+    void *const h_resid = rb.resid;
+    const size_t views_bytes = h_views ? sizeof(uint32_t) * (size_t)F * kn : 0, resid_bytes = h_resid ? osz * (size_t)F * kn : 0;
+    const size_t views_off = (cnt_off + 8 * (size_t)F + 15) & ~(size_t)15, resid_off = views_off + ((views_bytes + 15) & ~(size_t)15);
+    const size_t out_total = (h_views || h_resid) ? resid_off + resid_bytes : cnt_off + 8 * (size_t)F;
     const bool pinned = memspace == SNOWTRI_HOST && np_off + np_bytes <= kPinnedMaxBytes && out_total <= kPinnedMaxBytes;
     if (memspace == SNOWTRI_HOST) {
         rc = ctx->in.ensure(np_off + np_bytes + 64);
@@ -2888,6 +3037,8 @@ extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int3
         d_ps = o + ps_off;
         d_cnt = (int32_t *)(o + cnt_off);
         d_fl = (uint32_t *)(d_cnt + F);
+        if (h_views) rb.views = (uint32_t *)(o + views_off);
+        if (h_resid) rb.resid = o + resid_off;
     } else if (!d_fl) {
         rc = ctx->cur->misc.ensure(sizeof(uint32_t) * F);
         if (rc) return rc;
@@ -2897,17 +3048,17 @@ extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int3
     ctx->last_slow_frames = -1;
     ctx->last_handover = false;
     if (in_dtype == SNOWTRI_F32 && out_dtype == SNOWTRI_F32)
-        rc = fused_dispatch<float, float>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method);
+        rc = fused_dispatch<float, float>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method, rb);
 #ifdef SNOWTRI_DEV_MIN  // kernel-development builds (scripts/ab_build.sh): float32 I/O, 4 cameras only
     else
         rc = SNOWTRI_ERR_BAD_ARG;
 #else
     else if (in_dtype == SNOWTRI_F32)
-        rc = fused_dispatch<float, double>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method);
+        rc = fused_dispatch<float, double>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method, rb);
     else if (out_dtype == SNOWTRI_F32)
-        rc = fused_dispatch<double, float>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method);
+        rc = fused_dispatch<double, float>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method, rb);
     else
-        rc = fused_dispatch<double, double>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method);
+        rc = fused_dispatch<double, double>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout_max, d_xyzs, d_ps, d_cnt, d_fl, method, rb);
 #endif
     ctx->cur = &ctx->sets[0];
     if (rc) return rc;
@@ -2926,6 +3077,8 @@ extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int3
                 std::memcpy(out_flags, o + cnt_off + sizeof(int32_t) * F, sizeof(uint32_t) * F);
             else
                 fl = (uint32_t *)(o + cnt_off + sizeof(int32_t) * F);
+            if (h_views) std::memcpy(h_views, o + views_off, views_bytes);
+            if (h_resid) std::memcpy(h_resid, o + resid_off, resid_bytes);
         } else {
             HIP_TRY(hipMemcpyAsync(out_xyzs, d_xyzs, o4, hipMemcpyDeviceToHost, st));
             if (out_pscore) HIP_TRY(hipMemcpyAsync(out_pscore, d_ps, ops, hipMemcpyDeviceToHost, st));
@@ -2935,6 +3088,8 @@ extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int3
                 fl = fl_host.data();
             }
             HIP_TRY(hipMemcpyAsync(fl, d_fl, sizeof(uint32_t) * F, hipMemcpyDeviceToHost, st));
+            if (h_views) HIP_TRY(hipMemcpyAsync(h_views, rb.views, views_bytes, hipMemcpyDeviceToHost, st));
+            if (h_resid) HIP_TRY(hipMemcpyAsync(h_resid, rb.resid, resid_bytes, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
         uint32_t any = 0;
@@ -2949,3 +3104,4 @@ extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int3
     }
     return SNOWTRI_OK;
 }
+}  // namespace

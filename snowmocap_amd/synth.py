@@ -231,3 +231,23 @@ def make_keypoints_visible(rng, K, R, t, X, visible=None, pixel_sigma=1.0, score
             kpts[f, c, :len(order)] = rec[f, c, order]
             n_persons[f, c] = len(order)
     return kpts, n_persons
+
+
+def add_outliers(rng, kpts, fraction=0.1, shift_px=(20.0, 150.0)):
+    """One camera that is wrong about one joint: on `fraction` of the (frame, joint) items of a single-detection batch
+    kpts [F, C, 1, J, 3] ONE random camera's (u, v) is moved by shift_px[0] .. shift_px[1] pixels in a random direction (a flipped
+    limb, a hand detected on the neighbour), its confidence left as it is.  Returns (a copy of kpts with the shifts, cam [F, J]
+    int32: the shifted camera of the item, -1 where none is)."""
+    F, C, Pm, J, _ = kpts.shape
+    assert Pm == 1
+    out = np.array(kpts, copy=True)
+    cam = np.full((F, J), -1, dtype=np.int32)
+    hit = rng.uniform(size=(F, J)) < fraction
+    ff, jj = np.nonzero(hit)
+    cc = rng.integers(0, C, size=len(ff))
+    r = rng.uniform(shift_px[0], shift_px[1], size=len(ff))
+    ang = rng.uniform(0.0, 2.0 * np.pi, size=len(ff))
+    out[ff, cc, 0, jj, 0] = (out[ff, cc, 0, jj, 0].astype(np.float64) + r * np.cos(ang)).astype(out.dtype)
+    out[ff, cc, 0, jj, 1] = (out[ff, cc, 0, jj, 1].astype(np.float64) + r * np.sin(ang)).astype(out.dtype)
+    cam[ff, jj] = cc
+    return out, cam
