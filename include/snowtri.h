@@ -440,6 +440,43 @@ int snowtri_track_last_ms(snowtri_ctx *ctx, float kernel_ms[2]);
 int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t keypoint_num, const void *xyzs, int xyz_dtype,
                          int32_t S, const int32_t *person_of, void *xyzs_tracked, int memspace, void *stream);
 
+/* Gap filling: short dropouts in a track of joint records bridged before smoothing (no reference counterpart: the condense step
+ * leaves a joint too few views saw as the record (0, 0, 0, 0), triangulation.py:136-148, and the reference's filter takes it for a
+ * position at the origin).  xyzs[T][m][4] of xyz_dtype, m = persons * keypoint_num lanes of records (x, y, z, score), as
+ * snowtri_triangulate_condense and snowtri_track_gather write them -> out[T][m][4] of the same type, fill[T][m] uint8 codes (may be
+ * NULL: it then costs nothing).  All decisions and arithmetic are made on the values converted to fp64:
+ *   1. MISSING  record (t, l) is missing if its score == 0 (so -0.0 counts) or any of its four values is not finite; otherwise it
+ *      is MEASURED.
+ *   2. INTERIOR GAP  a measured record at frame a and the next measured record of the same lane at frame b, g = b - a - 1 with
+ *      1 <= g <= max_gap: for k = 1..g record a + k becomes the linear interpolation of the two in all four components (the score
+ *      included): w = (double)k / (double)(g + 1), d = B - A, p = w * d, v = A + p with every operation rounded separately (no FMA
+ *      contraction: the same rule as for the tracker's distances and the singular test above), v rounded once to xyz_dtype.
+ *      Code SNOWTRI_FILL_LERP.
+ *   3. ENDS OF THE ARRAY  b = the first measured frame of a lane: if 1 <= b <= max_gap, frames 0..b-1 become copies of record b;
+ *      a = the last measured frame: if 1 <= T - 1 - a <= max_gap, frames a+1..T-1 become copies of record a.  Code
+ *      SNOWTRI_FILL_HOLD.  Nothing else is held.
+ *   4. EVERYTHING ELSE is copied bit for bit: a measured record with code SNOWTRI_FILL_MEASURED, a missing record that no rule
+ *      filled with code SNOWTRI_FILL_MISSING (its NaN payloads survive the copy).
+ *   5. Lanes are independent: the result of a lane depends on nothing but that lane.
+ * snowmocap_amd/fill.py::fill_joint_track_reference is this rule in NumPy; the kernel (k_fill_gaps, snowmocap_amd/csrc/snowtri_fill.hpp)
+ * agrees with it bit for bit.  What the rule does NOT do: a joint that is missing in the first frame of a track and stays missing for
+ * more than max_gap frames is left alone, so a filter that starts there is still seeded with zeros.
+ * max_gap outside 1..255, an unknown dtype or memspace, negative T or m, a NULL xyzs or out: SNOWTRI_ERR_BAD_ARG.  out must not
+ * overlap xyzs (a tile of the kernel reads records of its neighbours that those have already overwritten): SNOWTRI_ERR_BAD_ARG.
+ * Sizes: T * m <= 2^58 records (64-bit byte offsets) and ceil(T / (4 * snowtri_fill_block_frames())) * ceil(m / 64) <= 2^31 - 1
+ * workgroups (a one-dimensional grid); beyond either SNOWTRI_ERR_BAD_ARG and snowtri_last_error() names the limit.  T == 0 (or
+ * m == 0) is SNOWTRI_OK and touches nothing.  A scratch-only context (C == 0) is enough.
+ * SNOWTRI_DEVICE: asynchronous on `stream`, no host read, no internal stream; xyzs and out aligned to 16 bytes (else
+ * SNOWTRI_ERR_BAD_ARG).  SNOWTRI_HOST: staged and synchronous.
+ * snowtri_fill_block_frames(): frames per tile of the kernel (results do not depend on it; tests aim gaps at its multiples). */
+#define SNOWTRI_FILL_MEASURED 0 /* measured record, copied                                  */
+#define SNOWTRI_FILL_LERP 1     /* interpolated between two measured records                */
+#define SNOWTRI_FILL_HOLD 2     /* copy of the nearest measured record, at an end of the array */
+#define SNOWTRI_FILL_MISSING 3  /* missing record that no rule filled, copied               */
+int snowtri_fill_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t max_gap,
+                             void *out, uint8_t *fill /* [T][m], may be NULL */, int memspace, void *stream);
+int snowtri_fill_block_frames(void);
+
 /* N4  Keypoint-level lens undistortion, for detections made on RAW frames (the reference undistorts whole
  * images before detection: main.py:52 cv2.undistort(frame, K, D)).  OpenCV's 5-coefficient Brown-Conrady model,
  * D[C][5] = (k1, k2, p1, p2, k3) per camera (camera_group_floor.json:53-61; Camera.D, camera.py:24,44); K as

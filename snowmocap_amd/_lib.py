@@ -125,6 +125,8 @@ _SIGNATURES = {
     "snowtri_track_last_ms": (ct.c_int, [_c_p, ct.POINTER(ct.c_float * 2)]),
     "snowtri_track_gather": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, _c_p,
                                         ct.c_int, _c_p]),
+    "snowtri_fill_joint_track": (ct.c_int, [_c_p, ct.c_int64, ct.c_int64, _c_p, ct.c_int, ct.c_int32, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_fill_block_frames": (ct.c_int, []),
     "snowtri_ctx_set_distortion": (ct.c_int, [_c_p, _c_p]),
     "snowtri_undistort_keypoints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, _c_p, ct.c_int,
                                                ct.c_int, _c_p]),

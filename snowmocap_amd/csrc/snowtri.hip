@@ -33,6 +33,7 @@
 #include "snowtri_blender.hpp"
 #include "snowtri_undistort.hpp"
 #include "snowtri_track.hpp"
+#include "snowtri_fill.hpp"
 #include "snowtri_kernels.hpp"
 
 using namespace snowtri;
@@ -1884,7 +1885,7 @@ int snowtri_blender_smooth(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const
 }
 
 // ------------------------------------------------------------------------------- person tracking
-static int track_fail(int status, const char *msg) {
+static int arg_fail(int status, const char *msg) {
     g_last_error = msg;
     return status;
 }
@@ -1896,20 +1897,20 @@ int snowtri_track_block_frames(void) { return kTrackBlockFrames; }
 int snowtri_track_persons(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t keypoint_num, const void *xyzs, int xyz_dtype,
                           const int32_t *count, int32_t S, int32_t center_point_index, double gate, int32_t max_missed, void *state,
                           int32_t *slot_of, int32_t *person_of, int32_t *track_id, uint32_t *flags, int memspace, void *stream) {
-    if (!ctx) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: null context");
+    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: null context");
     if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
-        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: unknown dtype or memory space");
-    if (F < 0 || keypoint_num < 1) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: F < 0 or keypoint_num < 1");
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: unknown dtype or memory space");
+    if (F < 0 || keypoint_num < 1) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: F < 0 or keypoint_num < 1");
     if (S < 1 || S > kTrackMax || Pout_max < 1 || Pout_max > kTrackMax)
-        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: S and Pout_max must lie in 1..16");
-    if (!(gate >= 0.0) || !std::isfinite(gate)) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: gate must be finite and >= 0");
-    if (max_missed < 0) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: max_missed must be >= 0");
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: S and Pout_max must lie in 1..16");
+    if (!(gate >= 0.0) || !std::isfinite(gate)) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: gate must be finite and >= 0");
+    if (max_missed < 0) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: max_missed must be >= 0");
     if (center_point_index < 0 || center_point_index >= keypoint_num)
-        return track_fail(SNOWTRI_ERR_BAD_INDEX, "snowtri_track_persons: center_point_index outside [0, keypoint_num)");
+        return arg_fail(SNOWTRI_ERR_BAD_INDEX, "snowtri_track_persons: center_point_index outside [0, keypoint_num)");
     if (F == 0) return SNOWTRI_OK;
-    if (!xyzs || !count || !slot_of || !person_of || !track_id) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: null array");
+    if (!xyzs || !count || !slot_of || !person_of || !track_id) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: null array");
     if (memspace == SNOWTRI_DEVICE && (((uintptr_t)xyzs & 15u) || (state && ((uintptr_t)state & 7u))))
-        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: xyzs must be aligned to 16 bytes, state to 8");
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: xyzs must be aligned to 16 bytes, state to 8");
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int P = Pout_max;
@@ -1944,7 +1945,7 @@ int snowtri_track_persons(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t
     }
     double *d_cen = (double *)ctx->track.p;
     const dim3 grid((unsigned)(((int64_t)F * P + 255) / 256));
-    if ((int64_t)F * P > (int64_t)0x7fffffff * 256) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: too many frames for one call");
+    if ((int64_t)F * P > (int64_t)0x7fffffff * 256) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: too many frames for one call");
     const bool timed = ctx->timing;
     ctx->track_ev_valid = false;
     if (timed) {
@@ -1988,16 +1989,16 @@ int snowtri_track_last_ms(snowtri_ctx *ctx, float kernel_ms[2]) {
 
 int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t keypoint_num, const void *xyzs, int xyz_dtype, int32_t S,
                          const int32_t *person_of, void *xyzs_tracked, int memspace, void *stream) {
-    if (!ctx) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: null context");
+    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: null context");
     if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
-        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: unknown dtype or memory space");
-    if (F < 0 || keypoint_num < 1) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: F < 0 or keypoint_num < 1");
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: unknown dtype or memory space");
+    if (F < 0 || keypoint_num < 1) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: F < 0 or keypoint_num < 1");
     if (S < 1 || S > kTrackMax || Pout_max < 1 || Pout_max > kTrackMax)
-        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: S and Pout_max must lie in 1..16");
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: S and Pout_max must lie in 1..16");
     if (F == 0) return SNOWTRI_OK;
-    if (!xyzs || !person_of || !xyzs_tracked) return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: null array");
+    if (!xyzs || !person_of || !xyzs_tracked) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: null array");
     if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) | ((uintptr_t)xyzs_tracked)) & 15u))
-        return track_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: xyzs and xyzs_tracked must be aligned to 16 bytes");
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_gather: xyzs and xyzs_tracked must be aligned to 16 bytes");
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const size_t person_bytes = dtype_size(xyz_dtype) * 4 * (size_t)keypoint_num;
@@ -2024,6 +2025,58 @@ int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t 
     HIP_TRY(hipGetLastError());
     if (memspace == SNOWTRI_HOST) {
         HIP_TRY(hipMemcpyAsync(xyzs_tracked, d_out, o_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SNOWTRI_OK;
+}
+
+// ------------------------------------------------------------------------------- gap filling
+int snowtri_fill_block_frames(void) { return kFillBlockFrames; }
+
+int snowtri_fill_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t max_gap, void *out, uint8_t *fill,
+                             int memspace, void *stream) {
+    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: null context");
+    if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: unknown dtype or memory space");
+    if (T < 0 || m < 0) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: T < 0 or m < 0");
+    if (max_gap < 1 || max_gap > kFillMaxGap) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: max_gap must lie in 1..255");
+    if (T == 0 || m == 0) return SNOWTRI_OK;
+    if (!xyzs || !out) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: null array");
+    // one workgroup per 64 lanes x (kFillWaves * kFillBlockFrames) frames on a one-dimensional grid; 64-bit byte offsets of 32-byte records
+    const int64_t ncols = (m + 63) / 64, nrows = (T + (int64_t)kFillWaves * kFillBlockFrames - 1) / ((int64_t)kFillWaves * kFillBlockFrames);
+    if (T > ((int64_t)1 << 58) / m)
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: T * m must not exceed 2^58 records");
+    if (nrows > (int64_t)0x7fffffff / ncols)
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: ceil(T / 256) * ceil(m / 64) must not exceed 2^31 - 1 workgroups");
+    const size_t bytes = dtype_size(xyz_dtype) * 4 * (size_t)T * (size_t)m, f_bytes = (size_t)T * (size_t)m;
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) | ((uintptr_t)out)) & 15u))
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: xyzs and out must be aligned to 16 bytes");
+    if ((uintptr_t)xyzs < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)xyzs + bytes)
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: out must not overlap xyzs");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const void *dx = xyzs;
+    void *d_out = out;
+    uint8_t *d_fill = fill;
+    if (memspace == SNOWTRI_HOST) {
+        int rc = ctx->in.ensure(bytes);
+        if (rc) return rc;
+        rc = ctx->out.ensure(pad16(bytes) + f_bytes);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->in.p, xyzs, bytes, hipMemcpyHostToDevice, st));
+        dx = ctx->in.p;
+        d_out = ctx->out.p;
+        d_fill = fill ? (uint8_t *)ctx->out.p + pad16(bytes) : nullptr;
+    }
+    const dim3 grid((unsigned)(ncols * nrows)), block(64, kFillWaves);
+    if (xyz_dtype == SNOWTRI_F32)
+        hipLaunchKernelGGL(k_fill_gaps<float>, grid, block, 0, st, T, m, (int)max_gap, ncols, (const uint4 *)dx, (uint4 *)d_out, d_fill);
+    else
+        hipLaunchKernelGGL(k_fill_gaps<double>, grid, block, 0, st, T, m, (int)max_gap, ncols, (const uint4 *)dx, (uint4 *)d_out, d_fill);
+    HIP_TRY(hipGetLastError());
+    if (memspace == SNOWTRI_HOST) {
+        HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+        if (fill) HIP_TRY(hipMemcpyAsync(fill, d_fill, f_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return SNOWTRI_OK;

@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib
 from .batch import BatchTriangulator
 from .blender import CONTROL_POINT_NAMES, _WIDTH
+from .fill import FILL_MISSING, MAX_GAP, fill_joint_track
 
 
 class TrackPipeline:
@@ -38,7 +39,7 @@ class TrackPipeline:
     def close(self):
         self.bt.close()
 
-    def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8):
+    def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -56,7 +57,19 @@ class TrackPipeline:
         its person).  Every array is then indexed by SLOT -- xyzs is the tracked gather of the triangulated persons (their list
         order is kept in xyzs_listed / slot_of) -- and each track id is filtered over the frames in which it occupies its slot,
         so a slot that is re-used by a new id starts fresh filters.  Adds present [F, P] (bool) and track_id [F, P]; tracked [F]
-        counts the present slots (they need not be a prefix: pass present= to to_blender_result).  Reads track_id on the host."""
+        counts the present slots (they need not be a prefix: pass present= to to_blender_result).  Reads track_id on the host.
+        fill_gaps=g > 0: short dropouts are bridged before the filters see them (fill.fill_joint_track with max_gap = g: a joint
+        the condense step left as the record (0, 0, 0, 0), or a record with a non-finite value, for at most g frames is
+        interpolated between its measured neighbours instead of pulling its filter towards the origin).  The fill runs on the
+        sequence the filters run on -- the whole [F, P * kn] array when every slot is carried in every frame, otherwise the
+        gathered frames of the slot or track id -- and the filters consume the filled records.  Adds xyzs_filled [F, P, kn, 4]
+        and fill [F, P, kn] (uint8, fill.FILL_*; outside every filtered sequence: the records of xyzs, FILL_MEASURED or
+        FILL_MISSING); xyzs stays the unfilled triangulation.  With ragged="track" a track id that leaves its slot for at most
+        g frames and returns to it is BRIDGED first (tracking.bridge_track_ids on the host copy of track_id): its frame set
+        becomes that of the bridged id, the tracked gather holds zero records where the person was absent, so those are
+        interpolated like any missing joint; track_id and present are then the bridged ones and bridged [F, P] (bool) marks
+        the frames that were added.  0 (the default): nothing of this, the dict is today's.  Not addressed: a joint that is
+        missing in the first frame of a sequence for more than g frames still seeds its filter with zeros."""
         import torch
         dev = torch.device("cuda", self.device)
         if not torch.is_tensor(kpts):
@@ -83,6 +96,9 @@ class TrackPipeline:
         xyzs = tri["xyzs"]
         th = self.th
         fzrd = (float(th["smooth_f"]), float(th["smooth_z"]), float(th["smooth_r"]), float(th["smooth_delta_time"]))
+        fill_gaps = int(fill_gaps)
+        if fill_gaps < 0 or fill_gaps > MAX_GAP:
+            raise ValueError(f"fill_gaps must be 0 (off) or a max_gap in 1..{MAX_GAP} (got {fill_gaps})")
         pts = torch.empty((F, self.P, 24, 4), dtype=torch.float64, device=dev)
         val = torch.empty((F, self.P, 24), dtype=torch.uint8, device=dev)
 
@@ -90,10 +106,15 @@ class TrackPipeline:
             _lib.check(L.snowtri_blender_points(h, n, self.kn, ct.c_void_p(x.data_ptr()), _lib.F64, ct.c_void_p(p_out.data_ptr()),
                                                 ct.c_void_p(v_out.data_ptr()), _lib.DEVICE, st), "snowtri_blender_points")
 
-        def filter_rows(src, idx, i, sm, pts_s):
-            """slot i over the frames idx (the first of them seeds the filters): gather, N1, N2 points, N2 filters, scatter"""
+        def filter_rows(src, idx, i, sm, pts_s, filled=None, codes=None):
+            """slot i over the frames idx (the first of them seeds the filters): gather, [fill into filled / codes,] N1, N2 points,
+            N2 filters, scatter"""
             T = int(idx.numel())
             xi = src[idx, i].contiguous()                                   # [T, kn, 4]
+            if filled is not None:
+                xi, ci = fill_joint_track(self.bt.ctx, xi, fill_gaps)
+                filled[idx, i] = xi
+                codes[idx, i] = ci
             si = torch.empty_like(xi)
             _lib.check(L.snowtri_smooth_joint_track(h, T, self.kn, ct.c_void_p(xi.data_ptr()), *fzrd, ct.c_void_p(si.data_ptr()),
                                                     _lib.DEVICE, st), "snowtri_smooth_joint_track")
@@ -109,26 +130,44 @@ class TrackPipeline:
             val[idx, i] = vi[:, 0]
             pts_s[idx, i] = qi[:, 0]
 
+        def unfilled(x):
+            """(xyzs_filled, fill) before any sequence has been filled: the records as they are, measured or missing"""
+            return x.clone(), ((x[..., 3] == 0) | ~torch.isfinite(x).all(dim=-1)).to(torch.uint8) * FILL_MISSING
+
         if ragged == "track":
-            from .tracking import PersonTracker
+            from .tracking import PersonTracker, bridge_track_ids
             trk_out = PersonTracker(self.bt.ctx, S=self.P, center_point_index=self.bt.params.center_point_index, gate=track_gate,
                                     max_missed=track_max_missed).run_torch(xyzs, tri["count"], gather=True, carry=False)
             listed, xyzs = xyzs, trk_out["xyzs_tracked"]
             tid = trk_out["track_id"].cpu().numpy()                          # the host decides which frames a track covers
+            if fill_gaps:
+                tid = bridge_track_ids(tid, fill_gaps)
+            filled, codes = unfilled(xyzs) if fill_gaps else (None, None)
             sm = torch.zeros_like(xyzs)
             pts.zero_()
             val.zero_()
             pts_s = torch.zeros_like(pts)
             for i in range(self.P):
                 for one in np.unique(tid[:, i][tid[:, i] >= 0]):
-                    filter_rows(xyzs, torch.from_numpy(np.nonzero(tid[:, i] == one)[0]).to(dev), i, sm, pts_s)
+                    filter_rows(xyzs, torch.from_numpy(np.nonzero(tid[:, i] == one)[0]).to(dev), i, sm, pts_s, filled, codes)
             present = trk_out["person_of"] >= 0
-            return dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"], flags=tri["flags"],
-                        tracked=present.sum(dim=1).to(torch.int32), present=present, track_id=trk_out["track_id"],
-                        slot_of=trk_out["slot_of"], track_flags=trk_out["flags"], xyzs_listed=listed)
+            res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"], flags=tri["flags"],
+                       tracked=present.sum(dim=1).to(torch.int32), present=present, track_id=trk_out["track_id"],
+                       slot_of=trk_out["slot_of"], track_flags=trk_out["flags"], xyzs_listed=listed)
+            if fill_gaps:
+                res["track_id"] = torch.from_numpy(tid).to(dev)
+                res["present"] = res["track_id"] >= 0
+                res["bridged"] = res["present"] & ~present
+                res["tracked"] = res["present"].sum(dim=1).to(torch.int32)
+                res["xyzs_filled"], res["fill"] = filled, codes
+            return res
         if tracked is None:
+            src = xyzs
+            if fill_gaps:
+                filled, codes = fill_joint_track(self.bt.ctx, xyzs, fill_gaps)
+                src = filled
             sm = torch.empty_like(xyzs)                    # only the points are filtered, the scores copied (triangulation.py:169-184)
-            _lib.check(L.snowtri_smooth_joint_track(h, F, self.P * self.kn, ct.c_void_p(xyzs.data_ptr()), *fzrd, ct.c_void_p(sm.data_ptr()),
+            _lib.check(L.snowtri_smooth_joint_track(h, F, self.P * self.kn, ct.c_void_p(src.data_ptr()), *fzrd, ct.c_void_p(sm.data_ptr()),
                                                     _lib.DEVICE, st), "snowtri_smooth_joint_track")
             blender_points(sm, F * self.P, pts, val)
             pts_s = torch.empty_like(pts)
@@ -139,14 +178,18 @@ class TrackPipeline:
         else:
             # slot by slot over the frames that carry it (frame 0 among them: it seeds the slot's filters)
             trk = torch.from_numpy(tracked).to(dev)
+            filled, codes = unfilled(xyzs) if fill_gaps else (None, None)
             sm = torch.zeros_like(xyzs)
             pts.zero_()
             val.zero_()
             pts_s = torch.zeros_like(pts)
             for i in range(int(tracked[0]) if F else 0):
-                filter_rows(xyzs, torch.nonzero(trk > i).view(-1), i, sm, pts_s)
-        return dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"],
-                    flags=tri["flags"], tracked=trk)
+                filter_rows(xyzs, torch.nonzero(trk > i).view(-1), i, sm, pts_s, filled, codes)
+        res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"],
+                   flags=tri["flags"], tracked=trk)
+        if fill_gaps:
+            res["xyzs_filled"], res["fill"] = filled, codes
+        return res
 
     @staticmethod
     def to_blender_result(points_smoothed, valid, armature_profile=None, tracked=None, present=None):
@@ -191,7 +234,9 @@ class ShardedTrackPipeline:
     That needs ONE number of another rank -- count[0], handed round with the ranks' error bits (sharded.tracked_counts) --
     and per slot i the frames with tracked > i that a rank holds are a block of the slot's own frame sequence: the N1 carry
     exchange and the N2 hold + carry exchanges run on those blocks unchanged (an empty block is a rank none of whose frames
-    carries the slot; the block with frame 0 starts the sequence)."""
+    carries the slot; the block with frame 0 starts the sequence).
+    TrackPipeline.run's fill_gaps is NOT offered here: a gap that crosses a shard boundary needs the measured records on both
+    sides of it, i.e. a halo exchange of up to max_gap frames per rank before the fill, which has not been built."""
 
     def __init__(self, K, R, t, thresholds, blender_smooth_profile, n_persons_out=1, device=0, group=None, method=_lib.PAIRWISE):
         self.pipe = TrackPipeline(K, R, t, thresholds, blender_smooth_profile, n_persons_out=n_persons_out, device=device, method=method)

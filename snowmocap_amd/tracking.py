@@ -151,6 +151,20 @@ def gather_reference(xyzs, person_of):
     return out
 
 
+def bridge_track_ids(track_id, max_gap):
+    """track_id [F, S] as the tracker writes it (-1 = slot empty in this frame) -> a copy in which, per slot, a run of -1 of
+    length <= max_gap between two frames that carry the SAME id takes that id: the person was lost for a moment and came back
+    to the slot (which max_missed kept for them).  Runs between different ids, and leading or trailing runs, stay -1.  NumPy."""
+    tid = np.array(track_id, dtype=np.int32, copy=True)
+    assert tid.ndim == 2
+    for s in range(tid.shape[1]):
+        seen = np.nonzero(tid[:, s] >= 0)[0]
+        for a, b in zip(seen[:-1], seen[1:]):
+            if 1 <= b - a - 1 <= int(max_gap) and tid[a, s] == tid[b, s]:
+                tid[a + 1:b, s] = tid[a, s]
+    return tid
+
+
 def _vp(x):
     return ct.c_void_p(x) if x else None
 
