@@ -503,11 +503,26 @@ int snowtri_ctx_create(int32_t C, const double *K, const double *R, const double
     CTX_TRY(hipMalloc(&ctx->dpairs, sizeof(int32_t) * std::max<size_t>(2, ctx->hpairs.size())));
     CTX_TRY(hipMalloc(&ctx->d_counters, sizeof(unsigned long long) * kCounterWords));
     CTX_TRY(hipMalloc(&ctx->dpairc, sizeof(double) * std::max<size_t>(6, hpairc.size())));
-    {   // world->pixel matrices P_c = K_c [R_c^T | -R_c^T t_c] for the DLT method
-        std::vector<double> hP((size_t)std::max(1, C) * 12, 0.0);
+    {   // The DLT method solves in the rig's own frame (include/snowtri.h, SNOWTRI_DLT): centre = the mean of the camera centres
+        // (summed in camera order), scale = max |t_c - centre| over cameras and axes (1 when that is 0), and the frame -> pixel
+        // matrices P_c = K_c [R_c^T | -R_c^T (t_c - centre) / scale].  A^T A squares the translation column f |t|: formed in world
+        // coordinates its fp64 error reaches metres for a millimetre rig in site coordinates.
+        // The four doubles (centre, scale) follow P in the same buffer: the kernels keep them in LDS beside P.
+        std::vector<double> hP((size_t)std::max(1, C) * 12 + kDltFrame, 0.0);
+        double *fc = hP.data() + (size_t)12 * C, &fs = hP[(size_t)12 * C + 3];
+        for (int i = 0; i < 3; i++) {
+            double sum = 0.0;
+            for (int c = 0; c < C; c++) sum += t[3 * c + i];
+            fc[i] = C > 0 ? sum / (double)C : 0.0;
+        }
+        double ext = 0.0;
+        for (int c = 0; c < C; c++)
+            for (int i = 0; i < 3; i++) ext = std::max(ext, std::fabs(t[3 * c + i] - fc[i]));
+        fs = ext > 0.0 ? ext : 1.0;   // (a NaN centre: 1)
         for (int c = 0; c < C; c++) {
-            const double *Kc = K + 9 * c, *Rc = R + 9 * c, *tc = t + 3 * c;
-            double Rt[12];  // [R^T | -R^T t]
+            const double *Kc = K + 9 * c, *Rc = R + 9 * c;
+            const double tc[3] = {(t[3 * c] - fc[0]) / fs, (t[3 * c + 1] - fc[1]) / fs, (t[3 * c + 2] - fc[2]) / fs};
+            double Rt[12];  // [R^T | -R^T (t - centre) / scale]
             for (int i = 0; i < 3; i++) {
                 for (int j = 0; j < 3; j++) Rt[4 * i + j] = Rc[3 * j + i];
                 Rt[4 * i + 3] = -(Rc[0 + i] * tc[0] + Rc[3 + i] * tc[1] + Rc[6 + i] * tc[2]);

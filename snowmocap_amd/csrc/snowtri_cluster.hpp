@@ -505,7 +505,7 @@ __global__ __launch_bounds__(kBlock, kWideWaves) void k_cluster_fuse_wide(const 
 // the observations whose confidence is not below keypoint_score_threshold, two needed, joint score = their mean confidence.
 // The persons' mean scores: k_person_scores.  P [C][12] in LDS (broadcast reads).  Dynamic LDS: cluster_dlt_lds_bytes(C).
 constexpr int kClusterDltWaves = 3;
-__host__ __device__ constexpr size_t cluster_dlt_lds_bytes(int C) { return (size_t)96 * C + 16; }
+__host__ __device__ constexpr size_t cluster_dlt_lds_bytes(int C) { return (size_t)96 * C + 8 * kDltFrame + 16; }
 template <int CT, typename TIn, typename TOut>
 __global__ __launch_bounds__(kBlock, kClusterDltWaves) void k_cluster_dlt(const ClusterDesc *__restrict__ desc, const uint32_t *__restrict__ words,
                                                               const unsigned long long *__restrict__ cnt, uint32_t desc_cap, Rig rig,
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(kBlock, kClusterDltWaves) void k_cluster_dlt(const 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int C = CT > 0 ? CT : rig.C, R = C * Pmax;
-    for (int i = tid; i < 12 * C; i += kBlock) Pl[i] = rig.P[i];
+    for (int i = tid; i < 12 * C + kDltFrame; i += kBlock) Pl[i] = rig.P[i];   // (P, the rig frame behind it)
     const unsigned long long nc64 = cnt[kHandComplete];
     const uint32_t ng_raw = hand_member_descs(cnt[kHandMembers]);
     const uint32_t nc = nc64 < (unsigned long long)desc_cap ? (uint32_t)nc64 : desc_cap, ng = ng_raw < desc_cap ? ng_raw : desc_cap;
@@ -627,9 +627,9 @@ __global__ __launch_bounds__(kBlock, kClusterDltWaves) void k_cluster_dlt(const 
             double e[4];
             dlt_solve(A, ok, e);   // (every lane of the wave: the solver votes)
             const double r = dlt_recip(e[3]);
-            ox = ok ? e[0] * r : 0.0;
-            oy = ok ? e[1] * r : 0.0;
-            oz = ok ? e[2] * r : 0.0;
+            ox = ok ? dlt_to_world(e[0] * r, Pl + 12 * C, 0) : 0.0;
+            oy = ok ? dlt_to_world(e[1] * r, Pl + 12 * C, 1) : 0.0;
+            oz = ok ? dlt_to_world(e[2] * r, Pl + 12 * C, 2) : 0.0;
             os = ok ? ssum * dlt_recip((double)nuse) : 0.0;
         }
         if (valid) cluster_store<TOut>(out4, ((uint64_t)d.x * (uint32_t)Pout + d.z) * (uint64_t)(uint32_t)kn + j, ox, oy, oz, os);

@@ -19,8 +19,8 @@ namespace snowtri {
 
 constexpr int kDltCoopWaves = 3;   // waves per SIMD the kernel is compiled for (dlt_item with P read per camera: ~140 VGPRs)
 __host__ __device__ constexpr size_t dlt_coop_lds_bytes(int C, int JC, int nf_max, int score_bytes = 4) {
-    // [P[C][12] | item -> input offset table (+ 128 entries of prefetch distance) | stash | mean per frame | detection mask per frame]
-    return (((size_t)96 * C + (size_t)4 * (lean_coop_items_pad(JC, nf_max) + 128) + (size_t)score_bytes * lean_coop_items_pad(JC, nf_max) +
+    // [P[C][12] + the rig frame | item -> input offset table (+ 128 entries of prefetch distance) | stash | mean per frame | detection mask per frame]
+    return (((size_t)96 * C + 8 * kDltFrame + (size_t)4 * (lean_coop_items_pad(JC, nf_max) + 128) + (size_t)score_bytes * lean_coop_items_pad(JC, nf_max) +
              (size_t)12 * kCoopMaxFrames + 16) + 15) & ~(size_t)15;
 }
 
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kBlock, kDltCoopWaves) void k_dlt_coop(int64_t F, i
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int items_pad = lean_coop_items_pad(JC, nf_max), ntable = items_pad + 128;
     double *Pl = reinterpret_cast<double *>(smem);
-    uint32_t *table = reinterpret_cast<uint32_t *>(Pl + 12 * C);
+    uint32_t *table = reinterpret_cast<uint32_t *>(Pl + 12 * C + kDltFrame);
     TOut *stash = reinterpret_cast<TOut *>(table + ntable);
     double *favg = reinterpret_cast<double *>(stash + items_pad);               // [kCoopMaxFrames]
     uint32_t *fmask = reinterpret_cast<uint32_t *>(favg + kCoopMaxFrames);      // [kCoopMaxFrames] bit c: camera c lists a detection
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kBlock, kDltCoopWaves) void k_dlt_coop(int64_t F, i
     };
     auto item_offset = [&](unsigned i) { return (i + (i / (unsigned)JC) * (unsigned)((C - 1) * JC)) * kRec; };
     // the constants are requested BEFORE the first keypoints (the vector-memory counter returns in order)
-    const double cP = rig.P[tid < 12 * C ? tid : 0];
+    const double cP = rig.P[tid < 12 * C + kDltFrame ? tid : 0];
     uint32_t cmask = 0xffffu;
     if (n_persons && tid < nf) {
         cmask = 0u;
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kBlock, kDltCoopWaves) void k_dlt_coop(int64_t F, i
     constexpr unsigned kNoItem = 0x40000000u;   // beyond every descriptor: the load returns zeros without touching memory
     fetch(bufA, npass > 0 ? item_offset(i0 + (unsigned)lane) : kNoItem);
     for (unsigned i = (unsigned)tid; i < (unsigned)ntable; i += kBlock) table[i] = item_offset(i);
-    if (tid < 12 * C) Pl[tid] = cP;
+    if (tid < 12 * C + kDltFrame) Pl[tid] = cP;
     if (tid < kCoopMaxFrames) fmask[tid] = cmask;
     const bool masked = n_persons != nullptr;   // (uniform)
     __syncthreads();

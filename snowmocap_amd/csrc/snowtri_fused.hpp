@@ -523,6 +523,11 @@ __device__ __forceinline__ void dlt_solve(double (&A)[4][4], bool live, double (
 // instructions per joint), 1 / 0 kept as the division has it
 __device__ __forceinline__ double dlt_recip(double x) { return x == 0.0 ? copysign(__builtin_inf(), x) : rcp_nr2(x); }
 
+// The solved point x = e[0:3] / e_3 is in the rig's frame: c + s x in the world.  ONE fma per coordinate, this expression at every
+// site that writes a DLT joint (dlt_item, k_cluster_dlt, k_frame_recompute<1>, k_dlt_robust): the routes stay bit-identical.
+// frame = the kDltFrame doubles (c_x, c_y, c_z, s) behind P[C][12] (Rig::P; in LDS beside P where P is).
+__device__ __forceinline__ double dlt_to_world(double x, const double *frame, int axis) { return fma(frame[3], x, frame[axis]); }
+
 // npmask: bit c set = camera c lists a detection in this frame (all ones without an n_persons array)
 template <int C, typename TIn>
 __device__ __forceinline__ void dlt_item(const double *__restrict__ Plds, const Kp3<TIn> (&cur)[C], uint32_t npmask,
@@ -572,9 +577,9 @@ __device__ __forceinline__ void dlt_item(const double *__restrict__ Plds, const 
     double e[4];
     dlt_solve(A, ok, e);
     const double r = dlt_recip(e[3]);
-    ox = ok ? e[0] * r : 0.0;
-    oy = ok ? e[1] * r : 0.0;
-    oz = ok ? e[2] * r : 0.0;
+    ox = ok ? dlt_to_world(e[0] * r, Plds + 12 * C, 0) : 0.0;   // (a joint nobody sees stays (0, 0, 0): not the rig's centre)
+    oy = ok ? dlt_to_world(e[1] * r, Plds + 12 * C, 1) : 0.0;
+    oz = ok ? dlt_to_world(e[2] * r, Plds + 12 * C, 2) : 0.0;
     os = ok ? ssum * dlt_recip((double)cnt) : 0.0;
 }
 
@@ -599,7 +604,7 @@ __global__ __launch_bounds__(kBlock, (FusedShape<C, METHOD, TIn>::kWaves)) void 
     const PackedWriter<TOut> wr{out4, out_ps};
     const Kp3<TIn> *kp3 = reinterpret_cast<const Kp3<TIn> *>(kpts);
     if constexpr (METHOD == 1) {
-        if (tid < 12 * C) Mlds[tid] = rig.P[tid];  // DLT: the 12 C doubles of M and t hold P instead
+        if (tid < 12 * C + kDltFrame) Mlds[tid] = rig.P[tid];  // DLT: the 12 C doubles of M and t hold P instead, the rig frame behind them
     } else {
         if (tid < 9 * C) Mlds[tid] = rig.M[tid];  // visible after the first __syncthreads() below
         if (tid < 3 * C) Mlds[9 * C + tid] = rig.t[tid];

@@ -679,9 +679,9 @@ __global__ __launch_bounds__(kBlock, kRecomputeWaves) void k_frame_recompute(int
                     dlt_solve(A, cnt >= 2, e);
                     if (cnt >= 2) {
                         const double r = dlt_recip(e[3]);
-                        ox = e[0] * r;
-                        oy = e[1] * r;
-                        oz = e[2] * r;
+                        ox = dlt_to_world(e[0] * r, rig.P + 12 * rig.C, 0);
+                        oy = dlt_to_world(e[1] * r, rig.P + 12 * rig.C, 1);
+                        oz = dlt_to_world(e[2] * r, rig.P + 12 * rig.C, 2);
                         os = ssum * dlt_recip((double)cnt);
                     }
                 }

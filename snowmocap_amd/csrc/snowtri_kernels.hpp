@@ -93,9 +93,12 @@ struct Rig {
     const double *t;
     const int32_t *pairs;
     const double *pairc;  // [npairs][6]: d = t_sc - t_mc, tsum = t_mc + t_sc (host-precomputed)
-    const double *P;      // [C][12]: world->pixel matrices K [R^T | -R^T t] (DLT method)
+    // The DLT method solves in the rig's own frame (include/snowtri.h, SNOWTRI_DLT): c = the mean of the camera centres, s = max |t_c - c|
+    // over cameras and axes (1 when that is 0); a point x of that frame is c + s x in the world.
+    const double *P;      // [C][12]: rig frame -> pixel matrices K [R^T | -R^T (t - c) / s], then kDltFrame doubles (c_x, c_y, c_z, s)
     int32_t C, npairs;
 };
+constexpr int kDltFrame = 4;   // the doubles behind P[C][12]: the kernels keep them in LDS beside P (dlt_to_world, snowtri_fused.hpp)
 
 template <typename TIn>
 __global__ __launch_bounds__(kBlock) void k_triangulate(int64_t F, int Pmax, int J, int Kc, Rig rig,

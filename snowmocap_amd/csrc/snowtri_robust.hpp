@@ -25,9 +25,9 @@ constexpr int kRobustMaxCams = 8;
 constexpr int kRobustMaxDrops = 6;    // at most C - 2 views can go
 constexpr int kRobustMaxTile = 16;    // frames per workgroup
 
-// [P[C][12] | stash [T][kn] fp64 | detection mask per frame]
+// [P[C][12] + the rig frame | stash [T][kn] fp64 | detection mask per frame]
 __host__ __device__ constexpr size_t robust_lds_bytes(int C, int T, int kn) {
-    return (((size_t)96 * C + (size_t)8 * T * kn + (size_t)4 * T) + 15) & ~(size_t)15;
+    return (((size_t)96 * C + 8 * kDltFrame + (size_t)8 * T * kn + (size_t)4 * T) + 15) & ~(size_t)15;
 }
 
 template <int C, typename TIn, typename TOut>
@@ -41,15 +41,15 @@ __global__ __launch_bounds__(kBlock, kRobustWaves) void k_dlt_robust(int64_t F, 
     static_assert(C >= 2 && C <= kRobustMaxCams, "k_dlt_robust: two to eight cameras");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int kn = prm.kn;
-    double *Pl = reinterpret_cast<double *>(smem);                           // [C][12] world->pixel matrices
-    double *stash = Pl + 12 * C;                                             // [T][kn] joint scores
+    double *Pl = reinterpret_cast<double *>(smem);                           // [C][12] rig frame -> pixel matrices, then the frame
+    double *stash = Pl + 12 * C + kDltFrame;                                 // [T][kn] joint scores
     uint32_t *fmask = reinterpret_cast<uint32_t *>(stash + (size_t)T * kn);  // [T] bit c: camera c lists a detection
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t f0 = (int64_t)blockIdx.x * T;
     const int nf = (int)((F - f0) < T ? (F - f0) : T);
     SNOWTRI_DEV_CHECK(f0 >= 0 && f0 < F && nf >= 1 && nf <= T && T <= kRobustMaxTile && kn >= 0 && kn <= J, 60);
-    if (tid < 12 * C) Pl[tid] = rig.P[tid];
+    if (tid < 12 * C + kDltFrame) Pl[tid] = rig.P[tid];
     if (tid < nf) {
         uint32_t m = (1u << C) - 1u;
         if (n_persons) {
@@ -171,7 +171,9 @@ __global__ __launch_bounds__(kBlock, kRobustWaves) void k_dlt_robust(int64_t F, 
         if (live) {
             const int64_t f = f0 + fl;
             Vec4T<TOut> *o = reinterpret_cast<Vec4T<TOut> *>(out4) + (f * Pout) * (int64_t)kn + j;
-            *o = Vec4T<TOut>{(TOut)(ok ? x : 0.0), (TOut)(ok ? y : 0.0), (TOut)(ok ? z : 0.0), (TOut)os};
+            // (x, y, z) is in the rig's frame, where the residuals were taken (P maps that frame to pixels): the world point is written
+            *o = Vec4T<TOut>{(TOut)(ok ? dlt_to_world(x, Pl + 12 * C, 0) : 0.0), (TOut)(ok ? dlt_to_world(y, Pl + 12 * C, 1) : 0.0),
+                             (TOut)(ok ? dlt_to_world(z, Pl + 12 * C, 2) : 0.0), (TOut)os};
             SNOWTRI_DEV_CHECK(fl * kn + j < T * kn, 63);
             stash[fl * kn + j] = os;
             if (out_views) out_views[f * kn + j] = ok ? S : 0u;

@@ -5,13 +5,15 @@ role tracking.track_persons_reference plays for the tracker.  It is not on the p
 and it is slow: an SVD per solve.
 
 The rule (include/snowtri.h, snowtri_triangulate_robust, states it for the C ABI).  One detection per camera.  Per frame f and
-joint j < keypoint_num, inputs converted to fp64, P[c] = K_c [R_c^T | -R_c^T t_c], tau = reproj_threshold_px:
+joint j < keypoint_num, inputs converted to fp64, tau = reproj_threshold_px.  As in method = DLT the solve happens in the rig's own
+frame: c = the mean of the camera centres (summed in camera order), s = max |t_c - c| over cameras and axes (1 if that is 0),
+P[c] = K_c [R_c^T | -R_c^T (t_c - c) / s], and x below is the point in that frame (pixels do not depend on the frame):
 
 1. S = {c : (n_persons is None or n_persons[f][c] > 0) and not (s_c < keypoint_score_threshold)}.  |S| < 2: the record is
    (0, 0, 0, 0), views = 0, resid = 0.
-2. solve(S): X = the DLT solution over the views of S as method = DLT defines it (rows u P[c][2] - P[c][0], v P[c][2] - P[c][1];
-   np.linalg.svd, last right singular vector, dehomogenised); r_c^2 = (p0 / p2 - u_c)^2 + (p1 / p2 - v_c)^2 with p = P[c] (X, 1);
-   m(S) = max_c r_c^2 (np.max: NaN if any is).
+2. solve(S): x = the DLT solution over the views of S as method = DLT defines it (rows u P[c][2] - P[c][0], v P[c][2] - P[c][1];
+   np.linalg.svd, last right singular vector, dehomogenised), X = c + s x; r_c^2 = (p0 / p2 - u_c)^2 + (p1 / p2 - v_c)^2 with
+   p = P[c] (x, 1); m(S) = max_c r_c^2 (np.max: NaN if any is).
 3. d = 0; while |S| >= 3 and d < max_drops and m(S) > tau^2: m_c = m(S \\ {c}) for every c in S in increasing c; drop c* = argmin:
    the lowest c starts as the best, a later candidate replaces it only if its m_c is strictly smaller, or if the best so far is NaN
    and m_c is not (ties go to the lowest c, a NaN never wins against a number); d += 1.
@@ -47,8 +49,27 @@ def projection_matrices(K, R, t):
     return P
 
 
+def rig_frame(t):
+    """-> (c, s): centre and scale of the frame the DLT is solved in (the rule above; oracle/dlt.py::rig_frame is the same)."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1, 3)
+    c = np.zeros(3)
+    for tc in t:                                    # summed in camera order
+        c = c + tc
+    c = c / t.shape[0]
+    s = float(np.max(np.abs(t - c))) if t.size else 0.0
+    return c, (s if s > 0.0 else 1.0)
+
+
+def rig_projection_matrices(K, R, t):
+    """-> (P [C, 3, 4], c, s) with P[c] = K_c [R_c^T | -R_c^T (t_c - c) / s]."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1, 3)
+    c, s = rig_frame(t)
+    return projection_matrices(K, R, (t - c) / s), c, s
+
+
 def _solve(P, uv, masks):
-    """uv [n, C, 2] fp64, masks [n] (every one with >= 2 bits) -> X [n, 3], r2 [n, C] (0 outside the mask), m [n]."""
+    """P of rig_projection_matrices; uv [n, C, 2] fp64, masks [n] (every one with >= 2 bits) -> x [n, 3] in the rig's frame,
+    r2 [n, C] (0 outside the mask), m [n]."""
     n, C = uv.shape[:2]
     X = np.zeros((n, 3))
     r2 = np.zeros((n, C))
@@ -88,7 +109,7 @@ def triangulate_robust_reference(K, R, t, kpts, n_persons, keypoint_score_thresh
     F, C, Pm, J, _ = kpts.shape
     assert Pm == 1, "the robust rule is defined for one detection per camera"
     kn = int(keypoint_num)
-    P = projection_matrices(K, R, t)
+    P, ctr, scl = rig_projection_matrices(K, R, t)
     tau = float(reproj_threshold_px)
     tau2 = tau * tau
     max_drops = int(max_drops)
@@ -190,7 +211,7 @@ def triangulate_robust_reference(K, R, t, kpts, n_persons, keypoint_score_thresh
     flat = out.reshape(N, 4)
     for i in io:
         cams = [c for c in range(C) if (int(S[i]) >> c) & 1]
-        flat[i, :3] = X[i]
+        flat[i, :3] = ctr + scl * X[i]
         flat[i, 3] = np.mean([sc[i, c] for c in cams])
         with np.errstate(all="ignore"):
             resid[i] = np.sqrt(np.mean([r2[i, c] for c in cams]))

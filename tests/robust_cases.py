@@ -74,10 +74,45 @@ def divergence_batch(kind):
     return _freeze(dict(K=K, R=R, t=t, X=X, kpts=kp, n_persons=None))
 
 
+FRAMES_RIGS = ("ring3", "ring8", "mixed8")      # (dlt_frames_cases.rig names; the rig with per-camera intrinsics at two placements)
+
+
+def frames_placements(name):
+    import dlt_frames_cases as fc
+    return fc.MIXED_PLACEMENTS if name.startswith("mixed") else tuple(fc.PLACEMENTS)
+
+
+@functools.lru_cache(maxsize=None)
+def frames_batch(name, placement):
+    """tests/test_gpu_dlt_frames.py: 3 frames of 133 joints, 0.5 px of noise, the outlier recipe, one camera that lists nobody in
+    frame 1, two joints without two views -- generated ONCE at home (the same pixels at every placement); K, R and the rig and scene moved to `placement`."""
+    import dlt_frames_cases as fc
+    K, R, t = fc.rig(name)
+    C = K.shape[0]
+    rng = np.random.default_rng(41 + C)
+    X = synth.make_people(rng, 3, 1)
+    kp, npers = synth.make_keypoints(rng, K, R, t, X, pixel_sigma=0.5, score_range=(2.0, 8.0))
+    kpo, cam = synth.add_outliers(rng, kp)
+    npers = npers.copy()
+    npers[1, (C - 1) // 2] = 0
+    kpo[0, :, 0, 7, 2] = 0.5                          # a joint nobody sees, a joint one camera sees: the zero record
+    kpo[2, 1:, 0, 9, 2] = 0.5
+    tp, Xp, _, _ = fc.place(t, X, placement)
+    return _freeze(dict(K=K, R=R, t=tp, X=Xp, kpts=kpo, cam=cam, n_persons=npers))
+
+
+def batch(batch_key):
+    if batch_key[0] == "parity":
+        return parity_batch(*batch_key[1:])
+    if batch_key[0] == "frames":
+        return frames_batch(*batch_key[1:])
+    return divergence_batch(batch_key[1])
+
+
 @functools.lru_cache(maxsize=None)
 def reference(batch_key, kn, tau, max_drops):
-    """batch_key: ("parity", name, F, J, dtype) or ("divergence", kind)."""
-    b = parity_batch(*batch_key[1:]) if batch_key[0] == "parity" else divergence_batch(batch_key[1])
+    """batch_key: ("parity", name, F, J, dtype), ("divergence", kind) or ("frames", name, placement)."""
+    b = batch(batch_key)
     return _freeze(triangulate_robust_reference(b["K"], b["R"], b["t"], b["kpts"], b["n_persons"], KTHR, kn, tau, max_drops))
 
 
@@ -96,4 +131,10 @@ def gpu_cases():
             cases.append((("parity", name, 40, 17, "float32"), 17, tau, md))
     for kind in ("one", "all", "mixed"):
         cases.append((("divergence", kind), 133, 6.0, 6))
+    cases += frames_cases()
     return cases
+
+
+# what tests/test_gpu_dlt_frames.py compares with the reference: every placement of every rig, tau 6, one and six drops
+def frames_cases():
+    return [(("frames", name, placement), 133, 6.0, md) for name in FRAMES_RIGS for placement in frames_placements(name) for md in (1, 6)]
