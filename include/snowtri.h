@@ -485,6 +485,53 @@ int snowtri_fill_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void 
                              void *out, uint8_t *fill /* [T][m], may be NULL */, int memspace, void *stream);
 int snowtri_fill_block_frames(void);
 
+/* Despiking: one- and two-frame jumps taken out of a track of joint records before gap filling (no reference counterpart).  A joint
+ * that was SEEN in the wrong place for a frame or two -- a flipped limb, a hand found on the neighbour -- is a measured record: the
+ * gap filler leaves it alone and the second-order filter rings on it for many frames.  The test is temporal, so it does not care
+ * which triangulation route produced the record.  xyzs[T][m][4] of xyz_dtype, the records snowtri_fill_joint_track takes ->
+ * out[T][m][4] of the same type, codes[T][m] uint8 (may be NULL: it then costs nothing).  All decisions are made on the values
+ * converted to fp64:
+ *   1. MISSING / MEASURED  exactly as for gap filling: record (t, l) is missing if its score == 0 (so -0.0 counts) or any of its four
+ *      values is not finite; otherwise it is measured.
+ *   2. WINDOW  for record (t, l) the window W holds the measured records of lane l at frames max(0, t - h) .. min(T - 1, t + h), the
+ *      record itself included; h = half_window (1..4), n = |W|.
+ *   3. MEDIAN  for each of x, y, z: the n values sorted ascending, med = (v[(n - 1) / 2] + v[n / 2]) * 0.5 (integer division; one
+ *      addition and one multiplication, each rounded once).
+ *   4. DEVIATION  d = value - med per coordinate, d2 = (dx * dx + dy * dy) + dz * dz, every operation rounded separately (no FMA
+ *      contraction: the same rule as for the tracker's distances).
+ *   5. SPIKE TEST  a measured record is a SPIKE iff n >= 3 and d2 > tol * tol, the product formed once in fp64.  The comparison is
+ *      exactly that: d2 == tol * tol is not a spike, and neither is a NaN d2 (from a sum that overflowed).
+ *   6. ALL SPIKES ARE DECIDED ON THE INPUT: removing one spike never changes the verdict on another; there is no iteration.
+ *   7. OUTPUT  mode SNOWTRI_DESPIKE_MARK: a spike is written as four +0.0 -- the condense step's zero record, which
+ *      snowtri_fill_joint_track bridges.  mode SNOWTRI_DESPIKE_REPLACE: a spike is written as (med_x + 0.0, med_y + 0.0, med_z + 0.0),
+ *      each rounded once to xyz_dtype, with the record's own score bits (the + 0.0 makes a zero median +0.0 whichever zero the sort
+ *      left in the middle).  Every other record is copied bit for bit (NaN payloads of missing records survive).
+ *   8. CODES  SNOWTRI_DESPIKE_KEPT: measured, tested, copied.  SNOWTRI_DESPIKE_SPIKE.  SNOWTRI_DESPIKE_MISSING: missing, copied.
+ *      SNOWTRI_DESPIKE_UNSUPPORTED: measured with n < 3, copied untested.
+ *   9. Lanes are independent: the result of a lane depends on nothing but that lane.
+ * snowmocap_amd/despike.py::despike_joint_track_reference is this rule in NumPy; the kernel (k_despike,
+ * snowmocap_amd/csrc/snowtri_despike.hpp) agrees with it bit for bit.  What the rule does NOT do: a run of more than h wrong records
+ * in a window outvotes the right ones, and on a fast path (more than about tol / h per frame) the median of a window with holes
+ * sits off-centre, so clean records next to dropouts are flagged.
+ * half_window outside 1..4, tol negative or NaN (+infinity is allowed: nothing is a spike), an unknown mode, dtype or memspace,
+ * negative T or m, a NULL xyzs or out: SNOWTRI_ERR_BAD_ARG, and snowtri_last_error() names the argument.  out must not overlap
+ * xyzs (a tile of the kernel reads records of its neighbours): SNOWTRI_ERR_BAD_ARG.  Sizes: T * m <= 2^58 records and
+ * ceil(T / (4 * snowtri_despike_block_frames())) * ceil(m / 64) <= 2^31 - 1 workgroups; beyond either SNOWTRI_ERR_BAD_ARG and
+ * snowtri_last_error() names the limit.  T == 0 (or m == 0) is SNOWTRI_OK and touches nothing.  A scratch-only context (C == 0)
+ * is enough.  SNOWTRI_DEVICE: asynchronous on `stream`, no host read, no internal stream; xyzs and out aligned to 16 bytes (else
+ * SNOWTRI_ERR_BAD_ARG).  SNOWTRI_HOST: staged and synchronous.
+ * snowtri_despike_block_frames(): frames per tile of the kernel (results do not depend on it; tests aim spikes at its multiples). */
+#define SNOWTRI_DESPIKE_MARK 0    /* mode: a spike becomes the zero record                     */
+#define SNOWTRI_DESPIKE_REPLACE 1 /* mode: a spike becomes the window median, its score kept    */
+#define SNOWTRI_DESPIKE_KEPT 0        /* measured, tested, copied                               */
+#define SNOWTRI_DESPIKE_SPIKE 1       /* measured, further than tol from the window median      */
+#define SNOWTRI_DESPIKE_MISSING 2     /* missing, copied                                        */
+#define SNOWTRI_DESPIKE_UNSUPPORTED 3 /* measured with fewer than 3 measured records in its window, copied untested */
+int snowtri_despike_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t half_window,
+                                double tol, int32_t mode, void *out, uint8_t *codes /* [T][m], may be NULL */, int memspace,
+                                void *stream);
+int snowtri_despike_block_frames(void);
+
 /* N4  Keypoint-level lens undistortion, for detections made on RAW frames (the reference undistorts whole
  * images before detection: main.py:52 cv2.undistort(frame, K, D)).  OpenCV's 5-coefficient Brown-Conrady model,
  * D[C][5] = (k1, k2, p1, p2, k3) per camera (camera_group_floor.json:53-61; Camera.D, camera.py:24,44); K as

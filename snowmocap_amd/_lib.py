@@ -19,6 +19,8 @@ F32, F64 = 0, 1
 HOST, DEVICE = 0, 1
 PAIRWISE, DLT, DLT_ROBUST = 0, 1, 2
 FLAG_SINGULAR, FLAG_OVERFLOW, FLAG_FASTPATH = 1, 2, 4
+DESPIKE_MARK, DESPIKE_REPLACE = 0, 1                       # snowtri_despike_joint_track: mode
+DESPIKE_KEPT, DESPIKE_SPIKE, DESPIKE_MISSING, DESPIKE_UNSUPPORTED = 0, 1, 2, 3   # ... and its codes
 CALL_NO_ZERO_FILL = 1          # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
 TEST_LIB_PATH = os.path.join(_HERE, "libsnowtri_dbg.so")   # -DSNOWTRI_DEBUG_BOUNDS -DSNOWTRI_TEST_KNOBS (tests only: use_library)
 
@@ -127,6 +129,9 @@ _SIGNATURES = {
                                         ct.c_int, _c_p]),
     "snowtri_fill_joint_track": (ct.c_int, [_c_p, ct.c_int64, ct.c_int64, _c_p, ct.c_int, ct.c_int32, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_fill_block_frames": (ct.c_int, []),
+    "snowtri_despike_joint_track": (ct.c_int, [_c_p, ct.c_int64, ct.c_int64, _c_p, ct.c_int, ct.c_int32, ct.c_double, ct.c_int32, _c_p, _c_p,
+                                               ct.c_int, _c_p]),
+    "snowtri_despike_block_frames": (ct.c_int, []),
     "snowtri_ctx_set_distortion": (ct.c_int, [_c_p, _c_p]),
     "snowtri_undistort_keypoints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, _c_p, ct.c_int,
                                                ct.c_int, _c_p]),

@@ -34,6 +34,7 @@
 #include "snowtri_undistort.hpp"
 #include "snowtri_track.hpp"
 #include "snowtri_fill.hpp"
+#include "snowtri_despike.hpp"
 #include "snowtri_kernels.hpp"
 
 using namespace snowtri;
@@ -2092,6 +2093,79 @@ int snowtri_fill_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void 
     if (memspace == SNOWTRI_HOST) {
         HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
         if (fill) HIP_TRY(hipMemcpyAsync(fill, d_fill, f_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SNOWTRI_OK;
+}
+
+// ------------------------------------------------------------------------------- despiking
+}  // extern "C"
+
+namespace {
+template <typename IO>
+void launch_despike(int half_window, dim3 grid, dim3 block, hipStream_t st, int64_t T, int64_t m, double tol2, int mode, int64_t ncols,
+                    const void *dx, void *d_out, uint8_t *d_codes) {
+    switch (half_window) {
+    case 1: hipLaunchKernelGGL((k_despike<IO, 1>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
+    case 2: hipLaunchKernelGGL((k_despike<IO, 2>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
+    case 3: hipLaunchKernelGGL((k_despike<IO, 3>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
+    default: hipLaunchKernelGGL((k_despike<IO, 4>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int snowtri_despike_block_frames(void) { return kDespikeBlockFrames; }
+
+int snowtri_despike_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t half_window, double tol,
+                                int32_t mode, void *out, uint8_t *codes, int memspace, void *stream) {
+    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: null context");
+    if (xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: unknown xyz_dtype");
+    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: unknown memspace");
+    if (T < 0 || m < 0) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: T < 0 or m < 0");
+    if (half_window < 1 || half_window > kDespikeMaxHalf)
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: half_window must lie in 1..4");
+    if (!(tol >= 0.0)) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: tol must be >= 0 and not NaN");
+    if (mode != SNOWTRI_DESPIKE_MARK && mode != SNOWTRI_DESPIKE_REPLACE) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: unknown mode");
+    if (T == 0 || m == 0) return SNOWTRI_OK;
+    if (!xyzs || !out) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: null array (xyzs or out)");
+    // one workgroup per 64 lanes x (kDespikeWaves * kDespikeBlockFrames) frames on a one-dimensional grid; 64-bit byte offsets of 32-byte records
+    const int64_t wg_frames = (int64_t)kDespikeWaves * kDespikeBlockFrames;
+    const int64_t ncols = (m + 63) / 64, nrows = (T + wg_frames - 1) / wg_frames;
+    if (T > ((int64_t)1 << 58) / m) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: T * m must not exceed 2^58 records");
+    if (nrows > (int64_t)0x7fffffff / ncols)
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: ceil(T / 256) * ceil(m / 64) must not exceed 2^31 - 1 workgroups");
+    const size_t bytes = dtype_size(xyz_dtype) * 4 * (size_t)T * (size_t)m, c_bytes = (size_t)T * (size_t)m;
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) | ((uintptr_t)out)) & 15u))
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: xyzs and out must be aligned to 16 bytes");
+    if ((uintptr_t)xyzs < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)xyzs + bytes)
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: out must not overlap xyzs");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const void *dx = xyzs;
+    void *d_out = out;
+    uint8_t *d_codes = codes;
+    if (memspace == SNOWTRI_HOST) {
+        int rc = ctx->in.ensure(bytes);
+        if (rc) return rc;
+        rc = ctx->out.ensure(pad16(bytes) + c_bytes);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->in.p, xyzs, bytes, hipMemcpyHostToDevice, st));
+        dx = ctx->in.p;
+        d_out = ctx->out.p;
+        d_codes = codes ? (uint8_t *)ctx->out.p + pad16(bytes) : nullptr;
+    }
+    const dim3 grid((unsigned)(ncols * nrows)), block(64, kDespikeWaves);
+    const double tol2 = tol * tol;   // formed once, in fp64
+    if (xyz_dtype == SNOWTRI_F32)
+        launch_despike<float>((int)half_window, grid, block, st, T, m, tol2, (int)mode, ncols, dx, d_out, d_codes);
+    else
+        launch_despike<double>((int)half_window, grid, block, st, T, m, tol2, (int)mode, ncols, dx, d_out, d_codes);
+    HIP_TRY(hipGetLastError());
+    if (memspace == SNOWTRI_HOST) {
+        HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+        if (codes) HIP_TRY(hipMemcpyAsync(codes, d_codes, c_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return SNOWTRI_OK;

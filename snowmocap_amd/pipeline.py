@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib
 from .batch import BatchTriangulator
 from .blender import CONTROL_POINT_NAMES, _WIDTH
+from .despike import DESPIKE_MARK, DESPIKE_MISSING, DESPIKE_REPLACE, DESPIKE_UNSUPPORTED, despike_args, despike_joint_track
 from .fill import FILL_MISSING, MAX_GAP, fill_joint_track
 
 
@@ -39,7 +40,7 @@ class TrackPipeline:
     def close(self):
         self.bt.close()
 
-    def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0):
+    def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0, despike=None):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -69,7 +70,16 @@ class TrackPipeline:
         becomes that of the bridged id, the tracked gather holds zero records where the person was absent, so those are
         interpolated like any missing joint; track_id and present are then the bridged ones and bridged [F, P] (bool) marks
         the frames that were added.  0 (the default): nothing of this, the dict is today's.  Not addressed: a joint that is
-        missing in the first frame of a sequence for more than g frames still seeds its filter with zeros."""
+        missing in the first frame of a sequence for more than g frames still seeds its filter with zeros.
+        despike=(tol, half_window): one- and two-frame jumps are taken out first (despike.despike_joint_track: a measured record
+        further than tol metres from the median of its lane's measured records at frames t - half_window .. t + half_window).  The
+        pass runs on exactly the arrays the fill is given (or would be given), immediately before it -- with ragged="track" after
+        the gather per track slot.  With fill_gaps > 0 a spike becomes the zero record (DESPIKE_MARK) and the fill bridges it; with
+        fill_gaps == 0 it becomes the window median (DESPIKE_REPLACE), since without a filler a marked spike would reach the filter
+        as a position at the origin.  Adds spike_codes [F, P, kn] (uint8, despike.DESPIKE_*) and xyzs_despiked [F, P, kn, 4], the
+        records the fill (or the filters) consumed; outside every filtered sequence: the records of xyzs, DESPIKE_MISSING or
+        DESPIKE_UNSUPPORTED (untested).  None (the default): off, nothing changes and no extra key appears."""
+        dsp = despike_args(despike)
         import torch
         dev = torch.device("cuda", self.device)
         if not torch.is_tensor(kpts):
@@ -99,6 +109,7 @@ class TrackPipeline:
         fill_gaps = int(fill_gaps)
         if fill_gaps < 0 or fill_gaps > MAX_GAP:
             raise ValueError(f"fill_gaps must be 0 (off) or a max_gap in 1..{MAX_GAP} (got {fill_gaps})")
+        dsp_mode = DESPIKE_MARK if fill_gaps > 0 else DESPIKE_REPLACE
         pts = torch.empty((F, self.P, 24, 4), dtype=torch.float64, device=dev)
         val = torch.empty((F, self.P, 24), dtype=torch.uint8, device=dev)
 
@@ -106,11 +117,15 @@ class TrackPipeline:
             _lib.check(L.snowtri_blender_points(h, n, self.kn, ct.c_void_p(x.data_ptr()), _lib.F64, ct.c_void_p(p_out.data_ptr()),
                                                 ct.c_void_p(v_out.data_ptr()), _lib.DEVICE, st), "snowtri_blender_points")
 
-        def filter_rows(src, idx, i, sm, pts_s, filled=None, codes=None):
-            """slot i over the frames idx (the first of them seeds the filters): gather, [fill into filled / codes,] N1, N2 points,
-            N2 filters, scatter"""
+        def filter_rows(src, idx, i, sm, pts_s, filled=None, codes=None, desp=None, scodes=None):
+            """slot i over the frames idx (the first of them seeds the filters): gather, [despike into desp / scodes,] [fill into
+            filled / codes,] N1, N2 points, N2 filters, scatter"""
             T = int(idx.numel())
             xi = src[idx, i].contiguous()                                   # [T, kn, 4]
+            if desp is not None:
+                xi, di = despike_joint_track(self.bt.ctx, xi, dsp[1], dsp[0], dsp_mode)
+                desp[idx, i] = xi
+                scodes[idx, i] = di
             if filled is not None:
                 xi, ci = fill_joint_track(self.bt.ctx, xi, fill_gaps)
                 filled[idx, i] = xi
@@ -134,6 +149,11 @@ class TrackPipeline:
             """(xyzs_filled, fill) before any sequence has been filled: the records as they are, measured or missing"""
             return x.clone(), ((x[..., 3] == 0) | ~torch.isfinite(x).all(dim=-1)).to(torch.uint8) * FILL_MISSING
 
+        def undespiked(x):
+            """(xyzs_despiked, spike_codes) before any sequence has been despiked: the records as they are, missing or untested"""
+            miss = (x[..., 3] == 0) | ~torch.isfinite(x).all(dim=-1)
+            return x.clone(), torch.where(miss, DESPIKE_MISSING, DESPIKE_UNSUPPORTED).to(torch.uint8)
+
         if ragged == "track":
             from .tracking import PersonTracker, bridge_track_ids
             trk_out = PersonTracker(self.bt.ctx, S=self.P, center_point_index=self.bt.params.center_point_index, gate=track_gate,
@@ -143,13 +163,14 @@ class TrackPipeline:
             if fill_gaps:
                 tid = bridge_track_ids(tid, fill_gaps)
             filled, codes = unfilled(xyzs) if fill_gaps else (None, None)
+            desp, scodes = undespiked(xyzs) if dsp else (None, None)
             sm = torch.zeros_like(xyzs)
             pts.zero_()
             val.zero_()
             pts_s = torch.zeros_like(pts)
             for i in range(self.P):
                 for one in np.unique(tid[:, i][tid[:, i] >= 0]):
-                    filter_rows(xyzs, torch.from_numpy(np.nonzero(tid[:, i] == one)[0]).to(dev), i, sm, pts_s, filled, codes)
+                    filter_rows(xyzs, torch.from_numpy(np.nonzero(tid[:, i] == one)[0]).to(dev), i, sm, pts_s, filled, codes, desp, scodes)
             present = trk_out["person_of"] >= 0
             res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"], flags=tri["flags"],
                        tracked=present.sum(dim=1).to(torch.int32), present=present, track_id=trk_out["track_id"],
@@ -160,11 +181,16 @@ class TrackPipeline:
                 res["bridged"] = res["present"] & ~present
                 res["tracked"] = res["present"].sum(dim=1).to(torch.int32)
                 res["xyzs_filled"], res["fill"] = filled, codes
+            if dsp:
+                res["xyzs_despiked"], res["spike_codes"] = desp, scodes
             return res
         if tracked is None:
             src = xyzs
+            if dsp:
+                desp, scodes = despike_joint_track(self.bt.ctx, src, dsp[1], dsp[0], dsp_mode)
+                src = desp
             if fill_gaps:
-                filled, codes = fill_joint_track(self.bt.ctx, xyzs, fill_gaps)
+                filled, codes = fill_joint_track(self.bt.ctx, src, fill_gaps)
                 src = filled
             sm = torch.empty_like(xyzs)                    # only the points are filtered, the scores copied (triangulation.py:169-184)
             _lib.check(L.snowtri_smooth_joint_track(h, F, self.P * self.kn, ct.c_void_p(src.data_ptr()), *fzrd, ct.c_void_p(sm.data_ptr()),
@@ -179,16 +205,19 @@ class TrackPipeline:
             # slot by slot over the frames that carry it (frame 0 among them: it seeds the slot's filters)
             trk = torch.from_numpy(tracked).to(dev)
             filled, codes = unfilled(xyzs) if fill_gaps else (None, None)
+            desp, scodes = undespiked(xyzs) if dsp else (None, None)
             sm = torch.zeros_like(xyzs)
             pts.zero_()
             val.zero_()
             pts_s = torch.zeros_like(pts)
             for i in range(int(tracked[0]) if F else 0):
-                filter_rows(xyzs, torch.nonzero(trk > i).view(-1), i, sm, pts_s, filled, codes)
+                filter_rows(xyzs, torch.nonzero(trk > i).view(-1), i, sm, pts_s, filled, codes, desp, scodes)
         res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"],
                    flags=tri["flags"], tracked=trk)
         if fill_gaps:
             res["xyzs_filled"], res["fill"] = filled, codes
+        if dsp:
+            res["xyzs_despiked"], res["spike_codes"] = desp, scodes
         return res
 
     @staticmethod
@@ -236,7 +265,9 @@ class ShardedTrackPipeline:
     exchange and the N2 hold + carry exchanges run on those blocks unchanged (an empty block is a rank none of whose frames
     carries the slot; the block with frame 0 starts the sequence).
     TrackPipeline.run's fill_gaps is NOT offered here: a gap that crosses a shard boundary needs the measured records on both
-    sides of it, i.e. a halo exchange of up to max_gap frames per rank before the fill, which has not been built."""
+    sides of it, i.e. a halo exchange of up to max_gap frames per rank before the fill, which has not been built.  Its despike is
+    left out for the same reason: the window of a record within half_window frames of a shard boundary holds records of the
+    neighbouring rank."""
 
     def __init__(self, K, R, t, thresholds, blender_smooth_profile, n_persons_out=1, device=0, group=None, method=_lib.PAIRWISE):
         self.pipe = TrackPipeline(K, R, t, thresholds, blender_smooth_profile, n_persons_out=n_persons_out, device=device, method=method)
