@@ -454,7 +454,7 @@ int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t 
  * snowtri_triangulate_condense and snowtri_track_gather write them -> out[T][m][4] of the same type, fill[T][m] uint8 codes (may be
  * NULL: it then costs nothing).  All decisions and arithmetic are made on the values converted to fp64:
  *   1. MISSING  record (t, l) is missing if its score == 0 (so -0.0 counts) or any of its four values is not finite; otherwise it
- *      is MEASURED.
+ *      is MEASURED (rec_is_missing, snowmocap_amd/csrc/snowtri_record.hpp).
  *   2. INTERIOR GAP  a measured record at frame a and the next measured record of the same lane at frame b, g = b - a - 1 with
  *      1 <= g <= max_gap: for k = 1..g record a + k becomes the linear interpolation of the two in all four components (the score
  *      included): w = (double)k / (double)(g + 1), d = B - A, p = w * d, v = A + p with every operation rounded separately (no FMA
@@ -492,7 +492,7 @@ int snowtri_fill_block_frames(void);
  * out[T][m][4] of the same type, codes[T][m] uint8 (may be NULL: it then costs nothing).  All decisions are made on the values
  * converted to fp64:
  *   1. MISSING / MEASURED  exactly as for gap filling: record (t, l) is missing if its score == 0 (so -0.0 counts) or any of its four
- *      values is not finite; otherwise it is measured.
+ *      values is not finite; otherwise it is measured (rec_is_missing, snowmocap_amd/csrc/snowtri_record.hpp).
  *   2. WINDOW  for record (t, l) the window W holds the measured records of lane l at frames max(0, t - h) .. min(T - 1, t + h), the
  *      record itself included; h = half_window (1..4), n = |W|.
  *   3. MEDIAN  for each of x, y, z: the n values sorted ascending, med = (v[(n - 1) / 2] + v[n / 2]) * 0.5 (integer division; one

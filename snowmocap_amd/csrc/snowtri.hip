@@ -2046,101 +2046,33 @@ int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t 
     return SNOWTRI_OK;
 }
 
-// ------------------------------------------------------------------------------- gap filling
-int snowtri_fill_block_frames(void) { return kFillBlockFrames; }
-
-int snowtri_fill_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t max_gap, void *out, uint8_t *fill,
-                             int memspace, void *stream) {
-    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: null context");
-    if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: unknown dtype or memory space");
-    if (T < 0 || m < 0) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: T < 0 or m < 0");
-    if (max_gap < 1 || max_gap > kFillMaxGap) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: max_gap must lie in 1..255");
-    if (T == 0 || m == 0) return SNOWTRI_OK;
-    if (!xyzs || !out) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: null array");
-    // one workgroup per 64 lanes x (kFillWaves * kFillBlockFrames) frames on a one-dimensional grid; 64-bit byte offsets of 32-byte records
-    const int64_t ncols = (m + 63) / 64, nrows = (T + (int64_t)kFillWaves * kFillBlockFrames - 1) / ((int64_t)kFillWaves * kFillBlockFrames);
-    if (T > ((int64_t)1 << 58) / m)
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: T * m must not exceed 2^58 records");
-    if (nrows > (int64_t)0x7fffffff / ncols)
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: ceil(T / 256) * ceil(m / 64) must not exceed 2^31 - 1 workgroups");
-    const size_t bytes = dtype_size(xyz_dtype) * 4 * (size_t)T * (size_t)m, f_bytes = (size_t)T * (size_t)m;
-    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) | ((uintptr_t)out)) & 15u))
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: xyzs and out must be aligned to 16 bytes");
-    if ((uintptr_t)xyzs < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)xyzs + bytes)
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: out must not overlap xyzs");
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    const void *dx = xyzs;
-    void *d_out = out;
-    uint8_t *d_fill = fill;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(pad16(bytes) + f_bytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, xyzs, bytes, hipMemcpyHostToDevice, st));
-        dx = ctx->in.p;
-        d_out = ctx->out.p;
-        d_fill = fill ? (uint8_t *)ctx->out.p + pad16(bytes) : nullptr;
-    }
-    const dim3 grid((unsigned)(ncols * nrows)), block(64, kFillWaves);
-    if (xyz_dtype == SNOWTRI_F32)
-        hipLaunchKernelGGL(k_fill_gaps<float>, grid, block, 0, st, T, m, (int)max_gap, ncols, (const uint4 *)dx, (uint4 *)d_out, d_fill);
-    else
-        hipLaunchKernelGGL(k_fill_gaps<double>, grid, block, 0, st, T, m, (int)max_gap, ncols, (const uint4 *)dx, (uint4 *)d_out, d_fill);
-    HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
-        if (fill) HIP_TRY(hipMemcpyAsync(fill, d_fill, f_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
-}
-
-// ------------------------------------------------------------------------------- despiking
 }  // extern "C"
 
+// ------------------------------------------------------------------------------- record passes: gap filling, despiking
 namespace {
-template <typename IO>
-void launch_despike(int half_window, dim3 grid, dim3 block, hipStream_t st, int64_t T, int64_t m, double tol2, int mode, int64_t ncols,
-                    const void *dx, void *d_out, uint8_t *d_codes) {
-    switch (half_window) {
-    case 1: hipLaunchKernelGGL((k_despike<IO, 1>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
-    case 2: hipLaunchKernelGGL((k_despike<IO, 2>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
-    case 3: hipLaunchKernelGGL((k_despike<IO, 3>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
-    default: hipLaunchKernelGGL((k_despike<IO, 4>), grid, block, 0, st, T, m, tol2, mode, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes); break;
-    }
-}
-}  // namespace
 
-extern "C" {
-
-int snowtri_despike_block_frames(void) { return kDespikeBlockFrames; }
-
-int snowtri_despike_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t half_window, double tol,
-                                int32_t mode, void *out, uint8_t *codes, int memspace, void *stream) {
-    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: null context");
-    if (xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: unknown xyz_dtype");
-    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: unknown memspace");
-    if (T < 0 || m < 0) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: T < 0 or m < 0");
-    if (half_window < 1 || half_window > kDespikeMaxHalf)
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: half_window must lie in 1..4");
-    if (!(tol >= 0.0)) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: tol must be >= 0 and not NaN");
-    if (mode != SNOWTRI_DESPIKE_MARK && mode != SNOWTRI_DESPIKE_REPLACE) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: unknown mode");
+// The host side of a pass xyzs[T][m][4] -> out[T][m][4] (+ codes[T][m], may be null) over a track of joint records, after the
+// entry point `who` has checked its context and its own parameters: every other refusal (nothing is written or enqueued on one),
+// an empty track (OK before any pointer is looked at), the staging of host arrays through ctx->in / ctx->out, and between the
+// two halves of that launch(grid, block, st, ncols, dx, d_out, d_codes) for the kernel.
+template <typename Launch>
+int record_pass(const char *who, snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, void *out, uint8_t *codes, int memspace,
+                void *stream, Launch launch) {
+    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) return refuse("unknown xyz_dtype");
+    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
+    if (T < 0 || m < 0) return refuse("T < 0 or m < 0");
     if (T == 0 || m == 0) return SNOWTRI_OK;
-    if (!xyzs || !out) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: null array (xyzs or out)");
-    // one workgroup per 64 lanes x (kDespikeWaves * kDespikeBlockFrames) frames on a one-dimensional grid; 64-bit byte offsets of 32-byte records
-    const int64_t wg_frames = (int64_t)kDespikeWaves * kDespikeBlockFrames;
+    if (!xyzs || !out) return refuse("null array (xyzs or out)");
+    // one workgroup per 64 lanes x (kRecWaves * kRecBlockFrames) frames on a one-dimensional grid; 64-bit byte offsets of 32-byte records
+    const int64_t wg_frames = (int64_t)kRecWaves * kRecBlockFrames;
     const int64_t ncols = (m + 63) / 64, nrows = (T + wg_frames - 1) / wg_frames;
-    if (T > ((int64_t)1 << 58) / m) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: T * m must not exceed 2^58 records");
-    if (nrows > (int64_t)0x7fffffff / ncols)
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: ceil(T / 256) * ceil(m / 64) must not exceed 2^31 - 1 workgroups");
+    if (T > ((int64_t)1 << 58) / m) return refuse("T * m must not exceed 2^58 records");
+    if (nrows > (int64_t)0x7fffffff / ncols) return refuse("ceil(T / 256) * ceil(m / 64) must not exceed 2^31 - 1 workgroups");
     const size_t bytes = dtype_size(xyz_dtype) * 4 * (size_t)T * (size_t)m, c_bytes = (size_t)T * (size_t)m;
-    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) | ((uintptr_t)out)) & 15u))
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: xyzs and out must be aligned to 16 bytes");
-    if ((uintptr_t)xyzs < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)xyzs + bytes)
-        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: out must not overlap xyzs");
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) | ((uintptr_t)out)) & 15u)) return refuse("xyzs and out must be aligned to 16 bytes");
+    // (a neighbouring tile reads through xyzs what this one writes through out)
+    if ((uintptr_t)xyzs < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)xyzs + bytes) return refuse("out must not overlap xyzs");
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const void *dx = xyzs;
@@ -2156,12 +2088,7 @@ int snowtri_despike_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const vo
         d_out = ctx->out.p;
         d_codes = codes ? (uint8_t *)ctx->out.p + pad16(bytes) : nullptr;
     }
-    const dim3 grid((unsigned)(ncols * nrows)), block(64, kDespikeWaves);
-    const double tol2 = tol * tol;   // formed once, in fp64
-    if (xyz_dtype == SNOWTRI_F32)
-        launch_despike<float>((int)half_window, grid, block, st, T, m, tol2, (int)mode, ncols, dx, d_out, d_codes);
-    else
-        launch_despike<double>((int)half_window, grid, block, st, T, m, tol2, (int)mode, ncols, dx, d_out, d_codes);
+    launch(dim3((unsigned)(ncols * nrows)), dim3(64, kRecWaves), st, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes);
     HIP_TRY(hipGetLastError());
     if (memspace == SNOWTRI_HOST) {
         HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
@@ -2169,6 +2096,54 @@ int snowtri_despike_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const vo
         HIP_TRY(hipStreamSynchronize(st));
     }
     return SNOWTRI_OK;
+}
+
+template <typename IO>
+void launch_despike(int half_window, dim3 grid, dim3 block, hipStream_t st, int64_t T, int64_t m, double tol2, int mode, int64_t ncols,
+                    const uint4 *dx, uint4 *d_out, uint8_t *d_codes) {
+    switch (half_window) {
+    case 1: hipLaunchKernelGGL((k_despike<IO, 1>), grid, block, 0, st, T, m, tol2, mode, ncols, dx, d_out, d_codes); break;
+    case 2: hipLaunchKernelGGL((k_despike<IO, 2>), grid, block, 0, st, T, m, tol2, mode, ncols, dx, d_out, d_codes); break;
+    case 3: hipLaunchKernelGGL((k_despike<IO, 3>), grid, block, 0, st, T, m, tol2, mode, ncols, dx, d_out, d_codes); break;
+    default: hipLaunchKernelGGL((k_despike<IO, 4>), grid, block, 0, st, T, m, tol2, mode, ncols, dx, d_out, d_codes); break;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int snowtri_fill_block_frames(void) { return kRecBlockFrames; }
+int snowtri_despike_block_frames(void) { return kRecBlockFrames; }
+
+int snowtri_fill_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t max_gap, void *out, uint8_t *fill,
+                             int memspace, void *stream) {
+    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: null context");
+    if (max_gap < 1 || max_gap > kFillMaxGap) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_fill_joint_track: max_gap must lie in 1..255");
+    return record_pass("snowtri_fill_joint_track", ctx, T, m, xyzs, xyz_dtype, out, fill, memspace, stream,
+                       [=](dim3 grid, dim3 block, hipStream_t st, int64_t ncols, const uint4 *dx, uint4 *d_out, uint8_t *d_fill) {
+                           if (xyz_dtype == SNOWTRI_F32)
+                               hipLaunchKernelGGL(k_fill_gaps<float>, grid, block, 0, st, T, m, (int)max_gap, ncols, dx, d_out, d_fill);
+                           else
+                               hipLaunchKernelGGL(k_fill_gaps<double>, grid, block, 0, st, T, m, (int)max_gap, ncols, dx, d_out, d_fill);
+                       });
+}
+
+int snowtri_despike_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, int32_t half_window, double tol,
+                                int32_t mode, void *out, uint8_t *codes, int memspace, void *stream) {
+    if (!ctx) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: null context");
+    if (half_window < 1 || half_window > kDespikeMaxHalf)
+        return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: half_window must lie in 1..4");
+    if (!(tol >= 0.0)) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: tol must be >= 0 and not NaN");
+    if (mode != SNOWTRI_DESPIKE_MARK && mode != SNOWTRI_DESPIKE_REPLACE) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_despike_joint_track: unknown mode");
+    const double tol2 = tol * tol;   // formed once, in fp64
+    return record_pass("snowtri_despike_joint_track", ctx, T, m, xyzs, xyz_dtype, out, codes, memspace, stream,
+                       [=](dim3 grid, dim3 block, hipStream_t st, int64_t ncols, const uint4 *dx, uint4 *d_out, uint8_t *d_codes) {
+                           if (xyz_dtype == SNOWTRI_F32)
+                               launch_despike<float>((int)half_window, grid, block, st, T, m, tol2, (int)mode, ncols, dx, d_out, d_codes);
+                           else
+                               launch_despike<double>((int)half_window, grid, block, st, T, m, tol2, (int)mode, ncols, dx, d_out, d_codes);
+                       });
 }
 
 }  // extern "C"

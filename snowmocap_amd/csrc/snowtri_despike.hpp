@@ -8,9 +8,9 @@
 // median with its own score (REPLACE); everything else is copied bit for bit.  Every verdict is made on the input: no iteration.
 //
 // The geometry is k_fill_gaps': one thread per lane l < m, consecutive threads on consecutive lanes, so a wave reads 64 adjacent
-// 16- or 32-byte records of one frame with 16-byte loads; a wave owns a TILE of 64 lanes x kDespikeBlockFrames frames (four
+// 16- or 32-byte records of one frame with 16-byte loads; a wave owns a TILE of 64 lanes x kRecBlockFrames frames (four
 // tiles, consecutive in time, per workgroup), writes exactly the records of its tile and reads, besides them, the H frames
-// before and the H frames after it (clipped to the array): 1 + 2 H / kDespikeBlockFrames reads and 1 write per record.
+// before and the H frames after it (clipped to the array): 1 + 2 H / kRecBlockFrames reads and 1 write per record.
 //
 // Inside a tile two rings of W = 2 H + 1 slots stay in registers, slot of frame t = (t - t0) mod W in both:
 //   win   the WINDOW: x, y, z of frames t - H .. t + H as fp64, +infinity where the record is missing or outside the array, and
@@ -38,12 +38,10 @@
 // snowmocap_amd/despike.py::despike_joint_track_reference computes.
 #pragma once
 #include <type_traits>
-#include "snowtri_fill.hpp"
+#include "snowtri_record.hpp"
 
 namespace snowtri {
 
-constexpr int kDespikeBlockFrames = 64;   // frames per tile
-constexpr int kDespikeWaves = 4;          // tiles (consecutive in time) per workgroup
 constexpr int kDespikeMaxHalf = 4;        // half_window: 1 .. 4
 
 enum : unsigned char { kDespikeKept = 0, kDespikeSpike = 1, kDespikeMissing = 2, kDespikeUnsupported = 3 };
@@ -100,17 +98,17 @@ __device__ __forceinline__ double despike_median(double (&v)[2 * H + 1], int n) 
 
 // The spike's replacement: (mx + 0.0, my + 0.0, mz + 0.0) rounded once to the I/O type (+ 0.0: a zero median is +0.0 whichever
 // zero the network left in the middle), the record's own score bits.
-__device__ __forceinline__ FillRec<float> despike_replacement(const FillRec<float> &cur, const double med[3]) {
+__device__ __forceinline__ Rec<float> despike_replacement(const Rec<float> &cur, const double med[3]) {
     double v[4] = {med[0] + 0.0, med[1] + 0.0, med[2] + 0.0, 0.0};
-    FillRec<float> r;
-    fill_pack(v, r);
+    Rec<float> r;
+    rec_pack(v, r);
     r.q[0].w = cur.q[0].w;
     return r;
 }
-__device__ __forceinline__ FillRec<double> despike_replacement(const FillRec<double> &cur, const double med[3]) {
+__device__ __forceinline__ Rec<double> despike_replacement(const Rec<double> &cur, const double med[3]) {
     double v[4] = {med[0] + 0.0, med[1] + 0.0, med[2] + 0.0, 0.0};
-    FillRec<double> r;
-    fill_pack(v, r);
+    Rec<double> r;
+    rec_pack(v, r);
     r.q[1].z = cur.q[1].z, r.q[1].w = cur.q[1].w;
     return r;
 }
@@ -122,10 +120,10 @@ struct DespikeWindow {
     unsigned measured;
 
     template <typename IO>
-    __device__ __forceinline__ void enter(int slot, const FillRec<IO> &r) {
+    __device__ __forceinline__ void enter(int slot, const Rec<IO> &r) {
         double v[4];
-        fill_values(r, v);
-        const bool ok = !fill_is_missing(r);
+        rec_values(r, v);
+        const bool ok = !rec_is_missing(r);
         const double inf = __longlong_as_double(0x7ff0000000000000ll);
         x[slot] = ok ? v[0] : inf, y[slot] = ok ? v[1] : inf, z[slot] = ok ? v[2] : inf;
         measured = (measured & ~(1u << slot)) | ((ok ? 1u : 0u) << slot);
@@ -133,33 +131,29 @@ struct DespikeWindow {
 };
 
 template <typename IO, int H>
-__global__ __launch_bounds__(64 * kDespikeWaves, 2) void k_despike(int64_t T, int64_t m, double tol2, int mode, int64_t ncols,
-                                                                const uint4 *__restrict__ in, uint4 *__restrict__ out,
-                                                                unsigned char *__restrict__ codes) {
+__global__ __launch_bounds__(64 * kRecWaves, 2) void k_despike(int64_t T, int64_t m, double tol2, int mode, int64_t ncols,
+                                                               const uint4 *__restrict__ in, uint4 *__restrict__ out,
+                                                               unsigned char *__restrict__ codes) {
     constexpr int W = 2 * H + 1;
     static_assert(H >= 1 && H <= kDespikeMaxHalf, "half_window");
-    const int64_t wg = blockIdx.x;
-    const int64_t row = wg / ncols, col = wg - row * ncols;
-    const int64_t l = col * 64 + threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);   // (one wave per y: the frame loops below are uniform)
-    const int64_t t0 = (row * kDespikeWaves + wave) * kDespikeBlockFrames;
-    if (l >= m || t0 >= T) return;
-    const int64_t t1 = t0 + kDespikeBlockFrames < T ? t0 + kDespikeBlockFrames : T;   // the tile: frames [t0, t1)
-    const int64_t tend = t1 + H < T ? t1 + H : T;                                       // frames read: [max(0, t0 - H), tend)
+    const RecTile own = rec_tile<true>(T, m, ncols);       // (one wave per y, taken as uniform: the frame loops below are uniform)
+    if (own.nothing) return;
+    const int64_t l = own.l, t0 = own.t0, t1 = own.t1;     // the tile: frames [t0, t1)
+    const int64_t tend = t1 + H < T ? t1 + H : T;          // frames read: [max(0, t0 - H), tend)
     SNOWTRI_DEV_CHECK(l >= 0 && t0 >= 0 && t0 < t1 && t1 <= tend && tend <= T && (mode == kDespikeMark || mode == kDespikeReplace), 91);
-    const FillRec<IO> zero = {};   // score 0: missing
+    const Rec<IO> zero = {};   // score 0: missing
 
     // the halo behind the tile and the first W frames from t0 on, all loads issued before the first is looked at
-    FillRec<IO> halo[H], raw[W];
+    Rec<IO> halo[H], raw[W];
     int64_t r = t0 * m + l;        // record index of the centre frame, stepped by m
 #pragma unroll
     for (int k = 0; k < H; k++) {
         const int64_t t = t0 - H + k;
         SNOWTRI_DEV_CHECK(t < 0 || (r - (int64_t)(H - k) * m == t * m + l && t < T), 93);
-        halo[k] = t >= 0 ? fill_load<IO>(in, r - (int64_t)(H - k) * m) : zero;
+        halo[k] = t >= 0 ? rec_load<IO>(in, r - (int64_t)(H - k) * m) : zero;
     }
 #pragma unroll
-    for (int k = 0; k < W; k++) raw[k] = t0 + k < tend ? fill_load<IO>(in, r + (int64_t)k * m) : zero;
+    for (int k = 0; k < W; k++) raw[k] = t0 + k < tend ? rec_load<IO>(in, r + (int64_t)k * m) : zero;
     DespikeWindow<W> win;
     win.measured = 0;
 #pragma unroll
@@ -174,10 +168,10 @@ __global__ __launch_bounds__(64 * kDespikeWaves, 2) void k_despike(int64_t T, in
             const int64_t t = tc + i;
             if (decltype(guarded)::value && t >= t1) break;
             // the centre leaves the raw ring, frame t + W takes its slot; frame t + H enters the window
-            const FillRec<IO> cur = raw[i];
+            const Rec<IO> cur = raw[i];
             if (!decltype(guarded)::value || t + W < tend) {
                 SNOWTRI_DEV_CHECK(r + ahead == (t + W) * m + l && t + W < tend, 92);
-                raw[i] = fill_load<IO>(in, r + ahead);
+                raw[i] = rec_load<IO>(in, r + ahead);
             } else {
                 raw[i] = zero;
             }
@@ -204,9 +198,9 @@ __global__ __launch_bounds__(64 * kDespikeWaves, 2) void k_despike(int64_t T, in
                 d2 = s + zz;
             }
             const bool spike = meas && n >= 3 && d2 > tol2;   // (false for a NaN d2)
-            const FillRec<IO> rep = fill_select<IO>(mode == kDespikeReplace, despike_replacement(cur, med), zero);
+            const Rec<IO> rep = rec_select<IO>(mode == kDespikeReplace, despike_replacement(cur, med), zero);
             SNOWTRI_DEV_CHECK(r == t * m + l && t >= t0 && t < t1 && l < m, 90);
-            fill_store<IO>(out, r, fill_select<IO>(spike, rep, cur));
+            rec_store<IO>(out, r, rec_select<IO>(spike, rep, cur));
             if (codes) codes[r] = !meas ? kDespikeMissing : spike ? kDespikeSpike : n >= 3 ? kDespikeKept : kDespikeUnsupported;
             r += m;
         }

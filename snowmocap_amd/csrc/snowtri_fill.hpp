@@ -7,7 +7,7 @@
 // (code 2), everything else is copied bit for bit (code 0 measured, code 3 missing and left alone).
 //
 // One thread per lane l < m, consecutive threads on consecutive lanes: a wave reads 64 adjacent 16- or 32-byte records of one
-// frame with 16-byte loads.  A wave owns a TILE of 64 lanes x kFillBlockFrames frames (four tiles, consecutive in time, per
+// frame with 16-byte loads.  A wave owns a TILE of 64 lanes x kRecBlockFrames frames (four tiles, consecutive in time, per
 // workgroup) and writes exactly the records of its tile:
 //   1. BACKWARDS from the frame before the tile for the nearest measured record A, at most max_gap frames or down to frame 0
 //      (one record when the frame before the tile is measured);
@@ -19,7 +19,7 @@
 //      copied from the input again (at most max_gap re-reads per run), later frames of it are copied as they come;
 //   3. a run still open at the end of the tile is followed FORWARD, at most until it outgrows max_gap or the track ends.
 // No LDS, no communication between workgroups, no atomics; the result does not depend on the tile length.  On tracks with few
-// dropouts the halo is one extra record per lane and tile: 1 + 1 / kFillBlockFrames reads and 1 write per record from HBM
+// dropouts the halo is one extra record per lane and tile: 1 + 1 / kRecBlockFrames reads and 1 write per record from HBM
 // (not counted: the re-reads of a run that was given up and the look into a neighbouring tile from a run at the edge, both
 // of records some wave has just read).
 //
@@ -29,79 +29,22 @@
 // snowmocap_amd/fill.py::fill_joint_track_reference computes.
 #pragma once
 #include <type_traits>
-#include "snowtri_math.hpp"
+#include "snowtri_record.hpp"
 
 namespace snowtri {
 
-constexpr int kFillBlockFrames = 64;   // frames per tile
 constexpr int kFillAhead = 4;          // records a thread has in flight inside its tile
-constexpr int kFillWaves = 4;          // tiles (consecutive in time) per workgroup
 constexpr int kFillMaxGap = 255;
 
 enum : unsigned char { kFillMeasured = 0, kFillLerp = 1, kFillHold = 2, kFillMissing = 3 };
 
-// One record as the bits it is stored as: 16 bytes (float) or 32 bytes (double).
-template <typename IO>
-struct FillRec {
-    static constexpr int NQ = (int)sizeof(IO) / 4;   // 16-byte words per record
-    uint4 q[NQ];
-};
-
-template <typename IO>
-__device__ __forceinline__ FillRec<IO> fill_load(const uint4 *__restrict__ base, int64_t rec) {
-    FillRec<IO> r;
-#pragma unroll
-    for (int i = 0; i < FillRec<IO>::NQ; i++) r.q[i] = base[rec * FillRec<IO>::NQ + i];
-    return r;
-}
-
-template <typename IO>
-__device__ __forceinline__ void fill_store(uint4 *__restrict__ base, int64_t rec, const FillRec<IO> &r) {
-#pragma unroll
-    for (int i = 0; i < FillRec<IO>::NQ; i++) base[rec * FillRec<IO>::NQ + i] = r.q[i];
-}
-
-__device__ __forceinline__ void fill_values(const FillRec<float> &r, double v[4]) {
-    v[0] = (double)__uint_as_float(r.q[0].x), v[1] = (double)__uint_as_float(r.q[0].y);
-    v[2] = (double)__uint_as_float(r.q[0].z), v[3] = (double)__uint_as_float(r.q[0].w);
-}
-__device__ __forceinline__ void fill_values(const FillRec<double> &r, double v[4]) {
-    v[0] = __hiloint2double((int)r.q[0].y, (int)r.q[0].x), v[1] = __hiloint2double((int)r.q[0].w, (int)r.q[0].z);
-    v[2] = __hiloint2double((int)r.q[1].y, (int)r.q[1].x), v[3] = __hiloint2double((int)r.q[1].w, (int)r.q[1].z);
-}
-__device__ __forceinline__ void fill_pack(const double v[4], FillRec<float> &r) {
-    r.q[0] = make_uint4(__float_as_uint((float)v[0]), __float_as_uint((float)v[1]), __float_as_uint((float)v[2]), __float_as_uint((float)v[3]));
-}
-__device__ __forceinline__ void fill_pack(const double v[4], FillRec<double> &r) {
-    r.q[0] = make_uint4((unsigned)__double2loint(v[0]), (unsigned)__double2hiint(v[0]), (unsigned)__double2loint(v[1]), (unsigned)__double2hiint(v[1]));
-    r.q[1] = make_uint4((unsigned)__double2loint(v[2]), (unsigned)__double2hiint(v[2]), (unsigned)__double2loint(v[3]), (unsigned)__double2hiint(v[3]));
-}
-
-// a ? x : y word by word (a conditional between two records as objects would send both through memory)
-template <typename IO>
-__device__ __forceinline__ FillRec<IO> fill_select(bool a, const FillRec<IO> &x, const FillRec<IO> &y) {
-    FillRec<IO> r;
-#pragma unroll
-    for (int i = 0; i < FillRec<IO>::NQ; i++)
-        r.q[i] = make_uint4(a ? x.q[i].x : y.q[i].x, a ? x.q[i].y : y.q[i].y, a ? x.q[i].z : y.q[i].z, a ? x.q[i].w : y.q[i].w);
-    return r;
-}
-
-// score == 0 (so -0.0 too) or any of the four values not finite
-template <typename IO>
-__device__ __forceinline__ bool fill_is_missing(const FillRec<IO> &r) {
-    double v[4];
-    fill_values(r, v);
-    return v[3] == 0.0 || !(isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]));
-}
-
 // record k of the g missing ones between A and B, k = 1 .. g
 template <typename IO>
-__device__ __forceinline__ FillRec<IO> fill_lerp(const FillRec<IO> &A, const FillRec<IO> &B, int k, int g) {
+__device__ __forceinline__ Rec<IO> fill_lerp(const Rec<IO> &A, const Rec<IO> &B, int k, int g) {
 #pragma clang fp contract(off)   // every operation rounded separately: the bits NumPy computes
     double a[4], b[4], v[4];
-    fill_values(A, a);
-    fill_values(B, b);
+    rec_values(A, a);
+    rec_values(B, b);
     const double w = (double)k / (double)(g + 1);
 #pragma unroll
     for (int c = 0; c < 4; c++) {
@@ -109,8 +52,8 @@ __device__ __forceinline__ FillRec<IO> fill_lerp(const FillRec<IO> &A, const Fil
         const double p = w * d;
         v[c] = a[c] + p;
     }
-    FillRec<IO> r;
-    fill_pack(v, r);
+    Rec<IO> r;
+    rec_pack(v, r);
     return r;
 }
 
@@ -123,54 +66,51 @@ struct FillTile {
     unsigned char *__restrict__ fill;
 
     __device__ __forceinline__ int64_t rec(int64_t t) const { return t * m + l; }
-    __device__ __forceinline__ void put_at(int64_t rec_index, const FillRec<IO> &r, unsigned char code) const {
-        fill_store<IO>(out, rec_index, r);
+    __device__ __forceinline__ void put_at(int64_t rec_index, const Rec<IO> &r, unsigned char code) const {
+        rec_store<IO>(out, rec_index, r);
         if (fill) fill[rec_index] = code;
     }
-    __device__ __forceinline__ void put(int64_t t, const FillRec<IO> &r, unsigned char code) const {
+    __device__ __forceinline__ void put(int64_t t, const Rec<IO> &r, unsigned char code) const {
         SNOWTRI_DEV_CHECK(t >= t0 && t < t1 && l >= 0 && l < m, 80);
         put_at(rec(t), r, code);
     }
     // The run of `run` missing records in front of frame `end` is decided: A (if has_a) is the measured record before it, B (if
     // has_b) the one at `end`.  Writes the frames of the run that lie in the tile.
-    __device__ __forceinline__ void resolve(int64_t end, int run, bool has_a, const FillRec<IO> &A, bool has_b, const FillRec<IO> &B) const {
+    __device__ __forceinline__ void resolve(int64_t end, int run, bool has_a, const Rec<IO> &A, bool has_b, const Rec<IO> &B) const {
         const int64_t first = end - run;   // first frame of the run; A sits at first - 1
         const int64_t lo = first > t0 ? first : t0, hi = end < t1 ? end : t1;
         const bool fits = run <= max_gap;
-        const FillRec<IO> H = fill_select<IO>(has_a, A, B);
+        const Rec<IO> H = rec_select<IO>(has_a, A, B);
         for (int64_t t = lo; t < hi; t++) {
             if (fits && has_a && has_b)
                 put(t, fill_lerp<IO>(A, B, (int)(t - first) + 1, run), kFillLerp);
             else if (fits && (has_a || has_b))
                 put(t, H, kFillHold);
             else
-                put(t, fill_load<IO>(in, rec(t)), kFillMissing);
+                put(t, rec_load<IO>(in, rec(t)), kFillMissing);
         }
     }
 };
 
 template <typename IO>
-__global__ __launch_bounds__(64 * kFillWaves) void k_fill_gaps(int64_t T, int64_t m, int max_gap, int64_t ncols, const uint4 *__restrict__ in,
-                                                               uint4 *__restrict__ out, unsigned char *__restrict__ fill) {
-    const int64_t wg = blockIdx.x;
-    const int64_t row = wg / ncols, col = wg - row * ncols;
+__global__ __launch_bounds__(64 * kRecWaves) void k_fill_gaps(int64_t T, int64_t m, int max_gap, int64_t ncols, const uint4 *__restrict__ in,
+                                                              uint4 *__restrict__ out, unsigned char *__restrict__ fill) {
+    const RecTile own = rec_tile<false>(T, m, ncols);
+    if (own.nothing) return;
     FillTile<IO> tile;
-    tile.m = m, tile.l = col * 64 + threadIdx.x;
-    tile.t0 = (row * kFillWaves + threadIdx.y) * kFillBlockFrames;
-    if (tile.l >= m || tile.t0 >= T) return;
-    tile.t1 = tile.t0 + kFillBlockFrames < T ? tile.t0 + kFillBlockFrames : T;
+    tile.m = m, tile.l = own.l, tile.t0 = own.t0, tile.t1 = own.t1;
     tile.max_gap = max_gap, tile.in = in, tile.out = out, tile.fill = fill;
     const int64_t t0 = tile.t0, t1 = tile.t1;
     SNOWTRI_DEV_CHECK(max_gap >= 1 && max_gap <= kFillMaxGap && t0 >= 0 && t1 <= T, 81);
 
     // 1. the nearest measured record behind the tile.  None within max_gap frames: the run that enters the tile is as long as
     // the frames looked at, which is either the whole track so far (t0 <= max_gap) or already max_gap, one short of given up.
-    FillRec<IO> A = {};
+    Rec<IO> A = {};
     bool has_a = false;
     int run = 0;   // missing records directly in front of the current frame, saturating at max_gap + 1 (= given up)
     for (int64_t t = t0 - 1; t >= 0 && run < max_gap; t--) {
-        A = fill_load<IO>(in, tile.rec(t));
-        if (!fill_is_missing(A)) {
+        A = rec_load<IO>(in, tile.rec(t));
+        if (!rec_is_missing(A)) {
             has_a = true;
             break;
         }
@@ -183,24 +123,24 @@ __global__ __launch_bounds__(64 * kFillWaves) void k_fill_gaps(int64_t T, int64_
     // unconditional: a load behind a branch would leave the compiler no count of the loads in flight to wait on, and it
     // would wait for all of them.  The last one or two trips (refills past the tile's end are skipped, a clipped tile ends
     // inside a trip) run guarded.  r = record index of frame t, stepped by m.
-    FillRec<IO> q[kFillAhead] = {};
+    Rec<IO> q[kFillAhead] = {};
     int64_t r = tile.rec(t0);
     const int64_t ahead = (int64_t)kFillAhead * m;
 #pragma unroll
     for (int i = 0; i < kFillAhead; i++)
-        if (t0 + i < t1) q[i] = fill_load<IO>(in, r + i * m);
+        if (t0 + i < t1) q[i] = rec_load<IO>(in, r + i * m);
     auto trip = [&](const int64_t tc, auto guarded) {
 #pragma unroll
         for (int i = 0; i < kFillAhead; i++) {
             const int64_t t = tc + i;
             if (decltype(guarded)::value && t >= t1) break;
-            const FillRec<IO> cur = q[i];
+            const Rec<IO> cur = q[i];
             if (!decltype(guarded)::value || t + kFillAhead < t1) {
                 SNOWTRI_DEV_CHECK(r + ahead == tile.rec(t + kFillAhead) && t + kFillAhead < t1, 82);
-                q[i] = fill_load<IO>(in, r + ahead);
+                q[i] = rec_load<IO>(in, r + ahead);
             }
             SNOWTRI_DEV_CHECK(r == tile.rec(t) && t >= t0 && t < t1, 80);
-            if (!fill_is_missing(cur)) {
+            if (!rec_is_missing(cur)) {
                 tile.put_at(r, cur, kFillMeasured);
                 if (run > 0 && run <= max_gap) tile.resolve(t, run, has_a, A, true, cur);
                 A = cur, has_a = true, run = 0;
@@ -220,12 +160,12 @@ __global__ __launch_bounds__(64 * kFillWaves) void k_fill_gaps(int64_t T, int64_
 
     // 3. a run that leaves the tile undecided
     if (run > 0 && run <= max_gap) {
-        FillRec<IO> B = {};
+        Rec<IO> B = {};
         bool has_b = false;
         int64_t t = t1;
         for (; t < T && run <= max_gap; t++) {
-            B = fill_load<IO>(in, tile.rec(t));
-            if (!fill_is_missing(B)) {
+            B = rec_load<IO>(in, tile.rec(t));
+            if (!rec_is_missing(B)) {
                 has_b = true;
                 break;
             }

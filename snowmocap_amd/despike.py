@@ -4,7 +4,7 @@ A joint that was SEEN in the wrong place for a frame or two -- a flipped limb, a
 record: the gap filler leaves it alone and the second-order filter rings on it.  The rule (include/snowtri.h, "Despiking") on
 xyzs[T][m][4] = (x, y, z, score), every lane on its own, all decisions in fp64:
 
-  1. a record is MISSING if its score == 0 (so -0.0 too) or any of its four values is not finite, else MEASURED (fill.py's rule);
+  1. a record is MISSING if its score == 0 (so -0.0 too) or any of its four values is not finite, else MEASURED (records.py);
   2. the window of record (t, l): the n measured records of lane l at frames max(0, t - h) .. min(T - 1, t + h), itself included;
   3. per coordinate med = (v[(n - 1) // 2] + v[n // 2]) * 0.5 of the n values sorted ascending;
   4. d = value - med, d2 = (dx * dx + dy * dy) + dz * dz, every operation rounded separately;
@@ -24,13 +24,11 @@ with holes sits off-centre and clean records next to dropouts are flagged (about
 """
 from __future__ import annotations
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
 from ._lib import (DESPIKE_KEPT, DESPIKE_MARK, DESPIKE_MISSING, DESPIKE_REPLACE, DESPIKE_SPIKE, DESPIKE_UNSUPPORTED)  # noqa: F401
-from .fill import _check_shape, missing_records
+from .records import as_records, missing_records, run_record_pass
 
 MAX_HALF_WINDOW = 4            # half_window: 1 .. 4
 
@@ -66,14 +64,8 @@ def despike_args(despike):
 def despike_joint_track_reference(xyzs, half_window, tol, mode=DESPIKE_MARK):
     """xyzs [T, ..., 4] (float32 / float64; the axes between the first and the last are the lanes) -> (out, codes): out of the same
     shape and dtype, codes uint8 of shape xyzs.shape[:-1].  Pure NumPy."""
-    xyzs = np.asarray(xyzs)
-    if xyzs.dtype != np.float32:
-        xyzs = xyzs.astype(np.float64, copy=False)
     h, tol, mode = _check_args(half_window, tol, mode)
-    _check_shape(xyzs.shape)
-    T = xyzs.shape[0]
-    m = int(np.prod(xyzs.shape[1:-1], dtype=np.int64))
-    x = np.ascontiguousarray(xyzs).reshape(T, m, 4)
+    xyzs, x, T, m = as_records(xyzs)
     out = x.copy()
     codes = np.zeros((T, m), dtype=np.uint8)
     if T == 0 or m == 0:
@@ -112,39 +104,5 @@ def despike_joint_track(ctx, xyzs, half_window=3, tol=0.1, mode=DESPIKE_MARK, co
     float32 or float64: a CUDA(=HIP) tensor is used in place, asynchronously on `stream` (default: torch's current stream), and
     tensors come back; anything else is taken as a NumPy array, staged and synchronous.  Returns (out, codes) with codes
     uint8 of shape xyzs.shape[:-1], or None with codes=False (the kernel then does not write them)."""
-    half_window, tol, mode = _check_args(half_window, tol, mode)
-    if ctx is None:
-        ctx = _lib.scratch_context()
-    L, h = ctx.L, ctx.handle
-    if hasattr(xyzs, "is_cuda"):
-        import torch
-        if xyzs.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"snowtri supports float32/float64 joints, not {xyzs.dtype}")
-        _check_shape(xyzs.shape)
-        if not xyzs.is_cuda or not xyzs.is_contiguous():
-            raise ValueError("a tensor given to despike_joint_track must be a contiguous CUDA tensor (NumPy arrays are staged from the host)")
-        code = _lib.F32 if xyzs.dtype == torch.float32 else _lib.F64
-        T = int(xyzs.shape[0])
-        m = int(xyzs.numel() // (4 * T)) if T else 0
-        out = torch.empty_like(xyzs)
-        cd = torch.empty(xyzs.shape[:-1], dtype=torch.uint8, device=xyzs.device) if codes else None
-        if stream is None:
-            stream = torch.cuda.current_stream(xyzs.device).cuda_stream
-        args = (ct.c_void_p(xyzs.data_ptr()), code, half_window, tol, mode, ct.c_void_p(out.data_ptr()),
-                ct.c_void_p(cd.data_ptr()) if codes else None, _lib.DEVICE, ct.c_void_p(stream) if stream else None)
-    else:
-        xyzs = np.asarray(xyzs)
-        if xyzs.dtype != np.float32:
-            xyzs = xyzs.astype(np.float64, copy=False)
-        xyzs = np.ascontiguousarray(xyzs)
-        _check_shape(xyzs.shape)
-        T = int(xyzs.shape[0])
-        m = int(xyzs.size // (4 * T)) if T else 0
-        out = np.empty_like(xyzs)
-        cd = np.empty(xyzs.shape[:-1], dtype=np.uint8) if codes else None
-        args = (_lib.ptr(xyzs), _lib.dtype_code(xyzs.dtype), half_window, tol, mode, _lib.ptr(out), _lib.ptr(cd), _lib.HOST, None)
-    rc = L.snowtri_despike_joint_track(h, T, m, *args)
-    if rc == _lib.ERR_BAD_ARG:
-        raise ValueError(f"snowtri_despike_joint_track: {L.snowtri_last_error().decode()}")
-    _lib.check(rc, "snowtri_despike_joint_track")
-    return out, cd
+    return run_record_pass(ctx, xyzs, "snowtri_despike_joint_track", _check_args(half_window, tol, mode), codes, stream,
+                           "despike_joint_track")

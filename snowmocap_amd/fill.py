@@ -17,11 +17,10 @@ bit for bit.  `fill_joint_track` runs the HIP kernel (snowtri_fill_joint_track).
 """
 from __future__ import annotations
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
+from .records import as_records, missing_records, run_record_pass  # noqa: F401  (missing_records: rule 1, importable from here)
 
 FILL_MEASURED, FILL_LERP, FILL_HOLD, FILL_MISSING = 0, 1, 2, 3
 MAX_GAP = 255                  # max_gap: 1 .. 255
@@ -38,28 +37,11 @@ def _check_max_gap(max_gap):
     return int(max_gap)
 
 
-def _check_shape(shape):
-    if len(shape) < 2 or shape[-1] != 4:
-        raise ValueError(f"xyzs must be [T, ..., 4] records (got shape {tuple(shape)})")
-
-
-def missing_records(xyzs):
-    """[..., 4] records -> bool [...]: rule 1 (score == 0, or a value that is not finite)."""
-    v = np.asarray(xyzs).astype(np.float64)
-    return (v[..., 3] == 0) | ~np.isfinite(v).all(axis=-1)
-
-
 def fill_joint_track_reference(xyzs, max_gap):
     """xyzs [T, ..., 4] (float32 / float64; the axes between the first and the last are the lanes) -> (out, codes): out of
     the same shape and dtype, codes uint8 of shape xyzs.shape[:-1].  Pure NumPy."""
-    xyzs = np.asarray(xyzs)
-    if xyzs.dtype != np.float32:
-        xyzs = xyzs.astype(np.float64, copy=False)
     max_gap = _check_max_gap(max_gap)
-    _check_shape(xyzs.shape)
-    T = xyzs.shape[0]
-    m = int(np.prod(xyzs.shape[1:-1], dtype=np.int64))
-    x = np.ascontiguousarray(xyzs).reshape(T, m, 4)
+    xyzs, x, T, m = as_records(xyzs)
     out = x.copy()
     codes = np.zeros((T, m), dtype=np.uint8)
     if T == 0 or m == 0:
@@ -94,39 +76,4 @@ def fill_joint_track(ctx, xyzs, max_gap, codes=True, stream=None):
     float32 or float64: a CUDA(=HIP) tensor is used in place, asynchronously on `stream` (default: torch's current stream), and
     tensors come back; anything else is taken as a NumPy array, staged and synchronous.  Returns (out, codes) with codes
     uint8 of shape xyzs.shape[:-1], or None with codes=False (the kernel then does not write them)."""
-    max_gap = _check_max_gap(max_gap)
-    if ctx is None:
-        ctx = _lib.scratch_context()
-    L, h = ctx.L, ctx.handle
-    if hasattr(xyzs, "is_cuda"):
-        import torch
-        if xyzs.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"snowtri supports float32/float64 joints, not {xyzs.dtype}")
-        _check_shape(xyzs.shape)
-        if not xyzs.is_cuda or not xyzs.is_contiguous():
-            raise ValueError("a tensor given to fill_joint_track must be a contiguous CUDA tensor (NumPy arrays are staged from the host)")
-        code = _lib.F32 if xyzs.dtype == torch.float32 else _lib.F64
-        T = int(xyzs.shape[0])
-        m = int(xyzs.numel() // (4 * T)) if T else 0
-        out = torch.empty_like(xyzs)
-        fl = torch.empty(xyzs.shape[:-1], dtype=torch.uint8, device=xyzs.device) if codes else None
-        if stream is None:
-            stream = torch.cuda.current_stream(xyzs.device).cuda_stream
-        args = (ct.c_void_p(xyzs.data_ptr()), code, max_gap, ct.c_void_p(out.data_ptr()),
-                ct.c_void_p(fl.data_ptr()) if codes else None, _lib.DEVICE, ct.c_void_p(stream) if stream else None)
-    else:
-        xyzs = np.asarray(xyzs)
-        if xyzs.dtype != np.float32:
-            xyzs = xyzs.astype(np.float64, copy=False)
-        xyzs = np.ascontiguousarray(xyzs)
-        _check_shape(xyzs.shape)
-        T = int(xyzs.shape[0])
-        m = int(xyzs.size // (4 * T)) if T else 0
-        out = np.empty_like(xyzs)
-        fl = np.empty(xyzs.shape[:-1], dtype=np.uint8) if codes else None
-        args = (_lib.ptr(xyzs), _lib.dtype_code(xyzs.dtype), max_gap, _lib.ptr(out), _lib.ptr(fl), _lib.HOST, None)
-    rc = L.snowtri_fill_joint_track(h, T, m, *args)
-    if rc == _lib.ERR_BAD_ARG:
-        raise ValueError(f"snowtri_fill_joint_track: {L.snowtri_last_error().decode()}")
-    _lib.check(rc, "snowtri_fill_joint_track")
-    return out, fl
+    return run_record_pass(ctx, xyzs, "snowtri_fill_joint_track", (_check_max_gap(max_gap),), codes, stream, "fill_joint_track")

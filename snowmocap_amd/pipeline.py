@@ -145,14 +145,17 @@ class TrackPipeline:
             val[idx, i] = vi[:, 0]
             pts_s[idx, i] = qi[:, 0]
 
+        def missing(x):
+            """records.missing_records on a tensor"""
+            return (x[..., 3] == 0) | ~torch.isfinite(x).all(dim=-1)
+
         def unfilled(x):
             """(xyzs_filled, fill) before any sequence has been filled: the records as they are, measured or missing"""
-            return x.clone(), ((x[..., 3] == 0) | ~torch.isfinite(x).all(dim=-1)).to(torch.uint8) * FILL_MISSING
+            return x.clone(), missing(x).to(torch.uint8) * FILL_MISSING
 
         def undespiked(x):
             """(xyzs_despiked, spike_codes) before any sequence has been despiked: the records as they are, missing or untested"""
-            miss = (x[..., 3] == 0) | ~torch.isfinite(x).all(dim=-1)
-            return x.clone(), torch.where(miss, DESPIKE_MISSING, DESPIKE_UNSUPPORTED).to(torch.uint8)
+            return x.clone(), torch.where(missing(x), DESPIKE_MISSING, DESPIKE_UNSUPPORTED).to(torch.uint8)
 
         if ragged == "track":
             from .tracking import PersonTracker, bridge_track_ids

@@ -6,7 +6,8 @@
  *     SNOWTRI_ERR_NO_DEVICE;
  *   - with a GPU (tests/test_gpu_parity.py runs it against libsnowtri.so): the same plus, on a real context,
  *     wrong shapes / dtype codes / memory spaces / method, center_point_index and keypoint_num out of range,
- *     missing required pointers, a camera index out of range, too few Blender joints, a singular K.
+ *     missing required pointers, a camera index out of range, too few Blender joints, a singular K, and every refusal of
+ *     the two record passes (gap filling, despiking) that comes before a launch.
  * Exit code = number of failed expectations; prints each failure.
  */
 #include <stdint.h>
@@ -121,6 +122,15 @@ int main(void) {
         EXPECT(snowtri_candidates_token(NULL), 0);
         EXPECT(snowtri_condense_resident(NULL, 1, &prm, 1, buf, buf, buf, ibuf, ubuf), SNOWTRI_ERR_BAD_ARG);
     }
+    EXPECT(snowtri_triangulate_robust(NULL, 1, 5, fbuf, SNOWTRI_F32, NULL, &prm, 10.0, 1, 1, fbuf, fbuf, SNOWTRI_F32, ibuf, ubuf, ubuf, fbuf,
+                                      SNOWTRI_HOST, NULL),
+           SNOWTRI_ERR_BAD_ARG);
+    EXPECT(snowtri_track_persons(NULL, 1, 1, 5, fbuf, SNOWTRI_F32, ibuf, 1, 0, 0.5, 0, buf, ibuf, ibuf, ibuf, ubuf, SNOWTRI_HOST, NULL),
+           SNOWTRI_ERR_BAD_ARG);
+    EXPECT(snowtri_track_gather(NULL, 1, 1, 5, fbuf, SNOWTRI_F32, 1, ibuf, fbuf + 64, SNOWTRI_HOST, NULL), SNOWTRI_ERR_BAD_ARG);
+    EXPECT(snowtri_fill_joint_track(NULL, 4, 3, fbuf, SNOWTRI_F32, 5, fbuf + 64, bbuf, SNOWTRI_HOST, NULL), SNOWTRI_ERR_BAD_ARG);
+    EXPECT(snowtri_despike_joint_track(NULL, 4, 3, fbuf, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, fbuf + 64, bbuf, SNOWTRI_HOST, NULL),
+           SNOWTRI_ERR_BAD_ARG);
 
     /* ---- context creation with bad arguments -------------------------------------------------------------- */
     {
@@ -230,6 +240,40 @@ int main(void) {
             EXPECT(snowtri_condense_resident(ctx, 0, &prm, 1, buf, buf, buf, ibuf, ubuf), SNOWTRI_ERR_BAD_ARG);       /* no candidates resident */
             EXPECT(snowtri_condense_resident(ctx, 123456789, &prm, 1, buf, buf, buf, ibuf, ubuf), SNOWTRI_ERR_BAD_ARG); /* a stale token */
             EXPECT(snowtri_ctx_overrides(ctx) != NULL, 1);
+        }
+        {   /* the two record passes (gap filling, despiking): every refusal comes before anything is enqueued or written */
+            float *in = fbuf, *out = fbuf + 64;   /* [4][3][4] float32 records each, 16-byte aligned, apart */
+            volatile double zero = 0.0;
+            const double nan = zero / zero;
+#define FILL(T_, m_, x_, dt_, gap_, o_, ms_) snowtri_fill_joint_track(ctx, T_, m_, x_, dt_, gap_, o_, bbuf, ms_, NULL)
+#define DESPIKE(T_, m_, x_, dt_, h_, tol_, mode_, o_, ms_) snowtri_despike_joint_track(ctx, T_, m_, x_, dt_, h_, tol_, mode_, o_, bbuf, ms_, NULL)
+            EXPECT(FILL(4, 3, in, 7, 5, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(4, 3, in, SNOWTRI_F32, 5, out, 5), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(-1, 3, in, SNOWTRI_F32, 5, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(4, -1, in, SNOWTRI_F32, 5, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(4, 3, NULL, SNOWTRI_F32, 5, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(4, 3, in, SNOWTRI_F32, 5, NULL, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(4, 3, in, SNOWTRI_F32, 5, in, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);          /* out == xyzs */
+            EXPECT(FILL(4, 3, in, SNOWTRI_F32, 0, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(4, 3, in, SNOWTRI_F32, 256, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(FILL(0, 3, in, SNOWTRI_F32, 0, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);         /* a bad max_gap even on an empty track */
+            EXPECT(FILL(0, 3, NULL, SNOWTRI_F32, 5, NULL, SNOWTRI_HOST), SNOWTRI_OK);               /* empty track: no pointer is looked at */
+            EXPECT(DESPIKE(4, 3, in, 7, 3, 0.1, SNOWTRI_DESPIKE_MARK, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, 3, in, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, out, 5), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(-1, 3, in, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, -1, in, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, 3, NULL, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, 3, in, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, NULL, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, 3, in, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, in, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);   /* out == xyzs */
+            EXPECT(DESPIKE(4, 3, in, SNOWTRI_F32, 0, 0.1, SNOWTRI_DESPIKE_MARK, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, 3, in, SNOWTRI_F32, 5, 0.1, SNOWTRI_DESPIKE_MARK, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, 3, in, SNOWTRI_F32, 3, nan, SNOWTRI_DESPIKE_MARK, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(4, 3, in, SNOWTRI_F32, 3, 0.1, 2, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);
+            EXPECT(DESPIKE(0, 3, in, SNOWTRI_F32, 3, 0.1, 2, out, SNOWTRI_HOST), SNOWTRI_ERR_BAD_ARG);   /* a bad mode even on an empty track */
+            EXPECT(DESPIKE(0, 3, NULL, SNOWTRI_F32, 3, 0.1, SNOWTRI_DESPIKE_MARK, NULL, SNOWTRI_HOST), SNOWTRI_OK);
+#undef FILL
+#undef DESPIKE
+            EXPECT(out[0] == 0.0f && bbuf[0] == 0, 1);   /* nothing was written */
         }
         EXPECT(snowtri_ctx_destroy(ctx), SNOWTRI_OK);
     }
