@@ -283,7 +283,8 @@ class Context:
 
     def undistort_keypoints(self, kpts):
         """Raw-image keypoints kpts[F, C, Pmax, J, 3] -> the same array with (u, v) moved to the undistorted
-        image (scores untouched); host arrays, float32 or float64."""
+        image (scores untouched); host arrays, float32 or float64.  A pixel's result depends on that pixel and its camera's
+        lens only (not on the batch around it); a non-finite u or v gives a non-finite u and v."""
         a = np.asarray(kpts)
         if a.dtype != np.float32:
             a = a.astype(np.float64, copy=False)

@@ -6,7 +6,8 @@
 //   rho = 1 + k1 r2 + k2 r2^2 + k3 r2^3,  r2 = x^2 + y^2  (normalised coordinates).
 // cv2.undistort paints output pixel p_u from input pixel K.distort(K^-1 p_u), so a raw-image keypoint p_d maps
 // to p_u = K.undistort(K^-1 p_d): the exact inverse, here by Newton on the 2x2 system (symmetric Jacobian),
-// iterated until every lane of the wave has converged (NaN inputs stop at the bound).
+// each lane iterated until its own step is below 1e-8 and frozen there, the loop left once every lane of the wave has
+// converged (NaN inputs stop at the bound): a pixel's bits depend on its own input only.
 // Three to five iterations from x = x_d reach 5e-13 px on the shipped rig (55 px of distortion at the corners);
 // OpenCV's own undistortPoints default (5 fixed-point sweeps) stops 0.15 px short of that point.
 // One lane per observation, (u, v) rewritten and the score copied: 24 B of traffic for ~300 flop --
@@ -31,6 +32,7 @@ __device__ __forceinline__ void undistort_pixel(const Lens &q, double u, double 
     const double yd = (v - q.cy) * q.ify;
     const double xd = (u - q.cx - q.s * yd) * q.ifx;
     double x = xd, y = yd;
+    bool done = false;
 #pragma unroll 1
     for (int it = 0; it < kUndistortIters; it++) {
         const double r2 = fma(x, x, y * y);
@@ -42,13 +44,19 @@ __device__ __forceinline__ void undistort_pixel(const Lens &q, double u, double 
         const double a = fma(2.0 * x * x, drho, rho) + fma(2.0 * q.p1, y, 6.0 * q.p2 * x);
         const double b = fma(xy2, drho, 2.0 * fma(q.p1, x, q.p2 * y));
         const double d = fma(2.0 * y * y, drho, rho) + fma(6.0 * q.p1, y, 2.0 * q.p2 * x);
-        const double idet = rcp_nr2(fma(a, d, -b * b));
+        // A lane applies steps until ITS OWN step is below 1e-8 (normalised units; Newton converges quadratically, so that
+        // step leaves an error of ~1e-16), that one included, and is frozen from then on: what it returns depends on its own
+        // pixel only, never on which lanes share its wave.  (A further step would be rounding noise that flips the last bit.)
+        // Frozen = its step is made an exact zero through 1 / det (one select instead of one per coordinate; a converged
+        // lane's numerators are finite, so 0 * them is 0 and x - 0 is x), which also keeps `done` set.
+        const double idet = done ? 0.0 : rcp_nr2(fma(a, d, -b * b));
         const double dx = (d * f1 - b * f2) * idet, dy = (a * f2 - b * f1) * idet;
         x -= dx;
         y -= dy;
-        // Newton converges quadratically: a step below 1e-8 (normalised units) leaves an error of ~1e-16.
-        // Wave-uniform exit: the joints of one detection sit close together and need the same step count.
-        if (__all(fmax(fabs(dx), fabs(dy)) < 1e-8)) break;
+        done = fmax(fabs(dx), fabs(dy)) < 1e-8;
+        // The exit stays wave-uniform and only decides when the loop ends: the joints of one detection sit close together
+        // and need the same step count.  A NaN lane never sets `done` and holds its wave to the bound.
+        if (__all(done)) break;
     }
     uo = fma(q.fx, x, fma(q.s, y, q.cx));
     vo = fma(q.fy, y, q.cy);
