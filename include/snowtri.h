@@ -543,6 +543,53 @@ int snowtri_ctx_set_distortion(snowtri_ctx *ctx, const double *D);
 int snowtri_undistort_keypoints(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void *kpts_in,
                                 void *kpts_out, int dtype, int memspace, void *stream);
 
+/* Reprojection: 3D joint records back into the cameras' images, and what each camera's detections cost against them (no reference
+ * counterpart; the direction opposite to triangulation and to snowtri_undistort_keypoints).  How well does camera c agree with a
+ * result, which of its detections belongs to 3D person p, where is the skeleton drawn on the frame.  The rule, in fp64, per camera c,
+ * frame f, person p and joint j < kn, with K, R, t as given to snowtri_ctx_create and the record (X, score) = xyzs[f][p][j] of
+ * xyz_dtype converted to fp64:
+ *   1. d = X - t_c, pc = R_c^T d, x = pc0 / pc2, y = pc1 / pc2.
+ *   2. With SNOWTRI_REPROJECT_RAW in `flags`: (x, y) goes through the forward lens model (x_d, y_d of the header of
+ *      snowmocap_amd/csrc/snowtri_undistort.hpp) with the D of snowtri_ctx_set_distortion -- the pixel on the RAW frame, the exact
+ *      opposite of snowtri_undistort_keypoints.
+ *   3. u = fx x + s y + cx, v = fy y + cy.
+ *   4. The projection is VALID iff the record is measured (rule 1 of gap filling: score != 0 and four finite values), pc2 > 0 (the
+ *      point lies in front of the camera) and u, v are finite.
+ * snowmocap_amd/reproject.py::reproject_reference / reprojection_cost_reference are this rule in NumPy, plain operations in this
+ * order; the kernels (snowmocap_amd/csrc/snowtri_reproject.hpp: fused multiply-adds, one 1 / pc2 for x and y) stay within 1e-11 px of
+ * the exact value of the rule (2e-11 px with RAW) on rigs with fx <= 760 and points within |d| / pc2 <= 1.8 (tests/test_gpu_reproject.py).
+ *
+ * snowtri_reproject: xyzs [F][P][kn][4] -> pix [F][C][P][kn][3] of pix_dtype, the layout of kpts: the output feeds
+ * snowtri_triangulate_condense unchanged.  A valid projection writes (u, v, score), each rounded once to pix_dtype; an invalid one
+ * writes (0, 0, 0), which every score gate downstream drops.  A pixel's bits depend on its own record and camera only, never on the
+ * batch around it (k_reproject: one lane per observation, no loop).
+ *
+ * snowtri_reproject_cost: the same projections compared with the detections kpts [F][C][Pmax][kn][3] of kpts_dtype (n_persons
+ * [F][C] int32 or NULL = Pmax everywhere) without being written anywhere: cost_sum [F][C][P][Pmax] float64, cost_n the same shape
+ * int32.  Joint j of detection q COUNTS iff q < n_persons[f][c], not (score < keypoint_score_threshold), and its u, v are finite.
+ * cost_n[f][c][p][q] = the joints j whose projection of (p, j) is valid and whose detection (q, j) counts; cost_sum = the sum over
+ * those joints of (u - u_det)^2 + (v - v_det)^2 in fp64, px^2, and 0 when cost_n is 0.  With SNOWTRI_REPROJECT_RAW the comparison
+ * is made on the raw frame against raw detections: no undistorted copy of the keypoints is needed.  The sum of an item is formed in
+ * an order that depends on kn alone (k_reproject_cost: one wave per (f, c, p), lane l adds joints l, l + 64, ... in turn, then a
+ * fixed butterfly over the wave): not on F, the item's place in the launch or how a batch is cut into calls; it is NOT joint order,
+ * so it agrees with the NumPy rule to rounding (128 eps of the sum), not bit for bit.  Both kernels share one projection function:
+ * the cost of a person against its own float64 snowtri_reproject output is exactly 0.
+ *
+ * Refusals (SNOWTRI_ERR_BAD_ARG, snowtri_last_error() names the argument; nothing is enqueued or written): a NULL or camera-less
+ * context, an unknown dtype, memspace or flag bit, F < 0, P, kn or Pmax < 1, a K that is not [[fx, s, cx], [0, fy, cy], [0, 0, 1]]
+ * with fx, fy != 0 (the condition of snowtri_ctx_set_distortion), SNOWTRI_REPROJECT_RAW before snowtri_ctx_set_distortion, a NaN
+ * threshold, a NULL array other than n_persons, a device pointer that is not aligned to its element size.  Sizes: snowtri_reproject
+ * F * C * P * kn <= (2^31 - 1) * 256 observations; snowtri_reproject_cost kn <= 256 (a lane holds four joints), F * C * P <=
+ * (2^31 - 1) * 4 and F * C * P * Pmax <= 2^48.  F == 0 is SNOWTRI_OK and looks at no pointer.  SNOWTRI_DEVICE: asynchronous on
+ * `stream`, no host read, no allocation, no internal stream.  SNOWTRI_HOST: staged and synchronous. */
+#define SNOWTRI_REPROJECT_RAW 1u /* flags: pixels on the raw (distorted) frame */
+int snowtri_reproject(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, uint32_t flags,
+                      void *pix, int pix_dtype, int memspace, void *stream);
+int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+                           const void *kpts, int kpts_dtype, const int32_t *n_persons /* [F][C], may be NULL */,
+                           double keypoint_score_threshold, uint32_t flags, double *cost_sum, int32_t *cost_n, int memspace,
+                           void *stream);
+
 /* Measurement aid: HIP-event time (ms) of the kernels launched by the LAST
  * snowtri_triangulate_condense call on this context, measured on the stream they ran on
  * (blocks until they finish).  kernel_ms[0] = dominant fused kernel, [1] = everything else. */

@@ -21,6 +21,7 @@ PAIRWISE, DLT, DLT_ROBUST = 0, 1, 2
 FLAG_SINGULAR, FLAG_OVERFLOW, FLAG_FASTPATH = 1, 2, 4
 DESPIKE_MARK, DESPIKE_REPLACE = 0, 1                       # snowtri_despike_joint_track: mode
 DESPIKE_KEPT, DESPIKE_SPIKE, DESPIKE_MISSING, DESPIKE_UNSUPPORTED = 0, 1, 2, 3   # ... and its codes
+REPROJECT_RAW = 1              # snowtri_reproject / snowtri_reproject_cost: flags -- pixels on the raw (distorted) frame
 CALL_NO_ZERO_FILL = 1          # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
 TEST_LIB_PATH = os.path.join(_HERE, "libsnowtri_dbg.so")   # -DSNOWTRI_DEBUG_BOUNDS -DSNOWTRI_TEST_KNOBS (tests only: use_library)
 
@@ -135,6 +136,9 @@ _SIGNATURES = {
     "snowtri_ctx_set_distortion": (ct.c_int, [_c_p, _c_p]),
     "snowtri_undistort_keypoints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, _c_p, ct.c_int,
                                                ct.c_int, _c_p]),
+    "snowtri_reproject": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_uint32, _c_p, ct.c_int, ct.c_int, _c_p]),
+    "snowtri_reproject_cost": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p,
+                                          ct.c_double, ct.c_uint32, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_last_kernel_ms": (ct.c_int, [_c_p, ct.POINTER(ct.c_float * 2)]),
     "snowtri_set_timing": (ct.c_int, [_c_p, ct.c_int]),
     "snowtri_timing_collect": (ct.c_int, [_c_p, _c_p, ct.c_int32]),
@@ -227,6 +231,14 @@ def dtype_code(dt):
     raise TypeError(f"snowtri supports float32/float64 I/O, not {dt}")
 
 
+def _float_code(dtype):
+    """F32 / F64 of a NumPy or torch dtype (or its name)."""
+    try:
+        return dtype_code(dtype)
+    except TypeError:
+        return dtype_code(str(dtype).replace("torch.", ""))
+
+
 class Context:
     """Owner of a snowtri_ctx (rig constants + device scratch).  Not thread-safe."""
 
@@ -295,6 +307,101 @@ class Context:
         check(self.L.snowtri_undistort_keypoints(self.handle, F, Pmax, J, ptr(a), ptr(out), dtype_code(a.dtype), HOST,
                                                 None), "snowtri_undistort_keypoints")
         return out
+
+    # ---- reprojection (include/snowtri.h, "Reprojection") -----------------------------------------
+    def _records_in(self, xyzs, who):
+        """xyzs [F, P, kn, 4], a host array or a contiguous CUDA tensor -> (array, is_tensor, F, P, kn, dtype code)."""
+        if hasattr(xyzs, "is_cuda"):
+            import torch
+            if xyzs.dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"snowtri supports float32/float64 joints, not {xyzs.dtype}")
+            if not xyzs.is_cuda or not xyzs.is_contiguous():
+                raise ValueError(f"a tensor given to {who} must be a contiguous CUDA tensor (NumPy arrays are staged from the host)")
+            code = F32 if xyzs.dtype == torch.float32 else F64
+            tensor = True
+        else:
+            xyzs = np.asarray(xyzs)
+            if xyzs.dtype != np.float32:
+                xyzs = xyzs.astype(np.float64, copy=False)
+            xyzs = np.ascontiguousarray(xyzs)
+            code = dtype_code(xyzs.dtype)
+            tensor = False
+        if len(xyzs.shape) != 4 or xyzs.shape[-1] != 4:
+            raise ValueError(f"xyzs must be [F, P, kn, 4] records (got shape {tuple(xyzs.shape)})")
+        F, P, kn, _ = (int(v) for v in xyzs.shape)
+        return xyzs, tensor, F, P, kn, code
+
+    def _reproject_status(self, rc, where):
+        if rc == ERR_BAD_ARG:
+            raise ValueError(f"{where}: {self.L.snowtri_last_error().decode()}")
+        check(rc, where)
+
+    def reproject(self, xyzs, raw=False, dtype=None, stream=None):
+        """Joint records xyzs [F, P, kn, 4] (float32 / float64; a host array, or a contiguous CUDA tensor used in place and
+        asynchronously on `stream`, default torch's current one) -> pix [F, C, P, kn, 3] = (u, v, score) in every camera, the
+        layout of kpts; (0, 0, 0) where the record is missing, the point is behind the camera or the pixel is not finite.
+        raw: pixels on the raw frame (set_distortion first).  dtype: of pix, float32 or float64 (default: that of xyzs)."""
+        xyzs, tensor, F, P, kn, code = self._records_in(xyzs, "Context.reproject")
+        flags = REPROJECT_RAW if raw else 0
+        if tensor:
+            import torch
+            pdt = xyzs.dtype if dtype is None else (torch.float32 if _float_code(dtype) == F32 else torch.float64)
+            pix = torch.empty((F, self.C, P, kn, 3), dtype=pdt, device=xyzs.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(xyzs.device).cuda_stream
+            rc = self.L.snowtri_reproject(self.handle, F, P, kn, ct.c_void_p(xyzs.data_ptr()), code, flags, ct.c_void_p(pix.data_ptr()),
+                                          F32 if pdt == torch.float32 else F64, DEVICE, ct.c_void_p(stream) if stream else None)
+        else:
+            pix = np.empty((F, self.C, P, kn, 3), dtype=xyzs.dtype if dtype is None else (np.float32 if _float_code(dtype) == F32 else np.float64))
+            rc = self.L.snowtri_reproject(self.handle, F, P, kn, ptr(xyzs), code, flags, ptr(pix), dtype_code(pix.dtype), HOST, None)
+        self._reproject_status(rc, "snowtri_reproject")
+        return pix
+
+    def reproject_cost(self, xyzs, kpts, n_persons=None, keypoint_score_threshold=0.0, raw=False, stream=None):
+        """xyzs [F, P, kn, 4] against the detections kpts [F, C, Pmax, kn, 3] (n_persons [F, C] int32 or None) ->
+        (cost_sum [F, C, P, Pmax] float64 px^2, cost_n int32): per 3D person and detection the summed squared pixel distance over the
+        joints whose projection is valid and whose detection counts, and how many those are.  Host arrays, or contiguous CUDA tensors
+        (all of them) used in place and asynchronously on `stream`.  raw: compared on the raw frame (set_distortion first)."""
+        xyzs, tensor, F, P, kn, code = self._records_in(xyzs, "Context.reproject_cost")
+        flags = REPROJECT_RAW if raw else 0
+        if hasattr(kpts, "is_cuda") != tensor or (n_persons is not None and hasattr(n_persons, "is_cuda") != tensor):
+            raise ValueError("Context.reproject_cost takes host arrays or CUDA tensors, not a mixture")
+        if len(kpts.shape) != 5 or tuple(kpts.shape[:2]) != (F, self.C) or tuple(kpts.shape[3:]) != (kn, 3):
+            raise ValueError(f"kpts must be [F={F}, C={self.C}, Pmax, kn={kn}, 3] (got shape {tuple(kpts.shape)})")
+        Pmax = int(kpts.shape[2])
+        if tensor:
+            import torch
+            if kpts.dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"snowtri supports float32/float64 keypoints, not {kpts.dtype}")
+            if not kpts.is_cuda or not kpts.is_contiguous() or kpts.device != xyzs.device:
+                raise ValueError("kpts must be a contiguous CUDA tensor on the device of xyzs")
+            if n_persons is not None and (n_persons.dtype != torch.int32 or not n_persons.is_contiguous() or n_persons.device != xyzs.device
+                                          or tuple(n_persons.shape) != (F, self.C)):
+                raise ValueError("n_persons must be a contiguous int32 CUDA tensor [F, C] on the device of xyzs")
+            cs = torch.empty((F, self.C, P, Pmax), dtype=torch.float64, device=xyzs.device)
+            cn = torch.empty((F, self.C, P, Pmax), dtype=torch.int32, device=xyzs.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(xyzs.device).cuda_stream
+            rc = self.L.snowtri_reproject_cost(self.handle, F, P, kn, ct.c_void_p(xyzs.data_ptr()), code, Pmax, ct.c_void_p(kpts.data_ptr()),
+                                               F32 if kpts.dtype == torch.float32 else F64,
+                                               ct.c_void_p(n_persons.data_ptr()) if n_persons is not None else None,
+                                               float(keypoint_score_threshold), flags, ct.c_void_p(cs.data_ptr()), ct.c_void_p(cn.data_ptr()),
+                                               DEVICE, ct.c_void_p(stream) if stream else None)
+        else:
+            kpts = np.asarray(kpts)
+            if kpts.dtype != np.float32:
+                kpts = kpts.astype(np.float64, copy=False)
+            kpts = np.ascontiguousarray(kpts)
+            if n_persons is not None:
+                n_persons = np.ascontiguousarray(n_persons, dtype=np.int32)
+                if n_persons.shape != (F, self.C):
+                    raise ValueError(f"n_persons must be [F={F}, C={self.C}] (got shape {n_persons.shape})")
+            cs = np.empty((F, self.C, P, Pmax), dtype=np.float64)
+            cn = np.empty((F, self.C, P, Pmax), dtype=np.int32)
+            rc = self.L.snowtri_reproject_cost(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), dtype_code(kpts.dtype), ptr(n_persons),
+                                               float(keypoint_score_threshold), flags, ptr(cs), ptr(cn), HOST, None)
+        self._reproject_status(rc, "snowtri_reproject_cost")
+        return cs, cn
 
     def set_timing(self, enabled=True, attach=False):
         """attach: single-kernel calls carry the event pair on their dispatch (the kernel's own begin / end) instead of being bracketed."""

@@ -120,6 +120,20 @@ class CameraGroup:
         out = ctx.undistort_keypoints(a[None] if single else a)
         return out[0] if single else out
 
+    def reproject(self, xyzs, raw=False):
+        """The opposite direction (additive): joint records xyzs[F, P, kn, 4] or one frame [P, kn, 4] -> pix[F, C, P, kn, 3] =
+        (u, v, score) in every camera, the layout of the keypoints (include/snowtri.h, "Reprojection"): (0, 0, 0) where the record
+        is missing or the point lies behind the camera.  raw=True: on the RAW frame, through each camera's D -- where to draw the
+        skeleton on a frame `cv2.undistort` has not touched.  GPU, one lane per pixel."""
+        a = np.asarray(xyzs)
+        single = a.ndim == 3
+        ctx = self.native_context()
+        if raw:
+            n = self.camera_num
+            ctx.set_distortion(np.stack([np.asarray(c.D, dtype=np.float64).reshape(-1)[:5] for c in self.cameras[:n]]))
+        out = ctx.reproject(a[None] if single else a, raw=raw)
+        return out[0] if single else out
+
     def camera_group_info_dict(self):
         return {"camera_num": self.camera_num,
                 "camera_group_info": [c.camera_info_dict() for c in self.cameras]}

@@ -32,6 +32,7 @@
 #include "snowtri_smooth.hpp"
 #include "snowtri_blender.hpp"
 #include "snowtri_undistort.hpp"
+#include "snowtri_reproject.hpp"
 #include "snowtri_track.hpp"
 #include "snowtri_fill.hpp"
 #include "snowtri_despike.hpp"
@@ -200,6 +201,8 @@ struct snowtri_ctx {
     int num_cus = 256;
     std::vector<double> hM, ht, hK;
     double *dLens = nullptr;  // [C][kLensStride], set by snowtri_ctx_set_distortion
+    double *dProj = nullptr;  // [C][kProjStride] of snowtri_reproject[_cost]: R, t, the pinhole part of K; the lens once one is set
+    std::vector<double> hProj;
     void *dBlenderTab = nullptr;          // 24 SmoothCoef of the last (fzr, dt) given to snowtri_blender_smooth
     std::vector<double> blender_key;      // that (fzr[72], dt)
     std::vector<int32_t> hpairs;
@@ -535,6 +538,16 @@ int snowtri_ctx_create(int32_t C, const double *K, const double *R, const double
         CTX_TRY(hipMalloc(&ctx->dP, sizeof(double) * hP.size()));
         CTX_TRY(hipMemcpy(ctx->dP, hP.data(), sizeof(double) * hP.size(), hipMemcpyHostToDevice));
     }
+    ctx->hProj.assign((size_t)std::max(1, C) * kProjStride, 0.0);
+    for (int c = 0; c < C; c++) {   // (whether K has the form the reprojection needs is the reprojection's question: checked there)
+        double *q = &ctx->hProj[(size_t)c * kProjStride];
+        std::memcpy(q, R + 9 * c, sizeof(double) * 9);
+        std::memcpy(q + 9, t + 3 * c, sizeof(double) * 3);
+        const double *Kc = K + 9 * c;
+        q[12] = Kc[0]; q[13] = Kc[1]; q[14] = Kc[2]; q[15] = Kc[4]; q[16] = Kc[5];
+    }
+    CTX_TRY(hipMalloc(&ctx->dProj, sizeof(double) * ctx->hProj.size()));
+    CTX_TRY(hipMemcpy(ctx->dProj, ctx->hProj.data(), sizeof(double) * ctx->hProj.size(), hipMemcpyHostToDevice));
     if (ctx->npairs > 0)
         CTX_TRY(hipMemcpy(ctx->dpairc, hpairc.data(), sizeof(double) * hpairc.size(), hipMemcpyHostToDevice));
     if (C > 0) {
@@ -560,6 +573,7 @@ int snowtri_ctx_destroy(snowtri_ctx *ctx) {
     if (ctx->dpairc) (void)hipFree(ctx->dpairc);
     if (ctx->dP) (void)hipFree(ctx->dP);
     if (ctx->dLens) (void)hipFree(ctx->dLens);
+    if (ctx->dProj) (void)hipFree(ctx->dProj);
     if (ctx->dBlenderTab) (void)hipFree(ctx->dBlenderTab);
     for (auto &S : ctx->sets) {
         if (S.d_counters) (void)hipFree(S.d_counters);
@@ -1617,6 +1631,9 @@ int snowtri_ctx_set_distortion(snowtri_ctx *ctx, const double *D) {
     ENTER_DEVICE(ctx->device);
     if (!ctx->dLens) HIP_TRY(hipMalloc(&ctx->dLens, sizeof(double) * lens.size()));
     HIP_TRY(hipMemcpy(ctx->dLens, lens.data(), sizeof(double) * lens.size(), hipMemcpyHostToDevice));
+    for (int c = 0; c < ctx->C; c++)   // the same coefficients for the forward direction (SNOWTRI_REPROJECT_RAW)
+        std::memcpy(&ctx->hProj[(size_t)c * kProjStride + 17], D + 5 * c, sizeof(double) * 5);
+    HIP_TRY(hipMemcpy(ctx->dProj, ctx->hProj.data(), sizeof(double) * ctx->hProj.size(), hipMemcpyHostToDevice));
     return SNOWTRI_OK;
 }
 
@@ -2144,6 +2161,149 @@ int snowtri_despike_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const vo
                            else
                                launch_despike<double>((int)half_window, grid, block, st, T, m, tol2, (int)mode, ncols, dx, d_out, d_codes);
                        });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------- reprojection
+namespace {
+
+// What snowtri_reproject and snowtri_reproject_cost check alike, before anything is enqueued or written.  -> 0, or the status.
+int reproject_args(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, int xyz_dtype, uint32_t flags, int other_dtype,
+                   int memspace) {
+    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!ctx) return refuse("null context");
+    if (ctx->C <= 0) return refuse("the context has no cameras");
+    if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (other_dtype != SNOWTRI_F32 && other_dtype != SNOWTRI_F64))
+        return refuse("unknown dtype");
+    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
+    if (flags & ~(uint32_t)SNOWTRI_REPROJECT_RAW) return refuse("unknown flag bit");
+    if (F < 0 || P < 1 || kn < 1) return refuse("F < 0, P < 1 or kn < 1");
+    for (int c = 0; c < ctx->C; c++) {
+        const double *K = &ctx->hK[9 * (size_t)c];
+        if (K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0 || K[0] == 0.0 || K[4] == 0.0)
+            return refuse("K must be [[fx, s, cx], [0, fy, cy], [0, 0, 1]] for every camera");
+    }
+    if ((flags & SNOWTRI_REPROJECT_RAW) && !ctx->dLens) return refuse("SNOWTRI_REPROJECT_RAW needs snowtri_ctx_set_distortion first");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int snowtri_reproject(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, uint32_t flags, void *pix,
+                      int pix_dtype, int memspace, void *stream) {
+    const char *who = "snowtri_reproject";
+    if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, flags, pix_dtype, memspace)) return rc;
+    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    // one lane per observation, 256 per workgroup on a one-dimensional grid; 64-bit element offsets
+    if (F == 0) return SNOWTRI_OK;
+    const int64_t max_obs = (int64_t)0x7fffffff * 256, per_person_frame = (int64_t)P * kn;   // (two int32: no overflow)
+    if (per_person_frame > max_obs / ctx->C || F > max_obs / (per_person_frame * ctx->C))
+        return refuse("F * C * P * kn must not exceed (2^31 - 1) * 256 observations");
+    const int64_t per_frame = per_person_frame * ctx->C;
+    if (!xyzs || !pix) return refuse("null array (xyzs or pix)");
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) & (dtype_size(xyz_dtype) - 1)) || (((uintptr_t)pix) & (dtype_size(pix_dtype) - 1))))
+        return refuse("xyzs and pix must be aligned to their element size");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_obs = F * per_frame;
+    const size_t x_bytes = dtype_size(xyz_dtype) * 4 * (size_t)F * P * kn, p_bytes = dtype_size(pix_dtype) * 3 * (size_t)n_obs;
+    const void *dx = xyzs;
+    void *dp = pix;
+    if (memspace == SNOWTRI_HOST) {
+        int rc = ctx->in.ensure(x_bytes);
+        if (rc) return rc;
+        rc = ctx->out.ensure(p_bytes);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->in.p, xyzs, x_bytes, hipMemcpyHostToDevice, st));
+        dx = ctx->in.p;
+        dp = ctx->out.p;
+    }
+    const dim3 grid((unsigned)((n_obs + 255) / 256));
+    const int raw = (flags & SNOWTRI_REPROJECT_RAW) ? 1 : 0;
+#define LAUNCH_REPROJECT(TX, TP)                                                                                                  \
+    hipLaunchKernelGGL((k_reproject<TX, TP>), grid, dim3(256), 0, st, n_obs, (int)ctx->C, (int)P, (int)kn, raw, (const double *)ctx->dProj, \
+                       (const TX *)dx, (TP *)dp)
+    if (xyz_dtype == SNOWTRI_F32) {
+        if (pix_dtype == SNOWTRI_F32) LAUNCH_REPROJECT(float, float);
+        else LAUNCH_REPROJECT(float, double);
+    } else {
+        if (pix_dtype == SNOWTRI_F32) LAUNCH_REPROJECT(double, float);
+        else LAUNCH_REPROJECT(double, double);
+    }
+#undef LAUNCH_REPROJECT
+    HIP_TRY(hipGetLastError());
+    if (memspace == SNOWTRI_HOST) {
+        HIP_TRY(hipMemcpyAsync(pix, dp, p_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SNOWTRI_OK;
+}
+
+int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
+                           int kpts_dtype, const int32_t *n_persons, double keypoint_score_threshold, uint32_t flags, double *cost_sum,
+                           int32_t *cost_n, int memspace, void *stream) {
+    const char *who = "snowtri_reproject_cost";
+    if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, flags, kpts_dtype, memspace)) return rc;
+    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (Pmax < 1) return refuse("Pmax < 1");
+    if (kn > kCostMaxJoints) return refuse("kn must not exceed 256 joints (four per lane of the wave that owns a person)");
+    if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
+    // one wave per (f, c, p), four per workgroup on a one-dimensional grid; 64-bit element offsets
+    if (F == 0) return SNOWTRI_OK;
+    const int64_t max_items = (int64_t)0x7fffffff * kCostWaves, cp = (int64_t)ctx->C * P;   // (two int32: no overflow)
+    if (cp > max_items || F > max_items / cp || Pmax > ((int64_t)1 << 48) / (F * cp))
+        return refuse("F * C * P must not exceed (2^31 - 1) * 4 persons in view, F * C * P * Pmax 2^48 costs");
+    if (!xyzs || !kpts || !cost_sum || !cost_n) return refuse("null array (xyzs, kpts, cost_sum or cost_n)");
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) & (dtype_size(xyz_dtype) - 1)) || (((uintptr_t)kpts) & (dtype_size(kpts_dtype) - 1)) ||
+                                       (((uintptr_t)cost_sum) & 7u) || (((uintptr_t)cost_n) & 3u) || (((uintptr_t)n_persons) & 3u)))
+        return refuse("xyzs, kpts, n_persons, cost_sum and cost_n must be aligned to their element size");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_items = F * cp, n_cost = n_items * Pmax;
+    const size_t x_bytes = dtype_size(xyz_dtype) * 4 * (size_t)F * P * kn, k_bytes = dtype_size(kpts_dtype) * 3 * (size_t)F * ctx->C * Pmax * kn;
+    const size_t np_bytes = sizeof(int32_t) * (size_t)F * ctx->C, s_bytes = sizeof(double) * (size_t)n_cost, n_bytes = sizeof(int32_t) * (size_t)n_cost;
+    const void *dx = xyzs, *dk = kpts;
+    const int32_t *dnp = n_persons;
+    double *ds = cost_sum;
+    int32_t *dn = cost_n;
+    if (memspace == SNOWTRI_HOST) {
+        int rc = ctx->in.ensure(pad16(x_bytes) + pad16(k_bytes) + np_bytes);
+        if (rc) return rc;
+        rc = ctx->out.ensure(pad16(s_bytes) + n_bytes);
+        if (rc) return rc;
+        unsigned char *din = (unsigned char *)ctx->in.p, *dout = (unsigned char *)ctx->out.p;
+        HIP_TRY(hipMemcpyAsync(din, xyzs, x_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes), kpts, k_bytes, hipMemcpyHostToDevice, st));
+        if (n_persons) HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes) + pad16(k_bytes), n_persons, np_bytes, hipMemcpyHostToDevice, st));
+        dx = din;
+        dk = din + pad16(x_bytes);
+        dnp = n_persons ? (const int32_t *)(din + pad16(x_bytes) + pad16(k_bytes)) : nullptr;
+        ds = (double *)dout;
+        dn = (int32_t *)(dout + pad16(s_bytes));
+    }
+    const dim3 grid((unsigned)((n_items + kCostWaves - 1) / kCostWaves));
+    const int raw = (flags & SNOWTRI_REPROJECT_RAW) ? 1 : 0;
+#define LAUNCH_COST(TX, TK)                                                                                                           \
+    hipLaunchKernelGGL((k_reproject_cost<TX, TK>), grid, dim3(64 * kCostWaves), 0, st, n_items, (int)ctx->C, (int)P, (int)Pmax, (int)kn, raw, \
+                       keypoint_score_threshold, (const double *)ctx->dProj, (const TX *)dx, (const TK *)dk, dnp, ds, dn)
+    if (xyz_dtype == SNOWTRI_F32) {
+        if (kpts_dtype == SNOWTRI_F32) LAUNCH_COST(float, float);
+        else LAUNCH_COST(float, double);
+    } else {
+        if (kpts_dtype == SNOWTRI_F32) LAUNCH_COST(double, float);
+        else LAUNCH_COST(double, double);
+    }
+#undef LAUNCH_COST
+    HIP_TRY(hipGetLastError());
+    if (memspace == SNOWTRI_HOST) {
+        HIP_TRY(hipMemcpyAsync(cost_sum, ds, s_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cost_n, dn, n_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SNOWTRI_OK;
 }
 
 }  // extern "C"

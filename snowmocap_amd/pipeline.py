@@ -40,7 +40,8 @@ class TrackPipeline:
     def close(self):
         self.bt.close()
 
-    def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0, despike=None):
+    def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0, despike=None,
+            reproject=None):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -78,7 +79,43 @@ class TrackPipeline:
         fill_gaps == 0 it becomes the window median (DESPIKE_REPLACE), since without a filler a marked spike would reach the filter
         as a position at the origin.  Adds spike_codes [F, P, kn] (uint8, despike.DESPIKE_*) and xyzs_despiked [F, P, kn, 4], the
         records the fill (or the filters) consumed; outside every filtered sequence: the records of xyzs, DESPIKE_MISSING or
-        DESPIKE_UNSUPPORTED (untested).  None (the default): off, nothing changes and no extra key appears."""
+        DESPIKE_UNSUPPORTED (untested).  None (the default): off, nothing changes and no extra key appears.
+        reproject=gate_px: how the views agree with the result.  res["xyzs"] (whatever indexes it: list order, or slots with
+        ragged="track") is projected back into every camera and compared with the keypoints the caller passed -- on the RAW frame
+        when the pipeline was built with D, so no undistorted copy is made: reproject.match_detections on k_reproject_cost with
+        this gate (an RMS pixel distance) and the pipeline's keypoint_score_threshold, reproject.view_residuals on k_reproject.
+        Adds det_of [F, C, P] (the detection of camera c that belongs to person p of xyzs, -1: none), shared [F, C, P] (persons of one
+        view that chose the same detection: the match is not one-to-one), view_rms [F, C, P] (px, NaN without a match) and view_n.
+        None (the default): off, nothing changes and no key is added."""
+        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike)
+        if reproject is not None:
+            self._add_reprojection(res, kpts, n_persons, float(reproject))
+        return res
+
+    def _add_reprojection(self, res, kpts, n_persons, gate_px):
+        """run(reproject=gate_px): res["xyzs"] against the keypoints the caller passed (on the raw frame when the pipeline has D)."""
+        import torch
+        from .reproject import match_detections, view_residuals
+        dev = torch.device("cuda", self.device)
+        if not torch.is_tensor(kpts):
+            kpts = torch.from_numpy(np.ascontiguousarray(kpts)).to(dev)
+        if n_persons is not None and not torch.is_tensor(n_persons):
+            n_persons = torch.from_numpy(np.ascontiguousarray(n_persons, dtype=np.int32)).to(dev)
+        if n_persons is not None:
+            n_persons = n_persons.to(torch.int32).contiguous()
+        kpts = kpts.contiguous()
+        J = int(kpts.shape[3])
+        if J != self.kn:                                  # the joints the triangulation kept are the first kn of a detection
+            kpts = kpts[:, :, :, :self.kn].contiguous()
+        xyzs = res["xyzs"].contiguous()
+        ctx, raw, thr = self.bt.ctx, self.bt.undistort, float(self.th["keypoint_score_threshold"])
+        cost_sum, cost_n = ctx.reproject_cost(xyzs, kpts, n_persons=n_persons, keypoint_score_threshold=thr, raw=raw)
+        res["det_of"], res["shared"] = match_detections(cost_sum, cost_n, gate_px)
+        pix = ctx.reproject(xyzs, raw=raw, dtype=torch.float64)
+        _, res["view_rms"], res["view_n"] = view_residuals(pix, kpts, res["det_of"], thr)
+
+    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike):
+        """run() without its reprojection keys."""
         dsp = despike_args(despike)
         import torch
         dev = torch.device("cuda", self.device)
@@ -270,7 +307,9 @@ class ShardedTrackPipeline:
     TrackPipeline.run's fill_gaps is NOT offered here: a gap that crosses a shard boundary needs the measured records on both
     sides of it, i.e. a halo exchange of up to max_gap frames per rank before the fill, which has not been built.  Its despike is
     left out for the same reason: the window of a record within half_window frames of a shard boundary holds records of the
-    neighbouring rank."""
+    neighbouring rank.  Its reproject is not offered either: the caller holds only its own block of keypoints, and the per-view
+    keys would have to be gathered beside the track; run TrackPipeline-style reprojection per rank with reproject.reprojection_cost
+    on the block's xyzs if it is wanted."""
 
     def __init__(self, K, R, t, thresholds, blender_smooth_profile, n_persons_out=1, device=0, group=None, method=_lib.PAIRWISE):
         self.pipe = TrackPipeline(K, R, t, thresholds, blender_smooth_profile, n_persons_out=n_persons_out, device=device, method=method)
