@@ -99,6 +99,62 @@ struct Scratch {
     }
 };
 
+// The host arrays of one call staged through two Scratch buffers: `ins` holds what the kernels only read, `outs` what they
+// write.  The entry point declares each array by the address of its own device-pointer variable, which holds the caller's
+// pointer until begin() puts the staged address there (a null pointer declares nothing and stays null); begin() goes before
+// the first launch, end() behind the last.  Both buffers are sized before either base pointer is taken -- Scratch::ensure
+// frees and reallocates -- and every array starts on a 16-byte boundary (the uint4 kernels).  With host == false (a
+// SNOWTRI_DEVICE call) nothing happens at all: the caller's pointers pass through and the buffers, which may hold a host
+// caller's data, are not touched.
+struct Staging {
+    enum Kind { kIn, kOut, kInOut };
+    struct Entry {
+        void *var, *host, *dev;   // the entry point's variable, the caller's array, its staged copy
+        size_t bytes, off;
+        Kind kind;
+    };
+    static constexpr int kMaxArrays = 8;
+    Scratch &ins, &outs;
+    const bool host;
+    const hipStream_t st;
+    Entry e[kMaxArrays];
+    int n = 0;
+    size_t in_bytes = 0, out_bytes = 0;
+
+    Staging(Scratch &ins_, Scratch &outs_, bool host_, hipStream_t st_) : ins(ins_), outs(outs_), host(host_), st(st_) {}
+    template <typename T> void in(const T **var, size_t bytes) { add(var, (void *)*var, bytes, kIn); }
+    template <typename T> void out(T **var, size_t bytes) { add(var, (void *)*var, bytes, kOut); }
+    template <typename T> void inout(T **var, size_t bytes) { add(var, (void *)*var, bytes, kInOut); }
+    void add(void *var, void *host_array, size_t bytes, Kind kind) {
+        if (!host || !host_array) return;
+        size_t &total = kind == kIn ? in_bytes : out_bytes;
+        if (n < kMaxArrays) e[n] = Entry{var, host_array, nullptr, bytes, total, kind};
+        ++n;
+        total += (bytes + 15) & ~(size_t)15;
+    }
+    int begin() {
+        if (n > kMaxArrays) {
+            g_last_error = "Staging: more arrays than kMaxArrays";
+            return SNOWTRI_ERR_BAD_ARG;
+        }
+        if (int rc = in_bytes ? ins.ensure(in_bytes) : 0) return rc;
+        if (int rc = out_bytes ? outs.ensure(out_bytes) : 0) return rc;
+        for (int i = 0; i < n; i++) {
+            e[i].dev = (char *)(e[i].kind == kIn ? ins.p : outs.p) + e[i].off;
+            if (e[i].kind != kOut) HIP_TRY(hipMemcpyAsync(e[i].dev, e[i].host, e[i].bytes, hipMemcpyHostToDevice, st));
+            std::memcpy(e[i].var, &e[i].dev, sizeof(void *));   // (the variable is a pointer to some T: all of one representation)
+        }
+        return SNOWTRI_OK;
+    }
+    int end() {   // the downloads of the declared outputs, then the call's one synchronisation
+        if (!host) return SNOWTRI_OK;
+        for (int i = 0; i < n; i++)
+            if (e[i].kind != kIn) HIP_TRY(hipMemcpyAsync(e[i].host, e[i].dev, e[i].bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return SNOWTRI_OK;
+    }
+};
+
 // Page-locked host staging for the small per-frame calls: one H2D and one D2H per call, both truly asynchronous
 // (a pageable copy is staged and synchronised by the runtime, ~10-20 us each).
 struct PinnedScratch {
@@ -149,6 +205,9 @@ int inv3(const double *m, double *o) {
     o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
     return 0;
 }
+
+// K = [[fx, s, cx], [0, fy, cy], [0, 0, 1]] with fx, fy != 0: the pinhole part the lens model and the reprojection take apart
+bool pinhole_K(const double *K) { return K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0; }
 
 constexpr int kTimingRing = 1024;
 // ctx->d_counters: [0] singular pairs, [1] slow frames, [2] frame queue of k_frame_recompute, [6..9] slow / exact / slow
@@ -808,37 +867,30 @@ int snowtri_fastmath_probe(snowtri_ctx *ctx, int64_t n, const double *x, double 
     if (!ctx || n < 1 || !x || !rcp_nr2_out || !rcp_nr1_out || !rsq_nr1_out) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     const size_t b = sizeof(double) * n;
-    int rc = ctx->in.ensure(b);
-    if (rc) return rc;
-    rc = ctx->out.ensure(3 * b);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(ctx->in.p, x, b, hipMemcpyHostToDevice));
-    double *o = (double *)ctx->out.p;
-    hipLaunchKernelGGL(k_fastmath_probe, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n,
-                       (const double *)ctx->in.p, o, o + n, o + 2 * n);
+    Staging sg(ctx->in, ctx->out, true, nullptr);
+    sg.in(&x, b);
+    sg.out(&rcp_nr2_out, b);
+    sg.out(&rcp_nr1_out, b);
+    sg.out(&rsq_nr1_out, b);
+    if (int rc = sg.begin()) return rc;
+    hipLaunchKernelGGL(k_fastmath_probe, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n, x, rcp_nr2_out, rcp_nr1_out,
+                       rsq_nr1_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(rcp_nr2_out, o, b, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rcp_nr1_out, o + n, b, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rsq_nr1_out, o + 2 * n, b, hipMemcpyDeviceToHost));
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 int snowtri_fastmath_probe_raw(snowtri_ctx *ctx, int64_t n, const double *x, double *rcp_raw_out, double *rsq_raw_out) {
     if (!ctx || n < 1 || !x || !rcp_raw_out || !rsq_raw_out) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     const size_t b = sizeof(double) * n;
-    int rc = ctx->in.ensure(b);
-    if (rc) return rc;
-    rc = ctx->out.ensure(2 * b);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(ctx->in.p, x, b, hipMemcpyHostToDevice));
-    double *o = (double *)ctx->out.p;
-    hipLaunchKernelGGL(k_fastmath_probe_raw, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n,
-                       (const double *)ctx->in.p, o, o + n);
+    Staging sg(ctx->in, ctx->out, true, nullptr);
+    sg.in(&x, b);
+    sg.out(&rcp_raw_out, b);
+    sg.out(&rsq_raw_out, b);
+    if (int rc = sg.begin()) return rc;
+    hipLaunchKernelGGL(k_fastmath_probe_raw, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n, x, rcp_raw_out, rsq_raw_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(rcp_raw_out, o, b, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rsq_raw_out, o + n, b, hipMemcpyDeviceToHost));
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 int snowtri_calib_stream(snowtri_ctx *ctx, const void *src, int64_t read_bytes, void *dst, int64_t write_bytes, void *stream) {
@@ -863,16 +915,13 @@ int snowtri_rays_from_pixels(snowtri_ctx *ctx, int32_t cam, int64_t n, const dou
     if (cam < 0 || cam >= ctx->C) return SNOWTRI_ERR_BAD_INDEX;   // cameras[camera_index] raises IndexError (camera.py:236)
     if (n == 0) return SNOWTRI_OK;
     ENTER_DEVICE(ctx->device);
-    int rc = ctx->in.ensure(sizeof(double) * 2 * n);
-    if (rc) return rc;
-    rc = ctx->out.ensure(sizeof(double) * 3 * n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(ctx->in.p, uv, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_rays, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n,
-                       ctx->dM + 9 * cam, (const double *)ctx->in.p, (double *)ctx->out.p);
+    Staging sg(ctx->in, ctx->out, true, nullptr);
+    sg.in(&uv, sizeof(double) * 2 * n);
+    sg.out(&rays, sizeof(double) * 3 * n);
+    if (int rc = sg.begin()) return rc;
+    hipLaunchKernelGGL(k_rays, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n, ctx->dM + 9 * cam, uv, rays);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(rays, ctx->out.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 // ------------------------------------------------------------------------------------------ A2
@@ -884,23 +933,18 @@ int snowtri_skew_ray_batch(snowtri_ctx *ctx, int64_t n, const double *hm, const 
     if (n == 0) return SNOWTRI_OK;
     ENTER_DEVICE(ctx->device);
     const size_t v = sizeof(double) * 3 * n;
-    int rc = ctx->in.ensure(4 * v);
-    if (rc) return rc;
-    rc = ctx->out.ensure(v + sizeof(double) * n);
-    if (rc) return rc;
-    char *din = (char *)ctx->in.p;
-    HIP_TRY(hipMemcpy(din, hm, v, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(din + v, hs, v, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(din + 2 * v, tm, v, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(din + 3 * v, ts, v, hipMemcpyHostToDevice));
+    Staging sg(ctx->in, ctx->out, true, nullptr);
+    sg.in(&hm, v);
+    sg.in(&hs, v);
+    sg.in(&tm, v);
+    sg.in(&ts, v);
+    sg.out(&W, v);
+    sg.out(&dist, sizeof(double) * n);
+    if (int rc = sg.begin()) return rc;
     HIP_TRY(hipMemset(ctx->d_counters, 0, sizeof(unsigned long long)));
-    double *dW = (double *)ctx->out.p, *ddist = dW + 3 * n;
-    hipLaunchKernelGGL(k_skew, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n,
-                       (const double *)din, (const double *)(din + v), (const double *)(din + 2 * v),
-                       (const double *)(din + 3 * v), ddist, dW, ctx->d_counters);
+    hipLaunchKernelGGL(k_skew, dim3(grid_for(n, kBlock, ctx->num_cus * 8)), dim3(kBlock), 0, 0, n, hm, hs, tm, ts, dist, W, ctx->d_counters);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(W, dW, v, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dist, ddist, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (int rc = sg.end()) return rc;
     unsigned long long ns = 0;
     HIP_TRY(hipMemcpy(&ns, ctx->d_counters, sizeof(ns), hipMemcpyDeviceToHost));
     if (n_singular) *n_singular = (int64_t)ns;
@@ -1464,24 +1508,13 @@ int snowtri_smooth_shard_local(snowtri_ctx *ctx, int64_t T, int64_t n, const dou
     const size_t bytes = sizeof(double) * (size_t)T * n;
     const double *dx = x;
     double *dy = y, *dend = end_state;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(bytes + sizeof(double) * 2 * n);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, x, bytes, hipMemcpyHostToDevice, st));
-        dx = (const double *)ctx->in.p;
-        dy = (double *)ctx->out.p;
-        dend = end_state ? dy + (size_t)T * n : nullptr;
-    }
-    int rc = smooth_local_dev(ctx, st, T, n, dx, dy, first != 0, k, dend);
-    if (rc) return rc;
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(y, dy, bytes, hipMemcpyDeviceToHost, st));
-        if (end_state) HIP_TRY(hipMemcpyAsync(end_state, dend, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, bytes);
+    sg.out(&dy, bytes);
+    sg.out(&dend, sizeof(double) * 2 * n);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = smooth_local_dev(ctx, st, T, n, dx, dy, first != 0, k, dend)) return rc;
+    return sg.end();
 }
 
 int snowtri_smooth_shard_fix(snowtri_ctx *ctx, int64_t T, int64_t n, int first, const double *start_state, double f,
@@ -1495,23 +1528,12 @@ int snowtri_smooth_shard_fix(snowtri_ctx *ctx, int64_t T, int64_t n, int first, 
     const size_t bytes = sizeof(double) * (size_t)T * n;
     double *dy = y;
     const double *dstart = start_state;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->out.ensure(bytes);
-        if (rc) return rc;
-        rc = ctx->misc.ensure(sizeof(double) * 2 * n);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->out.p, y, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->misc.p, start_state, sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
-        dy = (double *)ctx->out.p;
-        dstart = (const double *)ctx->misc.p;
-    }
-    int rc = smooth_fix_dev(ctx, st, T, n, dy, first != 0, dstart, k);
-    if (rc) return rc;
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(y, dy, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.inout(&dy, bytes);
+    sg.in(&dstart, sizeof(double) * 2 * n);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = smooth_fix_dev(ctx, st, T, n, dy, first != 0, dstart, k)) return rc;
+    return sg.end();
 }
 
 // The two-pass form of the sharded protocol (round 6): _reduce = the shard's zero-state end state from ONE read of x, _scan = the
@@ -1547,23 +1569,14 @@ int snowtri_smooth_shard_combine(snowtri_ctx *ctx, int32_t world, int32_t rank, 
     const size_t gbytes = sizeof(double) * (size_t)world * (4 * (size_t)n + 1), sbytes = sizeof(double) * 2 * (size_t)n;
     const double *dg = gathered;
     double *ds = start_state;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(gbytes);
-        if (rc) return rc;
-        rc = ctx->misc.ensure(sbytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, gathered, gbytes, hipMemcpyHostToDevice, st));
-        dg = (const double *)ctx->in.p;
-        ds = (double *)ctx->misc.p;
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dg, gbytes);
+    sg.out(&ds, sbytes);
+    if (int rc = sg.begin()) return rc;
     hipLaunchKernelGGL(k_smooth_combine<UniformCoef>, dim3((unsigned)((n + kSmoothBlock - 1) / kSmoothBlock)), dim3(kSmoothBlock), 0, st, (int)world,
                        (int)rank, n, dg, UniformCoef{k}, ds);
     HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(start_state, ds, sbytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 int snowtri_smooth_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const double *xyzs, double f, double z, double r,
@@ -1591,22 +1604,12 @@ int smooth_track_impl(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, d
     const size_t bytes = sizeof(double) * (size_t)T * n;
     const double *dx = x;
     double *dy = y;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(bytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, x, bytes, hipMemcpyHostToDevice, st));
-        dx = (const double *)ctx->in.p;
-        dy = (double *)ctx->out.p;
-    }
-    int rc = smooth_whole_dev(ctx, st, T, n, dx, dy, dx, k, NoHold{}, skip4);
-    if (rc) return rc;
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(y, dy, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, bytes);
+    sg.out(&dy, bytes);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = smooth_whole_dev(ctx, st, T, n, dx, dy, dx, k, NoHold{}, skip4)) return rc;
+    return sg.end();
 }
 }  // namespace
 
@@ -1618,8 +1621,7 @@ int snowtri_ctx_set_distortion(snowtri_ctx *ctx, const double *D) {
     std::vector<double> lens((size_t)ctx->C * kLensStride, 0.0);
     for (int c = 0; c < ctx->C; c++) {
         const double *K = &ctx->hK[9 * (size_t)c];
-        // the pinhole part must be [[fx, s, cx], [0, fy, cy], [0, 0, 1]]
-        if (K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0 || K[0] == 0.0 || K[4] == 0.0) return SNOWTRI_ERR_BAD_ARG;
+        if (!pinhole_K(K)) return SNOWTRI_ERR_BAD_ARG;
         double *L = &lens[(size_t)c * kLensStride];
         L[0] = K[0]; L[1] = K[1]; L[2] = K[2]; L[3] = K[4]; L[4] = K[5];
         L[5] = 1.0 / K[0]; L[6] = 1.0 / K[4];
@@ -1651,12 +1653,10 @@ int snowtri_undistort_keypoints(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32
     const size_t bytes = (size_t)n_obs * 3 * (dtype == SNOWTRI_F32 ? 4 : 8);
     const void *din = kpts_in;
     void *dout = kpts_out;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(bytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, kpts_in, bytes, hipMemcpyHostToDevice, st));
-        din = dout = ctx->in.p;
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&din, bytes);
+    sg.out(&dout, bytes);
+    if (int rc = sg.begin()) return rc;
     const dim3 grid((unsigned)((n_obs + 255) / 256));
     if (dtype == SNOWTRI_F32)
         hipLaunchKernelGGL(k_undistort<float>, grid, dim3(256), 0, st, n_obs, (int)ctx->C, (int)per_cam,
@@ -1665,11 +1665,7 @@ int snowtri_undistort_keypoints(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32
         hipLaunchKernelGGL(k_undistort<double>, grid, dim3(256), 0, st, n_obs, (int)ctx->C, (int)per_cam,
                            (const double *)ctx->dLens, (const double *)din, (double *)dout);
     HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(kpts_out, dout, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 // ---------------------------------------------------------------------------------------- N2
@@ -1688,33 +1684,23 @@ int snowtri_blender_points(snowtri_ctx *ctx, int64_t n, int32_t keypoint_num, co
     const void *dx = xyzs;
     double *dp = out_points;
     uint8_t *dv = out_valid;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(in_bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(pt_bytes + (size_t)kBlenderPoints * n);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, xyzs, in_bytes, hipMemcpyHostToDevice, st));
-        dx = ctx->in.p;
-        dp = (double *)ctx->out.p;
-        dv = (uint8_t *)ctx->out.p + pt_bytes;
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, in_bytes);
+    sg.out(&dp, pt_bytes);
+    sg.out(&dv, (size_t)kBlenderPoints * n);
+    if (int rc = sg.begin()) return rc;
     const dim3 grid((unsigned)((n + 255) / 256));
     if (xyz_dtype == SNOWTRI_F32)
         hipLaunchKernelGGL(k_blender_points<float>, grid, dim3(256), 0, st, n, (int)keypoint_num, (const float *)dx, dp, dv);
     else
         hipLaunchKernelGGL(k_blender_points<double>, grid, dim3(256), 0, st, n, (int)keypoint_num, (const double *)dx, dp, dv);
     HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(out_points, dp, pt_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_valid, dv, (size_t)kBlenderPoints * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
-// per-bone coefficient table of the context: rebuilt and uploaded only when (fzr, dt) change -- the common caller passes the
-// same smooth profile every time, and an upload has to drain the stream first
-static int blender_table(snowtri_ctx *ctx, hipStream_t st, const double *fzr, double dt) {
+// per-bone coefficient table of the context, as the filters take it (*k): rebuilt and uploaded only when (fzr, dt) change -- the
+// common caller passes the same smooth profile every time, and an upload has to drain the stream first
+static int blender_table(snowtri_ctx *ctx, hipStream_t st, const double *fzr, double dt, TableCoef *k) {
     std::vector<double> key(fzr, fzr + 3 * kBlenderPoints);
     key.push_back(dt);
     if (!ctx->dBlenderTab) HIP_TRY(hipMalloc(&ctx->dBlenderTab, sizeof(SmoothCoef) * kBlenderPoints));
@@ -1725,6 +1711,7 @@ static int blender_table(snowtri_ctx *ctx, hipStream_t st, const double *fzr, do
         HIP_TRY(hipMemcpy(ctx->dBlenderTab, tab, sizeof(tab), hipMemcpyHostToDevice));
         ctx->blender_key = key;
     }
+    *k = TableCoef{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
     return SNOWTRI_OK;
 }
 static bool blender_shard_args_ok(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *fzr, double dt) {
@@ -1733,6 +1720,24 @@ static bool blender_shard_args_ok(snowtri_ctx *ctx, int64_t T, int64_t n_persons
         for (int i = 0; i < kBlenderPoints; i++)
             if (!(fzr[3 * i] > 0.0)) return false;
     return true;
+}
+
+// The hold's scratch in ctx->aux for n lanes over the filter's nchunks chunks: [4096 bytes | H | start | Hf | entering], with
+// H and start [max(1, nchunks)][n] doubles, Hf as many bytes and entering [n] doubles on a 256-byte boundary.
+struct HoldScratch {
+    double *H, *start;
+    uint8_t *Hf;
+    double *entering;
+};
+static int hold_scratch(snowtri_ctx *ctx, int64_t nchunks, int64_t n, HoldScratch *hs) {
+    const size_t cn = (size_t)std::max<int64_t>(1, nchunks) * n;
+    const size_t off_H = 4096, off_start = off_H + sizeof(double) * cn, off_Hf = off_start + sizeof(double) * cn,
+                 off_ent = (off_Hf + cn + 255) & ~(size_t)255;
+    int rc = ctx->aux.ensure(off_ent + sizeof(double) * (size_t)n);
+    if (rc) return rc;
+    char *aux = (char *)ctx->aux.p;
+    *hs = HoldScratch{(double *)(aux + off_H), (double *)(aux + off_start), (uint8_t *)(aux + off_Hf), (double *)(aux + off_ent)};
+    return SNOWTRI_OK;
 }
 
 // ---- N2 on a FRAME-SHARDED track (device pointers only; include/snowtri.h describes the protocol)
@@ -1763,22 +1768,16 @@ int snowtri_blender_hold_shard_apply(snowtri_ctx *ctx, int32_t world, int32_t ra
     hipStream_t st = (hipStream_t)stream;
     const int64_t nchunks = (T - 1 + kSmoothChunk - 1) / kSmoothChunk;   // the filter's chunks: frames 1 .. T-1
     if (nchunks + 1 > 65535) return SNOWTRI_ERR_BAD_ARG;   // (k_hold_fill runs nchunks + 1 block rows: checked BEFORE anything is queued)
-    const size_t cn = (size_t)std::max<int64_t>(1, nchunks) * n;
-    const size_t off_H = 4096, off_start = off_H + sizeof(double) * cn, off_Hf = off_start + sizeof(double) * cn,
-                 off_ent = (off_Hf + cn + 255) & ~(size_t)255;
-    int rc = ctx->aux.ensure(off_ent + sizeof(double) * (size_t)n);
-    if (rc) return rc;
-    char *aux = (char *)ctx->aux.p;
-    double *H = (double *)(aux + off_H), *start = (double *)(aux + off_start), *entering = (double *)(aux + off_ent);
-    uint8_t *Hf = (uint8_t *)(aux + off_Hf);
+    HoldScratch h;
+    if (int rc = hold_scratch(ctx, nchunks, n, &h)) return rc;
     const dim3 g1 = smooth_grid(n, 1);
-    hipLaunchKernelGGL(k_hold_entering, g1, dim3(256), 0, st, (int)world, (int)rank, n, gathered, entering);
+    hipLaunchKernelGGL(k_hold_entering, g1, dim3(256), 0, st, (int)world, (int)rank, n, gathered, h.entering);
     if (nchunks > 0)
-        hipLaunchKernelGGL(k_hold_last, smooth_grid(n, nchunks), dim3(256), 0, st, T, n, kSmoothChunk, 4, points, valid, H, Hf);
-    hipLaunchKernelGGL(k_hold_carry, g1, dim3(256), 0, st, n, nchunks, 4, points, valid, (const double *)H, (const uint8_t *)Hf, start,
-                       (const double *)entering);
+        hipLaunchKernelGGL(k_hold_last, smooth_grid(n, nchunks), dim3(256), 0, st, T, n, kSmoothChunk, 4, points, valid, h.H, h.Hf);
+    hipLaunchKernelGGL(k_hold_carry, g1, dim3(256), 0, st, n, nchunks, 4, points, valid, (const double *)h.H, (const uint8_t *)h.Hf, h.start,
+                       (const double *)h.entering);
     hipLaunchKernelGGL(k_hold_fill, smooth_grid(n, nchunks + 1), dim3(256), 0, st, T, n, kSmoothChunk, 4, points, valid,
-                       (const double *)start, (const double *)entering, held);
+                       (const double *)h.start, (const double *)h.entering, held);
     HIP_TRY(hipGetLastError());
     return SNOWTRI_OK;
 }
@@ -1791,9 +1790,8 @@ int snowtri_blender_smooth_shard_local(snowtri_ctx *ctx, int64_t T, int64_t n_pe
     if (!held || !y) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = blender_table(ctx, st, fzr, dt);
-    if (rc) return rc;
-    const TableCoef k{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
+    TableCoef k;
+    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
     return smooth_local_dev(ctx, st, T, n, held, y, first != 0, k, end_state);
 }
 
@@ -1805,9 +1803,8 @@ int snowtri_blender_smooth_shard_reduce(snowtri_ctx *ctx, int64_t T, int64_t n_p
     if (!held || !end_state) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = blender_table(ctx, st, fzr, dt);
-    if (rc) return rc;
-    const TableCoef k{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
+    TableCoef k;
+    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
     return smooth_whole_dev(ctx, st, T, n, held, (double *)nullptr, (const double *)nullptr, k, NoHold{}, false, first ? 1 : 0, (const double *)nullptr, end_state);
 }
 
@@ -1819,9 +1816,8 @@ int snowtri_blender_smooth_shard_scan(snowtri_ctx *ctx, int64_t T, int64_t n_per
     if (!held || !y || !start_state) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = blender_table(ctx, st, fzr, dt);
-    if (rc) return rc;
-    const TableCoef k{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
+    TableCoef k;
+    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
     return smooth_whole_dev(ctx, st, T, n, held, y, (const double *)nullptr, k, NoHold{}, false, first ? 1 : 0, start_state, (double *)nullptr);
 }
 
@@ -1833,9 +1829,8 @@ int snowtri_blender_smooth_shard_combine(snowtri_ctx *ctx, int32_t world, int32_
     if (!gathered || !start_state) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = blender_table(ctx, st, fzr, dt);
-    if (rc) return rc;
-    const TableCoef k{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
+    TableCoef k;
+    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
     hipLaunchKernelGGL(k_smooth_combine<TableCoef>, dim3((unsigned)((n + kSmoothBlock - 1) / kSmoothBlock)), dim3(kSmoothBlock), 0, st, (int)world,
                        (int)rank, n, gathered, k, start_state);
     HIP_TRY(hipGetLastError());
@@ -1850,20 +1845,16 @@ int snowtri_blender_smooth_shard_fix(snowtri_ctx *ctx, int64_t T, int64_t n_pers
     if (!start_state || !y) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = blender_table(ctx, st, fzr, dt);
-    if (rc) return rc;
-    const TableCoef k{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
+    TableCoef k;
+    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
     return smooth_fix_dev(ctx, st, T, n, y, first != 0, start_state, k);
 }
 
 int snowtri_blender_smooth(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *points,
                            const uint8_t *valid, const double *fzr, double dt, double *out, int memspace,
                            void *stream) {
-    if (!ctx || T < 0 || n_persons < 0 || !fzr || !(dt > 0.0) ||
-        (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
+    if (!fzr || !blender_shard_args_ok(ctx, T, n_persons, fzr, dt) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
         return SNOWTRI_ERR_BAD_ARG;
-    for (int i = 0; i < kBlenderPoints; i++)
-        if (!(fzr[3 * i] > 0.0)) return SNOWTRI_ERR_BAD_ARG;
     if (T == 0 || n_persons == 0) return SNOWTRI_OK;
     if (!points || !valid || !out) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
@@ -1871,50 +1862,28 @@ int snowtri_blender_smooth(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const
     const int64_t n = n_persons * kBlenderPoints * 4, nv = n_persons * kBlenderPoints;
     const int64_t nchunks = (T - 1 + kSmoothChunk - 1) / kSmoothChunk;  // the filter's chunks: frames 1..T-1
     if (nchunks > 65535) return SNOWTRI_ERR_BAD_ARG;
-    const size_t bytes = sizeof(double) * (size_t)T * n, vbytes = (size_t)T * nv;
-    // aux: [coef table | hold scratch (H, start, Hf)] (+ staged valid for host calls)
-    const size_t cn = (size_t)std::max<int64_t>(1, nchunks) * n;
-    const size_t off_H = 4096, off_start = off_H + sizeof(double) * cn, off_Hf = off_start + sizeof(double) * cn,
-                 off_valid = (off_Hf + cn + 255) & ~(size_t)255;
-    int rc = ctx->aux.ensure(off_valid + vbytes);
-    if (rc) return rc;
-    char *aux = (char *)ctx->aux.p;
-    // per-bone coefficient table: rebuilt and uploaded only when (fzr, dt) change -- the common caller passes the
-    // same smooth profile every time, and an upload has to drain the stream first
-    rc = blender_table(ctx, st, fzr, dt);
-    if (rc) return rc;
+    const size_t bytes = sizeof(double) * (size_t)T * n;
+    HoldScratch h;
+    if (int rc = hold_scratch(ctx, nchunks, n, &h)) return rc;
+    TableCoef k;
+    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
     const double *dx = points;
     const uint8_t *dv = valid;
     double *dy = out;
-    if (memspace == SNOWTRI_HOST) {
-        rc = ctx->in.ensure(bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(bytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, points, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(aux + off_valid, valid, vbytes, hipMemcpyHostToDevice, st));
-        dx = (const double *)ctx->in.p;
-        dv = (const uint8_t *)(aux + off_valid);
-        dy = (double *)ctx->out.p;
-    }
-    double *H = (double *)(aux + off_H), *start = (double *)(aux + off_start);
-    uint8_t *Hf = (uint8_t *)(aux + off_Hf);
-    const dim3 g1 = smooth_grid(n, 1);
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, bytes);
+    sg.in(&dv, (size_t)T * nv);
+    sg.out(&dy, bytes);
+    if (int rc = sg.begin()) return rc;
     if (nchunks > 0)
-        hipLaunchKernelGGL(k_hold_last, smooth_grid(n, nchunks), dim3(256), 0, st, T, n, kSmoothChunk, 4, dx, dv, H, Hf);
-    hipLaunchKernelGGL(k_hold_carry, g1, dim3(256), 0, st, n, nchunks, 4, dx, dv, (const double *)H, (const uint8_t *)Hf,
-                       start);
+        hipLaunchKernelGGL(k_hold_last, smooth_grid(n, nchunks), dim3(256), 0, st, T, n, kSmoothChunk, 4, dx, dv, h.H, h.Hf);
+    hipLaunchKernelGGL(k_hold_carry, smooth_grid(n, 1), dim3(256), 0, st, n, nchunks, 4, dx, dv, (const double *)h.H, (const uint8_t *)h.Hf,
+                       h.start);
     HIP_TRY(hipGetLastError());
-    const TableCoef k{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
-    const HoldInput hs{dv, (const double *)start, 4};
+    const HoldInput hs{dv, (const double *)h.start, 4};
     // frame 0 is returned as given, NaNs included (blender.py:176); the filters are seeded with the held row
-    rc = smooth_whole_dev(ctx, st, T, n, dx, dy, (const double *)start, k, hs);
-    if (rc) return rc;
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(out, dy, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    if (int rc = smooth_whole_dev(ctx, st, T, n, dx, dy, (const double *)h.start, k, hs)) return rc;
+    return sg.end();
 }
 
 // ------------------------------------------------------------------------------- person tracking
@@ -1922,7 +1891,6 @@ static int arg_fail(int status, const char *msg) {
     g_last_error = msg;
     return status;
 }
-static size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 size_t snowtri_track_state_bytes(int32_t S) { return (S < 1 || S > kTrackMax) ? 0 : track_state_bytes(S); }
 int snowtri_track_block_frames(void) { return kTrackBlockFrames; }
@@ -1950,35 +1918,24 @@ int snowtri_track_persons(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t
     const size_t esz = dtype_size(xyz_dtype);
     const size_t x_bytes = esz * 4 * (size_t)keypoint_num * P * F, c_bytes = sizeof(int32_t) * (size_t)F;
     const size_t so_bytes = sizeof(int32_t) * (size_t)F * P, po_bytes = sizeof(int32_t) * (size_t)F * S, st_bytes = track_state_bytes(S);
-    int rc = ctx->track.ensure(sizeof(double) * 4 * (size_t)F * P);
-    if (rc) return rc;
+    if (int rc = ctx->track.ensure(sizeof(double) * 4 * (size_t)F * P)) return rc;
+    if ((int64_t)F * P > (int64_t)0x7fffffff * 256) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: too many frames for one call");
     const void *dx = xyzs;
     const int32_t *dc = count;
     int32_t *d_so = slot_of, *d_po = person_of, *d_id = track_id;
     uint32_t *d_fl = flags;
     unsigned char *d_state = (unsigned char *)state;
-    if (memspace == SNOWTRI_HOST) {
-        rc = ctx->in.ensure(pad16(x_bytes) + c_bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(pad16(so_bytes) + 2 * pad16(po_bytes) + pad16(c_bytes) + st_bytes);
-        if (rc) return rc;
-        unsigned char *din = (unsigned char *)ctx->in.p, *dout = (unsigned char *)ctx->out.p;
-        HIP_TRY(hipMemcpyAsync(din, xyzs, x_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes), count, c_bytes, hipMemcpyHostToDevice, st));
-        dx = din;
-        dc = (const int32_t *)(din + pad16(x_bytes));
-        d_so = (int32_t *)dout;
-        d_po = (int32_t *)(dout + pad16(so_bytes));
-        d_id = (int32_t *)(dout + pad16(so_bytes) + pad16(po_bytes));
-        d_fl = flags ? (uint32_t *)(dout + pad16(so_bytes) + 2 * pad16(po_bytes)) : nullptr;
-        if (state) {
-            d_state = dout + pad16(so_bytes) + 2 * pad16(po_bytes) + pad16(c_bytes);
-            HIP_TRY(hipMemcpyAsync(d_state, state, st_bytes, hipMemcpyHostToDevice, st));
-        }
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, x_bytes);
+    sg.in(&dc, c_bytes);
+    sg.out(&d_so, so_bytes);
+    sg.out(&d_po, po_bytes);
+    sg.out(&d_id, po_bytes);
+    sg.out(&d_fl, c_bytes);
+    sg.inout(&d_state, st_bytes);
+    if (int rc = sg.begin()) return rc;
     double *d_cen = (double *)ctx->track.p;
     const dim3 grid((unsigned)(((int64_t)F * P + 255) / 256));
-    if ((int64_t)F * P > (int64_t)0x7fffffff * 256) return arg_fail(SNOWTRI_ERR_BAD_ARG, "snowtri_track_persons: too many frames for one call");
     const bool timed = ctx->timing;
     ctx->track_ev_valid = false;
     if (timed) {
@@ -1998,15 +1955,7 @@ int snowtri_track_persons(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t
         HIP_TRY(hipEventRecord(ctx->track_ev[2], st));
         ctx->track_ev_valid = true;
     }
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(slot_of, d_so, so_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(person_of, d_po, po_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(track_id, d_id, po_bytes, hipMemcpyDeviceToHost, st));
-        if (flags) HIP_TRY(hipMemcpyAsync(flags, d_fl, c_bytes, hipMemcpyDeviceToHost, st));
-        if (state) HIP_TRY(hipMemcpyAsync(state, d_state, st_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 int snowtri_track_last_ms(snowtri_ctx *ctx, float kernel_ms[2]) {
@@ -2039,28 +1988,17 @@ int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t 
     const void *dx = xyzs;
     const int32_t *d_po = person_of;
     void *d_out = xyzs_tracked;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(pad16(x_bytes) + po_bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(o_bytes);
-        if (rc) return rc;
-        unsigned char *din = (unsigned char *)ctx->in.p;
-        HIP_TRY(hipMemcpyAsync(din, xyzs, x_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes), person_of, po_bytes, hipMemcpyHostToDevice, st));
-        dx = din;
-        d_po = (const int32_t *)(din + pad16(x_bytes));
-        d_out = ctx->out.p;
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, x_bytes);
+    sg.in(&d_po, po_bytes);
+    sg.out(&d_out, o_bytes);
+    if (int rc = sg.begin()) return rc;
     const int rec_per_person = (int)(person_bytes / 16);
     const int64_t total = (int64_t)F * S * rec_per_person;
     hipLaunchKernelGGL(k_track_gather, dim3(grid_for(total, 256, ctx->num_cus * 16)), dim3(256), 0, st, F, (int)Pout_max, (int)S, rec_per_person,
                        (const uint4 *)dx, d_po, (uint4 *)d_out);
     HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(xyzs_tracked, d_out, o_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 }  // extern "C"
@@ -2095,24 +2033,14 @@ int record_pass(const char *who, snowtri_ctx *ctx, int64_t T, int64_t m, const v
     const void *dx = xyzs;
     void *d_out = out;
     uint8_t *d_codes = codes;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(pad16(bytes) + c_bytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, xyzs, bytes, hipMemcpyHostToDevice, st));
-        dx = ctx->in.p;
-        d_out = ctx->out.p;
-        d_codes = codes ? (uint8_t *)ctx->out.p + pad16(bytes) : nullptr;
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, bytes);
+    sg.out(&d_out, bytes);
+    sg.out(&d_codes, c_bytes);
+    if (int rc = sg.begin()) return rc;
     launch(dim3((unsigned)(ncols * nrows)), dim3(64, kRecWaves), st, ncols, (const uint4 *)dx, (uint4 *)d_out, d_codes);
     HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
-        if (codes) HIP_TRY(hipMemcpyAsync(codes, d_codes, c_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 template <typename IO>
@@ -2179,11 +2107,8 @@ int reproject_args(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int3
     if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
     if (flags & ~(uint32_t)SNOWTRI_REPROJECT_RAW) return refuse("unknown flag bit");
     if (F < 0 || P < 1 || kn < 1) return refuse("F < 0, P < 1 or kn < 1");
-    for (int c = 0; c < ctx->C; c++) {
-        const double *K = &ctx->hK[9 * (size_t)c];
-        if (K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0 || K[0] == 0.0 || K[4] == 0.0)
-            return refuse("K must be [[fx, s, cx], [0, fy, cy], [0, 0, 1]] for every camera");
-    }
+    for (int c = 0; c < ctx->C; c++)
+        if (!pinhole_K(&ctx->hK[9 * (size_t)c])) return refuse("K must be [[fx, s, cx], [0, fy, cy], [0, 0, 1]] for every camera");
     if ((flags & SNOWTRI_REPROJECT_RAW) && !ctx->dLens) return refuse("SNOWTRI_REPROJECT_RAW needs snowtri_ctx_set_distortion first");
     return 0;
 }
@@ -2212,15 +2137,10 @@ int snowtri_reproject(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const 
     const size_t x_bytes = dtype_size(xyz_dtype) * 4 * (size_t)F * P * kn, p_bytes = dtype_size(pix_dtype) * 3 * (size_t)n_obs;
     const void *dx = xyzs;
     void *dp = pix;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(x_bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(p_bytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->in.p, xyzs, x_bytes, hipMemcpyHostToDevice, st));
-        dx = ctx->in.p;
-        dp = ctx->out.p;
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, x_bytes);
+    sg.out(&dp, p_bytes);
+    if (int rc = sg.begin()) return rc;
     const dim3 grid((unsigned)((n_obs + 255) / 256));
     const int raw = (flags & SNOWTRI_REPROJECT_RAW) ? 1 : 0;
 #define LAUNCH_REPROJECT(TX, TP)                                                                                                  \
@@ -2235,11 +2155,7 @@ int snowtri_reproject(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const 
     }
 #undef LAUNCH_REPROJECT
     HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(pix, dp, p_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
@@ -2269,21 +2185,13 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
     const int32_t *dnp = n_persons;
     double *ds = cost_sum;
     int32_t *dn = cost_n;
-    if (memspace == SNOWTRI_HOST) {
-        int rc = ctx->in.ensure(pad16(x_bytes) + pad16(k_bytes) + np_bytes);
-        if (rc) return rc;
-        rc = ctx->out.ensure(pad16(s_bytes) + n_bytes);
-        if (rc) return rc;
-        unsigned char *din = (unsigned char *)ctx->in.p, *dout = (unsigned char *)ctx->out.p;
-        HIP_TRY(hipMemcpyAsync(din, xyzs, x_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes), kpts, k_bytes, hipMemcpyHostToDevice, st));
-        if (n_persons) HIP_TRY(hipMemcpyAsync(din + pad16(x_bytes) + pad16(k_bytes), n_persons, np_bytes, hipMemcpyHostToDevice, st));
-        dx = din;
-        dk = din + pad16(x_bytes);
-        dnp = n_persons ? (const int32_t *)(din + pad16(x_bytes) + pad16(k_bytes)) : nullptr;
-        ds = (double *)dout;
-        dn = (int32_t *)(dout + pad16(s_bytes));
-    }
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, x_bytes);
+    sg.in(&dk, k_bytes);
+    sg.in(&dnp, np_bytes);
+    sg.out(&ds, s_bytes);
+    sg.out(&dn, n_bytes);
+    if (int rc = sg.begin()) return rc;
     const dim3 grid((unsigned)((n_items + kCostWaves - 1) / kCostWaves));
     const int raw = (flags & SNOWTRI_REPROJECT_RAW) ? 1 : 0;
 #define LAUNCH_COST(TX, TK)                                                                                                           \
@@ -2298,12 +2206,7 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
     }
 #undef LAUNCH_COST
     HIP_TRY(hipGetLastError());
-    if (memspace == SNOWTRI_HOST) {
-        HIP_TRY(hipMemcpyAsync(cost_sum, ds, s_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(cost_n, dn, n_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SNOWTRI_OK;
+    return sg.end();
 }
 
 }  // extern "C"
