@@ -216,10 +216,13 @@ def check(status, where):
 
 
 def ptr(a):
-    """void* of a NumPy array (or None)."""
-    if a is None:
-        return None
-    return ct.c_void_p(a.ctypes.data)
+    """void* for a C call: the data pointer of a NumPy array or of anything with data_ptr() (a torch tensor); an int is an address or
+    a HIP stream handle (0: NULL); None and a c_void_p pass through."""
+    if a is None or isinstance(a, ct.c_void_p):
+        return a
+    if isinstance(a, int):
+        return ct.c_void_p(a) if a else None
+    return ct.c_void_p(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
 
 
 def dtype_code(dt):
@@ -237,6 +240,75 @@ def _float_code(dtype):
         return dtype_code(dtype)
     except TypeError:
         return dtype_code(str(dtype).replace("torch.", ""))
+
+
+def host_floats(a):
+    """Anything array-like -> a contiguous NumPy array: float32 stays, every other dtype becomes float64 (no copy if it already is so)."""
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        a = a.astype(np.float64, copy=False)
+    return np.ascontiguousarray(a)
+
+
+class Space:
+    """Where the arrays of one wrapper call live: on the host (NumPy arrays, staged by the library, synchronous) or on one CUDA device
+    (torch tensors, used in place and asynchronously on `stream`, default torch's current stream of that device).  Made from the call's
+    array arguments (None: ignored), which are all tensors or all not; `who` names the wrapper in the messages.  `device` is None on
+    the host, else the torch device of the first tensor; every tensor checked later has to live there."""
+
+    def __init__(self, who, *arrays, stream=None):
+        tensors = [hasattr(a, "is_cuda") for a in arrays if a is not None]
+        if any(tensors) and not all(tensors):
+            raise ValueError(f"{who} takes host arrays or CUDA tensors, not a mixture")
+        self.who, self.device, self.stream = who, None, None
+        if any(tensors):
+            import torch
+            self.torch = torch
+            self.device = next(a for a in arrays if a is not None).device
+            if stream is None and self.device.type == "cuda":      # (a CPU tensor is refused by the check of its array)
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.stream = stream
+
+    def _resident(self, a):
+        return a.is_cuda and a.is_contiguous() and a.device == self.device
+
+    def floats(self, a, what):
+        """A float array in -> (the array, its F32 / F64 code): host_floats(a) on the host, a checked float32 / float64 tensor on the device."""
+        if self.device is None:
+            a = host_floats(a)
+            return a, dtype_code(a.dtype)
+        if a.dtype not in (self.torch.float32, self.torch.float64):
+            raise TypeError(f"snowtri supports float32/float64 {what}, not {a.dtype}")
+        if not self._resident(a):
+            raise ValueError(f"a tensor given to {self.who} must be a contiguous CUDA tensor (NumPy arrays are staged from the host)")
+        return a, F32 if a.dtype == self.torch.float32 else F64
+
+    def ints(self, a, shape, what):
+        """An int32 array of exactly `shape` in: converted on the host, checked on the device."""
+        if self.device is None:
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            ok = a.shape == tuple(shape)
+        else:
+            ok = a.dtype == self.torch.int32 and self._resident(a) and tuple(a.shape) == tuple(shape)
+        if not ok:
+            raise ValueError(f"{what} given to {self.who} must be {'int32' if self.device is None else 'a contiguous int32 CUDA tensor'} "
+                             f"of shape {tuple(shape)} (got {a.dtype} {tuple(a.shape)})")
+        return a
+
+    def empty(self, shape, kind):
+        """An uninitialised output: kind = "float32", "float64", "int32", "uint8", or "flags" (uint32 on the host, int32 in torch)."""
+        if kind == "flags":
+            kind = "uint32" if self.device is None else "int32"
+        if self.device is None:
+            return np.empty(shape, dtype=kind)
+        return self.torch.empty(tuple(shape), dtype=getattr(self.torch, kind), device=self.device)
+
+    def empty_like(self, a):
+        return self.empty(a.shape, str(a.dtype).replace("torch.", ""))
+
+    def tail(self):
+        """The two arguments that end a HOST/DEVICE entry point: (memory space, stream)."""
+        return (HOST, None) if self.device is None else (DEVICE, ptr(self.stream))
 
 
 class Context:
@@ -297,10 +369,7 @@ class Context:
         """Raw-image keypoints kpts[F, C, Pmax, J, 3] -> the same array with (u, v) moved to the undistorted
         image (scores untouched); host arrays, float32 or float64.  A pixel's result depends on that pixel and its camera's
         lens only (not on the batch around it); a non-finite u or v gives a non-finite u and v."""
-        a = np.asarray(kpts)
-        if a.dtype != np.float32:
-            a = a.astype(np.float64, copy=False)
-        a = np.ascontiguousarray(a)
+        a = host_floats(kpts)
         F, C, Pmax, J, three = a.shape
         assert C == self.C and three == 3
         out = np.empty_like(a)
@@ -309,27 +378,14 @@ class Context:
         return out
 
     # ---- reprojection (include/snowtri.h, "Reprojection") -----------------------------------------
-    def _records_in(self, xyzs, who):
-        """xyzs [F, P, kn, 4], a host array or a contiguous CUDA tensor -> (array, is_tensor, F, P, kn, dtype code)."""
-        if hasattr(xyzs, "is_cuda"):
-            import torch
-            if xyzs.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"snowtri supports float32/float64 joints, not {xyzs.dtype}")
-            if not xyzs.is_cuda or not xyzs.is_contiguous():
-                raise ValueError(f"a tensor given to {who} must be a contiguous CUDA tensor (NumPy arrays are staged from the host)")
-            code = F32 if xyzs.dtype == torch.float32 else F64
-            tensor = True
-        else:
-            xyzs = np.asarray(xyzs)
-            if xyzs.dtype != np.float32:
-                xyzs = xyzs.astype(np.float64, copy=False)
-            xyzs = np.ascontiguousarray(xyzs)
-            code = dtype_code(xyzs.dtype)
-            tensor = False
+    @staticmethod
+    def _records_in(space, xyzs):
+        """xyzs [F, P, kn, 4] in `space` -> (array, dtype code, F, P, kn)."""
+        xyzs, code = space.floats(xyzs, "joints")
         if len(xyzs.shape) != 4 or xyzs.shape[-1] != 4:
             raise ValueError(f"xyzs must be [F, P, kn, 4] records (got shape {tuple(xyzs.shape)})")
         F, P, kn, _ = (int(v) for v in xyzs.shape)
-        return xyzs, tensor, F, P, kn, code
+        return xyzs, code, F, P, kn
 
     def _reproject_status(self, rc, where):
         if rc == ERR_BAD_ARG:
@@ -341,19 +397,11 @@ class Context:
         asynchronously on `stream`, default torch's current one) -> pix [F, C, P, kn, 3] = (u, v, score) in every camera, the
         layout of kpts; (0, 0, 0) where the record is missing, the point is behind the camera or the pixel is not finite.
         raw: pixels on the raw frame (set_distortion first).  dtype: of pix, float32 or float64 (default: that of xyzs)."""
-        xyzs, tensor, F, P, kn, code = self._records_in(xyzs, "Context.reproject")
-        flags = REPROJECT_RAW if raw else 0
-        if tensor:
-            import torch
-            pdt = xyzs.dtype if dtype is None else (torch.float32 if _float_code(dtype) == F32 else torch.float64)
-            pix = torch.empty((F, self.C, P, kn, 3), dtype=pdt, device=xyzs.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(xyzs.device).cuda_stream
-            rc = self.L.snowtri_reproject(self.handle, F, P, kn, ct.c_void_p(xyzs.data_ptr()), code, flags, ct.c_void_p(pix.data_ptr()),
-                                          F32 if pdt == torch.float32 else F64, DEVICE, ct.c_void_p(stream) if stream else None)
-        else:
-            pix = np.empty((F, self.C, P, kn, 3), dtype=xyzs.dtype if dtype is None else (np.float32 if _float_code(dtype) == F32 else np.float64))
-            rc = self.L.snowtri_reproject(self.handle, F, P, kn, ptr(xyzs), code, flags, ptr(pix), dtype_code(pix.dtype), HOST, None)
+        space = Space("Context.reproject", xyzs, stream=stream)
+        xyzs, code, F, P, kn = self._records_in(space, xyzs)
+        pcode = code if dtype is None else _float_code(dtype)
+        pix = space.empty((F, self.C, P, kn, 3), "float32" if pcode == F32 else "float64")
+        rc = self.L.snowtri_reproject(self.handle, F, P, kn, ptr(xyzs), code, REPROJECT_RAW if raw else 0, ptr(pix), pcode, *space.tail())
         self._reproject_status(rc, "snowtri_reproject")
         return pix
 
@@ -362,44 +410,17 @@ class Context:
         (cost_sum [F, C, P, Pmax] float64 px^2, cost_n int32): per 3D person and detection the summed squared pixel distance over the
         joints whose projection is valid and whose detection counts, and how many those are.  Host arrays, or contiguous CUDA tensors
         (all of them) used in place and asynchronously on `stream`.  raw: compared on the raw frame (set_distortion first)."""
-        xyzs, tensor, F, P, kn, code = self._records_in(xyzs, "Context.reproject_cost")
-        flags = REPROJECT_RAW if raw else 0
-        if hasattr(kpts, "is_cuda") != tensor or (n_persons is not None and hasattr(n_persons, "is_cuda") != tensor):
-            raise ValueError("Context.reproject_cost takes host arrays or CUDA tensors, not a mixture")
+        space = Space("Context.reproject_cost", xyzs, kpts, n_persons, stream=stream)
+        xyzs, code, F, P, kn = self._records_in(space, xyzs)
         if len(kpts.shape) != 5 or tuple(kpts.shape[:2]) != (F, self.C) or tuple(kpts.shape[3:]) != (kn, 3):
             raise ValueError(f"kpts must be [F={F}, C={self.C}, Pmax, kn={kn}, 3] (got shape {tuple(kpts.shape)})")
+        kpts, kcode = space.floats(kpts, "keypoints")
         Pmax = int(kpts.shape[2])
-        if tensor:
-            import torch
-            if kpts.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"snowtri supports float32/float64 keypoints, not {kpts.dtype}")
-            if not kpts.is_cuda or not kpts.is_contiguous() or kpts.device != xyzs.device:
-                raise ValueError("kpts must be a contiguous CUDA tensor on the device of xyzs")
-            if n_persons is not None and (n_persons.dtype != torch.int32 or not n_persons.is_contiguous() or n_persons.device != xyzs.device
-                                          or tuple(n_persons.shape) != (F, self.C)):
-                raise ValueError("n_persons must be a contiguous int32 CUDA tensor [F, C] on the device of xyzs")
-            cs = torch.empty((F, self.C, P, Pmax), dtype=torch.float64, device=xyzs.device)
-            cn = torch.empty((F, self.C, P, Pmax), dtype=torch.int32, device=xyzs.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(xyzs.device).cuda_stream
-            rc = self.L.snowtri_reproject_cost(self.handle, F, P, kn, ct.c_void_p(xyzs.data_ptr()), code, Pmax, ct.c_void_p(kpts.data_ptr()),
-                                               F32 if kpts.dtype == torch.float32 else F64,
-                                               ct.c_void_p(n_persons.data_ptr()) if n_persons is not None else None,
-                                               float(keypoint_score_threshold), flags, ct.c_void_p(cs.data_ptr()), ct.c_void_p(cn.data_ptr()),
-                                               DEVICE, ct.c_void_p(stream) if stream else None)
-        else:
-            kpts = np.asarray(kpts)
-            if kpts.dtype != np.float32:
-                kpts = kpts.astype(np.float64, copy=False)
-            kpts = np.ascontiguousarray(kpts)
-            if n_persons is not None:
-                n_persons = np.ascontiguousarray(n_persons, dtype=np.int32)
-                if n_persons.shape != (F, self.C):
-                    raise ValueError(f"n_persons must be [F={F}, C={self.C}] (got shape {n_persons.shape})")
-            cs = np.empty((F, self.C, P, Pmax), dtype=np.float64)
-            cn = np.empty((F, self.C, P, Pmax), dtype=np.int32)
-            rc = self.L.snowtri_reproject_cost(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), dtype_code(kpts.dtype), ptr(n_persons),
-                                               float(keypoint_score_threshold), flags, ptr(cs), ptr(cn), HOST, None)
+        if n_persons is not None:
+            n_persons = space.ints(n_persons, (F, self.C), "n_persons")
+        cs, cn = space.empty((F, self.C, P, Pmax), "float64"), space.empty((F, self.C, P, Pmax), "int32")
+        rc = self.L.snowtri_reproject_cost(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons),
+                                           float(keypoint_score_threshold), REPROJECT_RAW if raw else 0, ptr(cs), ptr(cn), *space.tail())
         self._reproject_status(rc, "snowtri_reproject_cost")
         return cs, cn
 
@@ -438,7 +459,7 @@ class Context:
 
     def join(self, stream=None):
         """`stream` (a HIP stream handle, default the null stream) waits for every overlapped call issued since the last join."""
-        check(self.L.snowtri_ctx_join(self.handle, ct.c_void_p(stream) if stream else None), "snowtri_ctx_join")
+        check(self.L.snowtri_ctx_join(self.handle, ptr(stream)), "snowtri_ctx_join")
 
     def last_stream_counts(self):
         """(frames past the association's first launch, frames with an exactly re-done candidate sum, frames left to

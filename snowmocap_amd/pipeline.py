@@ -11,7 +11,6 @@ used for device memory and the stream only.
 """
 from __future__ import annotations
 
-import ctypes as ct
 
 import numpy as np
 
@@ -125,7 +124,7 @@ class TrackPipeline:
             n_persons = torch.from_numpy(np.ascontiguousarray(n_persons, dtype=np.int32)).to(dev)
         F = kpts.shape[0]
         L, h = self.bt.ctx.L, self.bt.ctx.handle
-        st = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.ptr(torch.cuda.current_stream(dev).cuda_stream)
         tri = self.bt.run_torch(kpts, n_persons)
         tracked = None                                   # None: every slot of every frame
         if check:
@@ -151,8 +150,8 @@ class TrackPipeline:
         val = torch.empty((F, self.P, 24), dtype=torch.uint8, device=dev)
 
         def blender_points(x, n, p_out, v_out):
-            _lib.check(L.snowtri_blender_points(h, n, self.kn, ct.c_void_p(x.data_ptr()), _lib.F64, ct.c_void_p(p_out.data_ptr()),
-                                                ct.c_void_p(v_out.data_ptr()), _lib.DEVICE, st), "snowtri_blender_points")
+            _lib.check(L.snowtri_blender_points(h, n, self.kn, _lib.ptr(x), _lib.F64, _lib.ptr(p_out),
+                                                _lib.ptr(v_out), _lib.DEVICE, st), "snowtri_blender_points")
 
         def filter_rows(src, idx, i, sm, pts_s, filled=None, codes=None, desp=None, scodes=None):
             """slot i over the frames idx (the first of them seeds the filters): gather, [despike into desp / scodes,] [fill into
@@ -168,14 +167,14 @@ class TrackPipeline:
                 filled[idx, i] = xi
                 codes[idx, i] = ci
             si = torch.empty_like(xi)
-            _lib.check(L.snowtri_smooth_joint_track(h, T, self.kn, ct.c_void_p(xi.data_ptr()), *fzrd, ct.c_void_p(si.data_ptr()),
+            _lib.check(L.snowtri_smooth_joint_track(h, T, self.kn, _lib.ptr(xi), *fzrd, _lib.ptr(si),
                                                     _lib.DEVICE, st), "snowtri_smooth_joint_track")
             pi = torch.empty((T, 1, 24, 4), dtype=torch.float64, device=dev)
             vi = torch.empty((T, 1, 24), dtype=torch.uint8, device=dev)
             blender_points(si, T, pi, vi)
             qi = torch.empty_like(pi)
-            _lib.check(L.snowtri_blender_smooth(h, T, 1, ct.c_void_p(pi.data_ptr()), ct.c_void_p(vi.data_ptr()),
-                                                _lib.ptr(self.fzr), fzrd[3], ct.c_void_p(qi.data_ptr()), _lib.DEVICE, st),
+            _lib.check(L.snowtri_blender_smooth(h, T, 1, _lib.ptr(pi), _lib.ptr(vi),
+                                                _lib.ptr(self.fzr), fzrd[3], _lib.ptr(qi), _lib.DEVICE, st),
                        "snowtri_blender_smooth")
             sm[idx, i] = si
             pts[idx, i] = pi[:, 0]
@@ -233,12 +232,12 @@ class TrackPipeline:
                 filled, codes = fill_joint_track(self.bt.ctx, src, fill_gaps)
                 src = filled
             sm = torch.empty_like(xyzs)                    # only the points are filtered, the scores copied (triangulation.py:169-184)
-            _lib.check(L.snowtri_smooth_joint_track(h, F, self.P * self.kn, ct.c_void_p(src.data_ptr()), *fzrd, ct.c_void_p(sm.data_ptr()),
+            _lib.check(L.snowtri_smooth_joint_track(h, F, self.P * self.kn, _lib.ptr(src), *fzrd, _lib.ptr(sm),
                                                     _lib.DEVICE, st), "snowtri_smooth_joint_track")
             blender_points(sm, F * self.P, pts, val)
             pts_s = torch.empty_like(pts)
-            _lib.check(L.snowtri_blender_smooth(h, F, self.P, ct.c_void_p(pts.data_ptr()), ct.c_void_p(val.data_ptr()),
-                                                _lib.ptr(self.fzr), fzrd[3], ct.c_void_p(pts_s.data_ptr()), _lib.DEVICE, st),
+            _lib.check(L.snowtri_blender_smooth(h, F, self.P, _lib.ptr(pts), _lib.ptr(val),
+                                                _lib.ptr(self.fzr), fzrd[3], _lib.ptr(pts_s), _lib.DEVICE, st),
                        "snowtri_blender_smooth")
             trk = torch.full((F,), self.P, dtype=torch.int32, device=dev)
         else:
@@ -334,7 +333,7 @@ class ShardedTrackPipeline:
         if T != hi - lo:
             raise ValueError(f"ShardedTrackPipeline: rank {rank} holds {T} frames, shard_bounds gives it [{lo}, {hi})")
         L, h = p.bt.ctx.L, p.bt.ctx.handle
-        st = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.ptr(torch.cuda.current_stream(dev).cuda_stream)
         P, kn, th = p.P, p.kn, p.th
         if T:
             tri = p.bt.run_torch(kpts_local, n_persons_local)
@@ -355,8 +354,8 @@ class ShardedTrackPipeline:
         val = torch.empty((T, P, 24), dtype=torch.uint8, device=dev)
 
         def blender_points(x, n_, p_out, v_out):
-            _lib.check(L.snowtri_blender_points(h, n_, kn, ct.c_void_p(x.data_ptr()), _lib.F64, ct.c_void_p(p_out.data_ptr()),
-                                                ct.c_void_p(v_out.data_ptr()), _lib.DEVICE, st), "snowtri_blender_points")
+            _lib.check(L.snowtri_blender_points(h, n_, kn, _lib.ptr(x), _lib.F64, _lib.ptr(p_out),
+                                                _lib.ptr(v_out), _lib.DEVICE, st), "snowtri_blender_points")
 
         if not (bits & 2):
             # every frame of every rank carries all P slots: the whole block at once

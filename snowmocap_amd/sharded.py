@@ -636,7 +636,6 @@ def smooth_track_sharded(x_local, f=2, z=0.75, r=0, delta_time=1 / 30, group=Non
     F_total (optional): the length of the whole track -- the block is then checked against shard_bounds and "this block
     starts the track" is derived from it instead of assumed for rank 0.  first (optional, without F_total): says it outright --
     for blocks that are NOT shard_bounds blocks, e.g. the frames of a block that carry one person slot (ShardedTrackPipeline)."""
-    import ctypes as ct
     import torch
     import torch.distributed as dist
     from . import _lib
@@ -651,23 +650,23 @@ def smooth_track_sharded(x_local, f=2, z=0.75, r=0, delta_time=1 / 30, group=Non
     for d in x_local.shape[1:]:
         n *= int(d)
     ctx = ctx or _lib.scratch_context(x_local.device.index)     # scratch and kernels on the GPU that holds the shard
-    stream = ct.c_void_p(torch.cuda.current_stream(x_local.device).cuda_stream)
+    stream = _lib.ptr(torch.cuda.current_stream(x_local.device).cuda_stream)
     L = ctx.L
     fzrd = (float(f), float(z), float(r), float(delta_time))
 
     def reduce_fn(x, is_first, payload):
-        _lib.check(L.snowtri_smooth_shard_reduce(ctx.handle, int(x.shape[0]), n, ct.c_void_p(x.data_ptr()), 1 if is_first else 0, *fzrd,
-                                                 ct.c_void_p(payload.data_ptr()), stream), "snowtri_smooth_shard_reduce")
+        _lib.check(L.snowtri_smooth_shard_reduce(ctx.handle, int(x.shape[0]), n, _lib.ptr(x), 1 if is_first else 0, *fzrd,
+                                                 _lib.ptr(payload), stream), "snowtri_smooth_shard_reduce")
 
     def combine_fn(allp, rk, start):
         # the entering state of this shard from the gathered carries, ON the device and the stream (k_smooth_combine: no host
         # round trip between the all-gather and the fix; combine_carries above is its host twin)
-        _lib.check(L.snowtri_smooth_shard_combine(ctx.handle, world, rk, n, ct.c_void_p(allp.data_ptr()), *fzrd,
-                                                  ct.c_void_p(start.data_ptr()), _lib.DEVICE, stream), "snowtri_smooth_shard_combine")
+        _lib.check(L.snowtri_smooth_shard_combine(ctx.handle, world, rk, n, _lib.ptr(allp), *fzrd,
+                                                  _lib.ptr(start), _lib.DEVICE, stream), "snowtri_smooth_shard_combine")
 
     def scan_fn(x, is_first, start, y):
-        _lib.check(L.snowtri_smooth_shard_scan(ctx.handle, int(x.shape[0]), n, ct.c_void_p(x.data_ptr()), 1 if is_first else 0,
-                                               ct.c_void_p(start.data_ptr()), *fzrd, ct.c_void_p(y.data_ptr()), stream), "snowtri_smooth_shard_scan")
+        _lib.check(L.snowtri_smooth_shard_scan(ctx.handle, int(x.shape[0]), n, _lib.ptr(x), 1 if is_first else 0,
+                                               _lib.ptr(start), *fzrd, _lib.ptr(y), stream), "snowtri_smooth_shard_scan")
 
     return smooth_exchange2(x_local, reduce_fn, combine_fn, scan_fn, group=group, first=first)
 
@@ -703,7 +702,6 @@ def blender_smooth_sharded(pts_local, val_local, fzr, delta_time=1 / 30, group=N
     track sharded in frame order.  Returns the smoothed block [T_r, P, 24, 4] = the rows snowtri_blender_smooth returns for
     these frames on the whole track (to rounding: the carries are propagated in closed form).  Two small all-gathers
     (2n and 4n + 1 doubles per rank, n = P * 96); the track itself never moves."""
-    import ctypes as ct
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -718,33 +716,33 @@ def blender_smooth_sharded(pts_local, val_local, fzr, delta_time=1 / 30, group=N
             raise ValueError(f"blender_smooth_sharded: rank {rank} holds {T} frames, shard_bounds gives it [{lo}, {hi})")
         first = lo == 0 and hi > lo
     ctx = ctx or _lib.scratch_context(pts_local.device.index)
-    stream = ct.c_void_p(torch.cuda.current_stream(pts_local.device).cuda_stream)
+    stream = _lib.ptr(torch.cuda.current_stream(pts_local.device).cuda_stream)
     L = ctx.L
     fzr = np.ascontiguousarray(fzr, dtype=np.float64).reshape(24, 3)
     dt = float(delta_time)
 
     def last_fn(p, v, payload):
-        _lib.check(L.snowtri_blender_hold_shard_last(ctx.handle, int(p.shape[0]), P, ct.c_void_p(p.data_ptr()), ct.c_void_p(v.data_ptr()),
-                                                     ct.c_void_p(payload.data_ptr()), stream), "snowtri_blender_hold_shard_last")
+        _lib.check(L.snowtri_blender_hold_shard_last(ctx.handle, int(p.shape[0]), P, _lib.ptr(p), _lib.ptr(v),
+                                                     _lib.ptr(payload), stream), "snowtri_blender_hold_shard_last")
 
     def apply_fn(allp, rk, p, v, held):
-        _lib.check(L.snowtri_blender_hold_shard_apply(ctx.handle, world, rk, int(p.shape[0]), P, ct.c_void_p(p.data_ptr()),
-                                                      ct.c_void_p(v.data_ptr()), ct.c_void_p(allp.data_ptr()), ct.c_void_p(held.data_ptr()),
+        _lib.check(L.snowtri_blender_hold_shard_apply(ctx.handle, world, rk, int(p.shape[0]), P, _lib.ptr(p),
+                                                      _lib.ptr(v), _lib.ptr(allp), _lib.ptr(held),
                                                       stream), "snowtri_blender_hold_shard_apply")
 
     held = hold_exchange(pts_local, val_local, last_fn, apply_fn, group=group)
 
     def reduce_fn(x, is_first, payload):
-        _lib.check(L.snowtri_blender_smooth_shard_reduce(ctx.handle, int(x.shape[0]), P, ct.c_void_p(x.data_ptr()), 1 if is_first else 0,
-                                                         _lib.ptr(fzr), dt, ct.c_void_p(payload.data_ptr()), stream), "snowtri_blender_smooth_shard_reduce")
+        _lib.check(L.snowtri_blender_smooth_shard_reduce(ctx.handle, int(x.shape[0]), P, _lib.ptr(x), 1 if is_first else 0,
+                                                         _lib.ptr(fzr), dt, _lib.ptr(payload), stream), "snowtri_blender_smooth_shard_reduce")
 
     def combine_fn(allp, rk, start):
-        _lib.check(L.snowtri_blender_smooth_shard_combine(ctx.handle, world, rk, P, ct.c_void_p(allp.data_ptr()), _lib.ptr(fzr), dt,
-                                                          ct.c_void_p(start.data_ptr()), stream), "snowtri_blender_smooth_shard_combine")
+        _lib.check(L.snowtri_blender_smooth_shard_combine(ctx.handle, world, rk, P, _lib.ptr(allp), _lib.ptr(fzr), dt,
+                                                          _lib.ptr(start), stream), "snowtri_blender_smooth_shard_combine")
 
     def scan_fn(x, is_first, start, y):
-        _lib.check(L.snowtri_blender_smooth_shard_scan(ctx.handle, int(x.shape[0]), P, ct.c_void_p(x.data_ptr()), 1 if is_first else 0,
-                                                       ct.c_void_p(start.data_ptr()), _lib.ptr(fzr), dt, ct.c_void_p(y.data_ptr()), stream),
+        _lib.check(L.snowtri_blender_smooth_shard_scan(ctx.handle, int(x.shape[0]), P, _lib.ptr(x), 1 if is_first else 0,
+                                                       _lib.ptr(start), _lib.ptr(fzr), dt, _lib.ptr(y), stream),
                    "snowtri_blender_smooth_shard_scan")
 
     y = smooth_exchange2(held, reduce_fn, combine_fn, scan_fn, group=group, first=first)

@@ -21,8 +21,6 @@ between calls, so a recording can be processed in consecutive frame blocks.
 """
 from __future__ import annotations
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
@@ -165,10 +163,6 @@ def bridge_track_ids(track_id, max_gap):
     return tid
 
 
-def _vp(x):
-    return ct.c_void_p(x) if x else None
-
-
 class PersonTracker:
     """The tracker on the GPU.  ctx_or_rig: a _lib.Context to share (e.g. BatchTriangulator.ctx), a (K, R, t) rig, or None
     for the rig-less scratch context of the current device.  The state lives where the last call's data lived (device
@@ -210,73 +204,51 @@ class PersonTracker:
             raise ValueError(f"{where}: {self.ctx.L.snowtri_last_error().decode()}")
         _lib.check(rc, where)
 
-    def run_host(self, xyzs, count, gather=True, carry=True):
-        """NumPy in / NumPy out (staged, synchronous).  carry=False: a fresh start that is not saved (state = NULL)."""
-        xyzs = np.ascontiguousarray(xyzs)
-        if xyzs.dtype != np.float32:
-            xyzs = np.ascontiguousarray(xyzs, dtype=np.float64)
-        F, P, kn, four = xyzs.shape
-        assert four == 4
-        count = np.ascontiguousarray(count, dtype=np.int32).reshape(F)
-        L, h, code = self.ctx.L, self.ctx.handle, _lib.dtype_code(xyzs.dtype)
-        state = None
-        if carry:
-            if self._state is None:
-                self._state = np.zeros(self.state_nbytes, dtype=np.uint8)
-            elif not isinstance(self._state, np.ndarray):
-                self._state = self._state.cpu().numpy()
-            state = self._state
-        out = dict(slot_of=np.empty((F, P), dtype=np.int32), person_of=np.empty((F, self.S), dtype=np.int32),
-                   track_id=np.empty((F, self.S), dtype=np.int32), flags=np.empty(F, dtype=np.uint32))
-        rc = L.snowtri_track_persons(h, F, P, kn, _lib.ptr(xyzs), code, _lib.ptr(count), self.S, self.cpi, self.gate, self.max_missed,
+    def _run(self, space, xyzs, count, gather, state_in):
+        """One call in `space`.  state_in: None (state = NULL), or a function that gives the state blob in that space; it is asked only
+        once the arguments have passed their checks, so a refused call leaves the state where it was."""
+        xyzs, code = space.floats(xyzs, "joints")
+        if len(xyzs.shape) != 4 or xyzs.shape[-1] != 4:
+            raise ValueError(f"xyzs must be [F, Pout_max, kn, 4] records (got shape {tuple(xyzs.shape)})")
+        F, P, kn, _ = (int(v) for v in xyzs.shape)
+        count = space.ints(count, (F,), "count")
+        state = state_in() if state_in else None
+        L, h, S, tail = self.ctx.L, self.ctx.handle, self.S, space.tail()
+        out = dict(slot_of=space.empty((F, P), "int32"), person_of=space.empty((F, S), "int32"), track_id=space.empty((F, S), "int32"),
+                   flags=space.empty((F,), "flags"))
+        rc = L.snowtri_track_persons(h, F, P, kn, _lib.ptr(xyzs), code, _lib.ptr(count), S, self.cpi, self.gate, self.max_missed,
                                      _lib.ptr(state), _lib.ptr(out["slot_of"]), _lib.ptr(out["person_of"]), _lib.ptr(out["track_id"]),
-                                     _lib.ptr(out["flags"]), _lib.HOST, None)
+                                     _lib.ptr(out["flags"]), *tail)
         if rc:
             self._raise(rc, "snowtri_track_persons")
         if gather:
-            out["xyzs_tracked"] = np.empty((F, self.S, kn, 4), dtype=xyzs.dtype)
-            rc = L.snowtri_track_gather(h, F, P, kn, _lib.ptr(xyzs), code, self.S, _lib.ptr(out["person_of"]),
-                                        _lib.ptr(out["xyzs_tracked"]), _lib.HOST, None)
+            out["xyzs_tracked"] = space.empty((F, S, kn, 4), "float32" if code == _lib.F32 else "float64")
+            rc = L.snowtri_track_gather(h, F, P, kn, _lib.ptr(xyzs), code, S, _lib.ptr(out["person_of"]), _lib.ptr(out["xyzs_tracked"]), *tail)
             if rc:
                 self._raise(rc, "snowtri_track_gather")
         return out
 
+    def run_host(self, xyzs, count, gather=True, carry=True):
+        """NumPy in / NumPy out (staged, synchronous).  carry=False: a fresh start that is not saved (state = NULL)."""
+        def state():
+            if self._state is None:
+                self._state = np.zeros(self.state_nbytes, dtype=np.uint8)
+            elif not isinstance(self._state, np.ndarray):
+                self._state = self._state.cpu().numpy()
+            return self._state
+        return self._run(_lib.Space("PersonTracker.run_host"), xyzs, np.reshape(count, -1), gather, state if carry else None)
+
     def run_torch(self, xyzs, count, gather=True, carry=True, stream=None):
         """CUDA(=HIP) tensors in / out, asynchronous on `stream` (default: torch's current stream); no host read."""
         import torch
-        assert xyzs.is_cuda and xyzs.is_contiguous() and count.is_cuda and count.is_contiguous() and count.dtype == torch.int32
-        F, P, kn, four = xyzs.shape
-        assert four == 4 and count.numel() == F
-        if xyzs.dtype == torch.float32:
-            code = _lib.F32
-        elif xyzs.dtype == torch.float64:
-            code = _lib.F64
-        else:
-            raise TypeError(f"snowtri supports float32/float64 joints, not {xyzs.dtype}")
-        dev = xyzs.device
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        L, h = self.ctx.L, self.ctx.handle
-        state = None
-        if carry:
+        space = _lib.Space("PersonTracker.run_torch", xyzs, count, stream=stream)
+        if space.device is None:
+            raise ValueError("PersonTracker.run_torch takes contiguous CUDA tensors (run_host takes NumPy arrays)")
+
+        def state():
             if self._state is None:
-                self._state = torch.zeros(self.state_nbytes, dtype=torch.uint8, device=dev)
+                self._state = torch.zeros(self.state_nbytes, dtype=torch.uint8, device=space.device)
             elif isinstance(self._state, np.ndarray):
-                self._state = torch.from_numpy(self._state).to(dev)
-            state = self._state
-        i32 = dict(dtype=torch.int32, device=dev)
-        out = dict(slot_of=torch.empty((F, P), **i32), person_of=torch.empty((F, self.S), **i32),
-                   track_id=torch.empty((F, self.S), **i32), flags=torch.empty((F,), **i32))
-        rc = L.snowtri_track_persons(h, F, P, kn, _vp(xyzs.data_ptr()), code, _vp(count.data_ptr()), self.S, self.cpi, self.gate,
-                                     self.max_missed, _vp(state.data_ptr()) if state is not None else None,
-                                     _vp(out["slot_of"].data_ptr()), _vp(out["person_of"].data_ptr()), _vp(out["track_id"].data_ptr()),
-                                     _vp(out["flags"].data_ptr()), _lib.DEVICE, _vp(stream))
-        if rc:
-            self._raise(rc, "snowtri_track_persons")
-        if gather:
-            out["xyzs_tracked"] = torch.empty((F, self.S, kn, 4), dtype=xyzs.dtype, device=dev)
-            rc = L.snowtri_track_gather(h, F, P, kn, _vp(xyzs.data_ptr()), code, self.S, _vp(out["person_of"].data_ptr()),
-                                        _vp(out["xyzs_tracked"].data_ptr()), _lib.DEVICE, _vp(stream))
-            if rc:
-                self._raise(rc, "snowtri_track_gather")
-        return out
+                self._state = torch.from_numpy(self._state).to(space.device)
+            return self._state
+        return self._run(space, xyzs, count.view(-1) if count.is_contiguous() else count, gather, state if carry else None)

@@ -147,7 +147,7 @@ def Human_Triangulation_Condense(result, condense_distance_tol=0.1, condense_per
     oxyz, oks, ops = oblk[:pout * knn * 3].reshape(pout, knn, 3), oblk[pout * knn * 3:pout * knn * 4].reshape(pout, knn), oblk[pout * knn * 4:]
     cnt = np.zeros(1, dtype=np.int32)
     obase = oblk.ctypes.data
-    p_xyz, p_ks, p_ps, p_cnt = ct.c_void_p(obase), ct.c_void_p(obase + 8 * pout * knn * 3), ct.c_void_p(obase + 8 * pout * knn * 4), _lib.ptr(cnt)
+    p_xyz, p_ks, p_ps, p_cnt = _lib.ptr(obase), _lib.ptr(obase + 8 * pout * knn * 3), _lib.ptr(obase + 8 * pout * knn * 4), _lib.ptr(cnt)
     rc = _lib.ERR_BAD_ARG
     resident = _Resident.match(points, scores)
     if resident is not None:        # the unmodified result of Human_Triangulation: its candidates are still on the device
