@@ -590,6 +590,58 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
                            double keypoint_score_threshold, uint32_t flags, double *cost_sum, int32_t *cost_n, int memspace,
                            void *stream);
 
+/* Refinement: joint records of ANY route moved to a local minimum of their weighted reprojection error, in pixels (no reference
+ * counterpart).  Every route ends in a closed-form estimate -- the score-weighted mean of two-ray midpoints (SNOWTRI_PAIRWISE), the
+ * minimiser of an algebraic error (the DLT methods) -- and none of them minimises the distance between the joint's projections and
+ * the detections, which is the quantity the detector's noise lives in and the one snowtri_reproject_cost reports.  A few
+ * Gauss-Newton steps from the closed-form point on a 3 x 3 system per joint find the maximum-likelihood point under pixel noise.
+ * The rule, in fp64 throughout (PD = positive definite), per record (f, p, j) of xyzs [F][P][kn][4], X0 = its (x, y, z), with the
+ * keypoints kpts [F][C][Pmax][kn][3] ON THE UNDISTORTED FRAME:
+ *   1. The view set V, fixed once at X0.  Camera c is in V iff ALL of:
+ *        - its detection q = det_of[f][c][p] satisfies 0 <= q < n_persons[f][c] (det_of NULL: q = p, which requires P <= Pmax;
+ *          n_persons NULL: Pmax everywhere; an n_persons above Pmax counts as Pmax);
+ *        - the observation (u, v, s) = kpts[f][c][q][j] has finite u, v and not (s < keypoint_score_threshold);
+ *        - bit c of views[f][p][j] is set, when `views` is given (the mask snowtri_triangulate_robust writes: refine over the
+ *          views the robust method kept);
+ *        - the projection of X0 into c is VALID by rule 4 of "Reprojection" (measured record, pc2 > 0, finite pixel).
+ *      Weight w_c = 1, or w_c = s with SNOWTRI_REFINE_SCORE_WEIGHTS.
+ *   2. A missing record is copied bit for bit (code SNOWTRI_REFINE_MISSING).  A measured record with |V| < 2 is copied bit for bit
+ *      (SNOWTRI_REFINE_FEW_VIEWS).
+ *   3. Cost E(X) = sum over c in V of w_c ((u_c(X) - u_c)^2 + (v_c(X) - v_c)^2) with the undistorted projection of rules 1 and 3 of
+ *      "Reprojection".  Analytic 2 x 3 Jacobian: dx = (R^T row 0 - x R^T row 2) / pc2, dy likewise, du = fx dx + s dy, dv = fy dy.
+ *   4. At most `iters` steps (1..16): H = sum w J^T J, g = sum w J^T r; H d = -g by a 3 x 3 LDL^T; a pivot that is not finite or not
+ *      > 0 ends the record's iteration.  The trial X + d is ACCEPTED iff every view of V is valid at it and E(X + d) < E(X),
+ *      strictly.  A rejected trial ends the record's iteration (no damping, no step halving).  So the output cost never exceeds the
+ *      input cost, and the iteration stops by itself at the rounding floor of E.
+ *   5. Output record = (X, the input score), rounded once to xyz_dtype; a record no step moved is the input's bits.  Code
+ *      SNOWTRI_REFINE_KEPT if no step was accepted, SNOWTRI_REFINE_MOVED otherwise.
+ * cost [F][P][kn][2] float64 (may be NULL): E at the input and at the output, (0, 0) for copied records.  codes [F][P][kn] uint8
+ * (may be NULL).  snowmocap_amd/refine.py::refine_joints_reference is this rule in NumPy, plain operations in this order; the kernel
+ * (snowmocap_amd/csrc/snowtri_refine.hpp: k_refine, one lane per record) fixes V with project_record itself and forms E in exactly
+ * these plain operations -- E at a given point is the NumPy rule's bit for bit, so the cost a caller recomputes that way never rises
+ * either, even at exact detections where E is nothing but rounding; only H and g use fused multiply-adds -- and reaches the
+ * same minimum to the rule's own floor -- strict decrease of E stops resolving a step d once d^T H d < eps E -- which
+ * tests/refine_cases.py measures against a 50-digit minimiser.  A record's output bits depend on its own record, its own
+ * observations and the rig only: not on F, its place in the launch, or how a batch is cut into calls.
+ *
+ * Refusals as for snowtri_reproject_cost (SNOWTRI_ERR_BAD_ARG, snowtri_last_error() names the argument; nothing is enqueued or
+ * written), and: iters outside 1..16, an unknown flag bit, more than 32 cameras, det_of == NULL with P > Pmax, out_xyzs overlapping
+ * xyzs other than exactly (out_xyzs == xyzs refines in place).  F * P * kn <= (2^31 - 1) * 256 records.  F == 0 is SNOWTRI_OK and
+ * looks at no pointer.  SNOWTRI_DEVICE: asynchronous on `stream`, no host read, no allocation, no internal stream.  SNOWTRI_HOST:
+ * staged and synchronous.
+ * NOT offered: refinement on the raw frame (undistort first: snowtri_undistort_keypoints is an exact inverse); a robust loss
+ * (Huber / IRLS: outliers are the business of SNOWTRI_DLT_ROBUST's mask, passed as `views`); more than 32 cameras. */
+#define SNOWTRI_REFINE_SCORE_WEIGHTS 1u /* flags: w_c = the observation's score instead of 1 */
+#define SNOWTRI_REFINE_MISSING 0
+#define SNOWTRI_REFINE_FEW_VIEWS 1
+#define SNOWTRI_REFINE_KEPT 2
+#define SNOWTRI_REFINE_MOVED 3
+int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+                          const void *kpts, int kpts_dtype, const int32_t *n_persons /* [F][C] or NULL */,
+                          const int32_t *det_of /* [F][C][P] or NULL */, const uint32_t *views /* [F][P][kn] or NULL */,
+                          double keypoint_score_threshold, int32_t iters, uint32_t flags, void *out_xyzs /* xyz_dtype; may be xyzs itself */,
+                          double *cost /* or NULL */, uint8_t *codes /* or NULL */, int memspace, void *stream);
+
 /* Measurement aid: HIP-event time (ms) of the kernels launched by the LAST
  * snowtri_triangulate_condense call on this context, measured on the stream they ran on
  * (blocks until they finish).  kernel_ms[0] = dominant fused kernel, [1] = everything else. */

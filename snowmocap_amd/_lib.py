@@ -22,7 +22,9 @@ FLAG_SINGULAR, FLAG_OVERFLOW, FLAG_FASTPATH = 1, 2, 4
 DESPIKE_MARK, DESPIKE_REPLACE = 0, 1                       # snowtri_despike_joint_track: mode
 DESPIKE_KEPT, DESPIKE_SPIKE, DESPIKE_MISSING, DESPIKE_UNSUPPORTED = 0, 1, 2, 3   # ... and its codes
 REPROJECT_RAW = 1              # snowtri_reproject / snowtri_reproject_cost: flags -- pixels on the raw (distorted) frame
-CALL_NO_ZERO_FILL = 1          # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
+REFINE_SCORE_WEIGHTS = 1       # snowtri_refine_joints: flags -- a view weighs its observation's score
+REFINE_MISSING, REFINE_FEW_VIEWS, REFINE_KEPT, REFINE_MOVED = 0, 1, 2, 3   # ... and its codes
+CALL_NO_ZERO_FILL = 1         # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
 TEST_LIB_PATH = os.path.join(_HERE, "libsnowtri_dbg.so")   # -DSNOWTRI_DEBUG_BOUNDS -DSNOWTRI_TEST_KNOBS (tests only: use_library)
 
 
@@ -139,6 +141,8 @@ _SIGNATURES = {
     "snowtri_reproject": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_uint32, _c_p, ct.c_int, ct.c_int, _c_p]),
     "snowtri_reproject_cost": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p,
                                           ct.c_double, ct.c_uint32, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_refine_joints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
+                                         ct.c_double, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_last_kernel_ms": (ct.c_int, [_c_p, ct.POINTER(ct.c_float * 2)]),
     "snowtri_set_timing": (ct.c_int, [_c_p, ct.c_int]),
     "snowtri_timing_collect": (ct.c_int, [_c_p, _c_p, ct.c_int32]),
@@ -423,6 +427,50 @@ class Context:
                                            float(keypoint_score_threshold), REPROJECT_RAW if raw else 0, ptr(cs), ptr(cn), *space.tail())
         self._reproject_status(rc, "snowtri_reproject_cost")
         return cs, cn
+
+    def refine_joints(self, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4,
+                      score_weights=False, diagnostics=False, out=None, stream=None):
+        """Joint records xyzs [F, P, kn, 4] moved to a local minimum of their reprojection error against the detections kpts
+        [F, C, Pmax, kn, 3] on the undistorted frame (include/snowtri.h, "Refinement"; at most `iters` Gauss-Newton steps, a record's
+        cost never rises, scores untouched).  det_of [F, C, P]: the detection of camera c that shows person p (match_detections'
+        int64 is handed on as int32; -1: none; None: detection p).  n_persons [F, C] int32 or None.  views [F, P, kn]: bit c = camera
+        c may be used (the uint32 / torch int32 mask of DLT_ROBUST's diagnostics; None: every camera).  score_weights: a view weighs
+        its observation's score instead of 1.  Host arrays, or contiguous CUDA tensors (all of them) used in place and
+        asynchronously on `stream`.  out: xyzs itself refines in place (default: a new array).
+        -> the refined records, or (records, cost [F, P, kn, 2] float64: E before and after, codes [F, P, kn] uint8: REFINE_*)
+        with diagnostics=True."""
+        space = Space("Context.refine_joints", xyzs, kpts, n_persons, det_of, views, stream=stream)
+        xyzs, code, F, P, kn = self._records_in(space, xyzs)
+        if len(kpts.shape) != 5 or tuple(kpts.shape[:2]) != (F, self.C) or tuple(kpts.shape[3:]) != (kn, 3):
+            raise ValueError(f"kpts must be [F={F}, C={self.C}, Pmax, kn={kn}, 3] (got shape {tuple(kpts.shape)})")
+        kpts, kcode = space.floats(kpts, "keypoints")
+        Pmax = int(kpts.shape[2])
+        if int(iters) != iters:
+            raise ValueError(f"iters must be an integer in 1..16 (got {iters})")
+        if n_persons is not None:
+            n_persons = space.ints(n_persons, (F, self.C), "n_persons")
+        if det_of is not None:
+            if space.device is not None and det_of.dtype == space.torch.int64:
+                det_of = det_of.to(space.torch.int32).contiguous()
+            det_of = space.ints(det_of, (F, self.C, P), "det_of")
+        if views is not None:
+            if space.device is None:
+                views = np.ascontiguousarray(views)
+                if views.dtype not in (np.uint32, np.int32) or views.shape != (F, P, kn):
+                    raise ValueError(f"views given to Context.refine_joints must be uint32 of shape {(F, P, kn)} (got {views.dtype} {views.shape})")
+            else:
+                views = space.ints(views, (F, P, kn), "views")
+        if out is None:
+            out = space.empty_like(xyzs)
+        elif out is not xyzs:
+            raise ValueError("out must be None (a new array) or xyzs itself (in place)")
+        cost = space.empty((F, P, kn, 2), "float64") if diagnostics else None
+        codes = space.empty((F, P, kn), "uint8") if diagnostics else None
+        rc = self.L.snowtri_refine_joints(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of), ptr(views),
+                                          float(keypoint_score_threshold), int(iters), REFINE_SCORE_WEIGHTS if score_weights else 0, ptr(out),
+                                          ptr(cost), ptr(codes), *space.tail())
+        self._reproject_status(rc, "snowtri_refine_joints")
+        return (out, cost, codes) if diagnostics else out
 
     def set_timing(self, enabled=True, attach=False):
         """attach: single-kernel calls carry the event pair on their dispatch (the kernel's own begin / end) instead of being bracketed."""

@@ -136,6 +136,7 @@ class BatchTriangulator:
                 self.ctx.handle, F, Pmax, J, ct.c_void_p(kpts.data_ptr()), ct.c_void_p(self._ukpts.data_ptr()),
                 in_code, _lib.DEVICE, ct.c_void_p(stream)), "snowtri_undistort_keypoints")
             kpts = self._ukpts
+        self.last_undistorted_kpts = kpts   # what the kernels of this call read: the caller's tensor, or the undistorted copy of it
         global FUSED_CALLS
         FUSED_CALLS += 1
         if self.diagnostics:

@@ -33,6 +33,7 @@
 #include "snowtri_blender.hpp"
 #include "snowtri_undistort.hpp"
 #include "snowtri_reproject.hpp"
+#include "snowtri_refine.hpp"
 #include "snowtri_track.hpp"
 #include "snowtri_fill.hpp"
 #include "snowtri_despike.hpp"
@@ -2205,6 +2206,94 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
         else LAUNCH_COST(double, double);
     }
 #undef LAUNCH_COST
+    HIP_TRY(hipGetLastError());
+    return sg.end();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------- refinement
+namespace {
+
+template <int CT>
+void launch_refine(int xyz_dtype, int kpts_dtype, dim3 grid, hipStream_t st, int64_t n_rec, int C, int P, int Pmax, int kn, double kthr, int iters,
+                   uint32_t flags, const double *proj, const void *dx, const void *dk, const int32_t *dnp, const int32_t *ddet,
+                   const uint32_t *dviews, void *d_out, double *d_cost, uint8_t *d_codes) {
+#define LAUNCH_REFINE(TX, TK)                                                                                                              \
+    hipLaunchKernelGGL((k_refine<CT, TX, TK>), grid, dim3(kRefineBlock), 0, st, n_rec, C, P, Pmax, kn, kthr, iters, flags, proj, (const TX *)dx, \
+                       (const TK *)dk, dnp, ddet, dviews, (TX *)d_out, d_cost, d_codes)
+    if (xyz_dtype == SNOWTRI_F32) {
+        if (kpts_dtype == SNOWTRI_F32) LAUNCH_REFINE(float, float);
+        else LAUNCH_REFINE(float, double);
+    } else {
+        if (kpts_dtype == SNOWTRI_F32) LAUNCH_REFINE(double, float);
+        else LAUNCH_REFINE(double, double);
+    }
+#undef LAUNCH_REFINE
+}
+
+}  // namespace
+
+extern "C" {
+
+int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
+                          int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                          double keypoint_score_threshold, int32_t iters, uint32_t flags, void *out_xyzs, double *cost, uint8_t *codes,
+                          int memspace, void *stream) {
+    const char *who = "snowtri_refine_joints";
+    if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, 0u, kpts_dtype, memspace)) return rc;
+    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (flags & ~(uint32_t)SNOWTRI_REFINE_SCORE_WEIGHTS) return refuse("unknown flag bit");
+    if (Pmax < 1) return refuse("Pmax < 1");
+    if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
+    if (iters < 1 || iters > kRefineMaxIters) return refuse("iters must lie in 1..16");
+    if (ctx->C > kRefineMaxCams) return refuse("more than 32 cameras (a view set is a 32-bit mask)");
+    if (!det_of && P > Pmax) return refuse("det_of == NULL pairs person p with detection p: P must not exceed Pmax");
+    // one lane per record, 256 per workgroup on a one-dimensional grid; 64-bit element offsets
+    if (F == 0) return SNOWTRI_OK;
+    const int64_t max_rec = (int64_t)0x7fffffff * kRefineBlock, per_frame = (int64_t)P * kn;   // (two int32: no overflow)
+    if (F > max_rec / per_frame) return refuse("F * P * kn must not exceed (2^31 - 1) * 256 records");
+    const int64_t per_view = (int64_t)Pmax * kn, cp = (int64_t)ctx->C * std::max(P, Pmax);
+    if (F > (((int64_t)1 << 56) / per_view) / ctx->C || F > ((int64_t)1 << 56) / cp)
+        return refuse("F * C * Pmax * kn and F * C * P must not exceed 2^56 elements");
+    if (!xyzs || !kpts || !out_xyzs) return refuse("null array (xyzs, kpts or out_xyzs)");
+    const size_t xs = dtype_size(xyz_dtype), ks = dtype_size(kpts_dtype);
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs | (uintptr_t)out_xyzs) & (xs - 1)) || (((uintptr_t)kpts) & (ks - 1)) ||
+                                       (((uintptr_t)n_persons | (uintptr_t)det_of | (uintptr_t)views) & 3u) || (((uintptr_t)cost) & 7u)))
+        return refuse("xyzs, out_xyzs, kpts, n_persons, det_of, views and cost must be aligned to their element size");
+    const int64_t n_rec = F * per_frame;
+    const size_t x_bytes = xs * 4 * (size_t)n_rec, k_bytes = ks * 3 * (size_t)F * ctx->C * (size_t)per_view;
+    // a lane reads its record and writes it at the same place: out_xyzs == xyzs is that; any other overlap lets one lane's store
+    // reach another lane's load
+    if (out_xyzs != xyzs && (uintptr_t)xyzs < (uintptr_t)out_xyzs + x_bytes && (uintptr_t)out_xyzs < (uintptr_t)xyzs + x_bytes)
+        return refuse("out_xyzs must be xyzs itself or not overlap it");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const void *dx = xyzs, *dk = kpts;
+    const int32_t *dnp = n_persons, *ddet = det_of;
+    const uint32_t *dviews = views;
+    void *d_out = out_xyzs;
+    double *d_cost = cost;
+    uint8_t *d_codes = codes;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, x_bytes);
+    sg.in(&dk, k_bytes);
+    sg.in(&dnp, sizeof(int32_t) * (size_t)F * ctx->C);
+    sg.in(&ddet, sizeof(int32_t) * (size_t)F * ctx->C * P);
+    sg.in(&dviews, sizeof(uint32_t) * (size_t)n_rec);
+    sg.out(&d_out, x_bytes);
+    sg.out(&d_cost, sizeof(double) * 2 * (size_t)n_rec);
+    sg.out(&d_codes, (size_t)n_rec);
+    if (int rc = sg.begin()) return rc;
+    // (a DEVICE call with out_xyzs == xyzs passes one pointer twice: the kernel declares neither of the two restrict)
+    const dim3 grid((unsigned)((n_rec + kRefineBlock - 1) / kRefineBlock));
+    const int C = ctx->C;
+#define REFINE_ARGS xyz_dtype, kpts_dtype, grid, st, n_rec, C, (int)P, (int)Pmax, (int)kn, keypoint_score_threshold, (int)iters, flags, \
+                    (const double *)ctx->dProj, dx, dk, dnp, ddet, dviews, d_out, d_cost, d_codes
+    if (C == 4) launch_refine<4>(REFINE_ARGS);
+    else if (C == 8) launch_refine<8>(REFINE_ARGS);
+    else launch_refine<0>(REFINE_ARGS);
+#undef REFINE_ARGS
     HIP_TRY(hipGetLastError());
     return sg.end();
 }

@@ -19,6 +19,7 @@ from .batch import BatchTriangulator
 from .blender import CONTROL_POINT_NAMES, _WIDTH
 from .despike import DESPIKE_MARK, DESPIKE_MISSING, DESPIKE_REPLACE, DESPIKE_UNSUPPORTED, despike_args, despike_joint_track
 from .fill import FILL_MISSING, MAX_GAP, fill_joint_track
+from .refine import refine_args
 
 
 class TrackPipeline:
@@ -40,7 +41,7 @@ class TrackPipeline:
         self.bt.close()
 
     def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0, despike=None,
-            reproject=None):
+            reproject=None, refine=None):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -85,8 +86,17 @@ class TrackPipeline:
         this gate (an RMS pixel distance) and the pipeline's keypoint_score_threshold, reproject.view_residuals on k_reproject.
         Adds det_of [F, C, P] (the detection of camera c that belongs to person p of xyzs, -1: none), shared [F, C, P] (persons of one
         view that chose the same detection: the match is not one-to-one), view_rms [F, C, P] (px, NaN without a match) and view_n.
-        None (the default): off, nothing changes and no key is added."""
-        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike)
+        None (the default): off, nothing changes and no key is added.
+        refine=iters or (iters, gate_px, score_weights): the triangulated joints are moved to a local minimum of their reprojection
+        error (refine.refine_joints: at most `iters` Gauss-Newton steps, a joint's cost never rises, scores untouched) right after
+        triangulation, before tracking, despiking, filling and smoothing, so everything downstream -- xyzs included -- is made of
+        the refined records.  Three steps on the UNDISTORTED keypoints: reprojection_cost of the triangulated persons against every
+        detection, reproject.match_detections with gate_px (default 6.0, the default of the robust gate; score_weights default
+        False) to find the detection of each camera that shows each person, refine_joints with that det_of and the pipeline's
+        keypoint_score_threshold.  With D the triangulator's own undistorted copy of the keypoints is reused (no second k_undistort
+        pass).  Adds refine_codes [F, P, kn] (uint8, refine.REFINE_*) and refine_cost [F, P, kn, 2] (px^2 before and after), both in
+        the triangulation's list order.  None (the default): off, nothing changes and no key is added."""
+        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, refine_args(refine))
         if reproject is not None:
             self._add_reprojection(res, kpts, n_persons, float(reproject))
         return res
@@ -113,7 +123,22 @@ class TrackPipeline:
         pix = ctx.reproject(xyzs, raw=raw, dtype=torch.float64)
         _, res["view_rms"], res["view_n"] = view_residuals(pix, kpts, res["det_of"], thr)
 
-    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike):
+    def _refine(self, xyzs, n_persons, rfn):
+        """run(refine=...): the triangulated records against the undistorted keypoints of the call that made them
+        -> (refined records, cost, codes)."""
+        from .reproject import match_detections
+        iters, gate_px, score_weights = rfn
+        ukpts = self.bt.last_undistorted_kpts
+        if int(ukpts.shape[3]) != self.kn:                # the joints the triangulation kept are the first kn of a detection
+            ukpts = ukpts[:, :, :, :self.kn].contiguous()
+        ctx, thr = self.bt.ctx, float(self.th["keypoint_score_threshold"])
+        xyzs = xyzs.contiguous()
+        cost_sum, cost_n = ctx.reproject_cost(xyzs, ukpts, n_persons=n_persons, keypoint_score_threshold=thr)
+        det_of, _ = match_detections(cost_sum, cost_n, gate_px)
+        return ctx.refine_joints(xyzs, ukpts, det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr, iters=iters,
+                                 score_weights=score_weights, diagnostics=True)
+
+    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None):
         """run() without its reprojection keys."""
         dsp = despike_args(despike)
         import torch
@@ -140,8 +165,10 @@ class TrackPipeline:
                     raise ValueError(f"frame 0 resolved to {int(cnt[0])} persons, the track has {self.P} slots (n_persons_out)")
                 tracked = np.minimum(cnt, int(cnt[0]) if F else 0).astype(np.int32)
         xyzs = tri["xyzs"]
+        if rfn:
+            xyzs, refine_cost, refine_codes = self._refine(xyzs, n_persons, rfn)
         th = self.th
-        fzrd = (float(th["smooth_f"]), float(th["smooth_z"]), float(th["smooth_r"]), float(th["smooth_delta_time"]))
+        fzrd =(float(th["smooth_f"]), float(th["smooth_z"]), float(th["smooth_r"]), float(th["smooth_delta_time"]))
         fill_gaps = int(fill_gaps)
         if fill_gaps < 0 or fill_gaps > MAX_GAP:
             raise ValueError(f"fill_gaps must be 0 (off) or a max_gap in 1..{MAX_GAP} (got {fill_gaps})")
@@ -222,6 +249,8 @@ class TrackPipeline:
                 res["xyzs_filled"], res["fill"] = filled, codes
             if dsp:
                 res["xyzs_despiked"], res["spike_codes"] = desp, scodes
+            if rfn:
+                res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
             return res
         if tracked is None:
             src = xyzs
@@ -257,6 +286,8 @@ class TrackPipeline:
             res["xyzs_filled"], res["fill"] = filled, codes
         if dsp:
             res["xyzs_despiked"], res["spike_codes"] = desp, scodes
+        if rfn:
+            res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
         return res
 
     @staticmethod
@@ -308,7 +339,8 @@ class ShardedTrackPipeline:
     left out for the same reason: the window of a record within half_window frames of a shard boundary holds records of the
     neighbouring rank.  Its reproject is not offered either: the caller holds only its own block of keypoints, and the per-view
     keys would have to be gathered beside the track; run TrackPipeline-style reprojection per rank with reproject.reprojection_cost
-    on the block's xyzs if it is wanted."""
+    on the block's xyzs if it is wanted.  Its refine is not offered for the same reason: refine.refine_joints on the block's xyzs and
+    keypoints does per rank what TrackPipeline.run(refine=...) does, a joint's refinement needs nothing from another frame."""
 
     def __init__(self, K, R, t, thresholds, blender_smooth_profile, n_persons_out=1, device=0, group=None, method=_lib.PAIRWISE):
         self.pipe = TrackPipeline(K, R, t, thresholds, blender_smooth_profile, n_persons_out=n_persons_out, device=device, method=method)

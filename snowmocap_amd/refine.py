@@ -1,0 +1,193 @@
+"""Refinement: joint records of any route moved to a local minimum of their weighted reprojection error, in pixels.
+
+Every route through the library ends in a closed-form 3D joint -- the score-weighted mean of two-ray midpoints (PAIRWISE), the
+minimiser of an algebraic error (DLT, DLT_ROBUST, the per-cluster DLT).  None of them minimises the distance between the joint's
+projections and the detections, which is the quantity the detector's noise lives in and the one `reprojection_cost` /
+`view_residuals` report.  A few Gauss-Newton steps from the closed-form point, on a 3 x 3 system per joint, find the
+maximum-likelihood point under pixel noise.
+
+The rule is stated in include/snowtri.h ("Refinement").  `refine_joints_reference` is that rule in NumPy: plain operations in its
+order (no fused multiply-add, a view's terms summed in camera order), no GPU, no library; it is what the host tests check and what
+the kernel k_refine (snowmocap_amd/csrc/snowtri_refine.hpp) is compared with: classes and costs, and the distance of both to a
+50-digit minimiser (tests/refine_cases.py).  `refine_joints` runs the kernel.
+
+The keypoints are on the UNDISTORTED frame (undistort first: Context.undistort_keypoints is an exact inverse).  Not offered: a robust
+loss (pass the `views` mask of DLT_ROBUST instead), more than 32 cameras, ShardedTrackPipeline.
+
+What it buys, on synthetic recipes (synth.ring_rig / the floor rig, two persons on the 1.5 m circle, 10 640 joints; not footage):
+with 1 px of noise in 4 cameras the RMS error against the truth goes from 7.08 mm (pairwise) / 6.95 mm (DLT) to 6.48 mm, with 8
+cameras from 5.37 / 5.29 to 4.87 mm; with a per-view sigma and score_weights = 1 / sigma^2 from 12.7 mm (DLT) over 11.8 mm (unit
+weights) to 9.4 mm.  On a single person standing at the rig's centre the gain is below 1 %: the geometry is symmetric.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from ._lib import REFINE_FEW_VIEWS, REFINE_KEPT, REFINE_MISSING, REFINE_MOVED  # noqa: F401
+from .records import missing_records
+from .reproject import _rig
+
+MAX_ITERS = 16
+MAX_CAMERAS = 32
+
+
+def _check_iters(iters):
+    if int(iters) != iters or not (1 <= int(iters) <= MAX_ITERS):
+        raise ValueError(f"iters must lie in 1..{MAX_ITERS} (got {iters})")
+    return int(iters)
+
+
+def refine_args(refine):
+    """TrackPipeline.run's `refine` argument -> None (off) or (iters, gate_px, score_weights), checked."""
+    if refine is None:
+        return None
+    if isinstance(refine, (tuple, list)):
+        if len(refine) != 3:
+            raise ValueError(f"refine must be None (off), iters or (iters, gate_px, score_weights) (got {refine!r})")
+        iters, gate_px, score_weights = refine
+    else:
+        iters, gate_px, score_weights = refine, 6.0, False
+    if not float(gate_px) >= 0.0:
+        raise ValueError("refine: gate_px must be >= 0 and not NaN")
+    return _check_iters(iters), float(gate_px), bool(score_weights)
+
+
+def refine_joints_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4,
+                            score_weights=False, return_views=False):
+    """The rule in NumPy: xyzs [F, P, kn, 4] (float32 / float64), kpts [F, C, Pmax, kn, 3], det_of [F, C, P] or None, n_persons
+    [F, C] or None, views [F, P, kn] (bit c: camera c may be used) or None ->
+    (out: xyzs' shape and dtype, cost [F, P, kn, 2] float64, codes [F, P, kn] uint8); with return_views also the view set V of
+    every record as a mask [F, P, kn] uint32 (0 for a copied record)."""
+    K, R, t, _, C = _rig(K, R, t, None)
+    iters = _check_iters(iters)
+    if C > MAX_CAMERAS:
+        raise ValueError(f"more than {MAX_CAMERAS} cameras")
+    thr = float(keypoint_score_threshold)
+    if thr != thr:
+        raise ValueError("keypoint_score_threshold is NaN")
+    xin = _lib.host_floats(xyzs)
+    if xin.ndim != 4 or xin.shape[-1] != 4:
+        raise ValueError(f"xyzs must be [F, P, kn, 4] records (got shape {xin.shape})")
+    F, P, kn, _ = xin.shape
+    kp = np.asarray(kpts).astype(np.float64)
+    if kp.ndim != 5 or kp.shape[:2] != (F, C) or kp.shape[3:] != (kn, 3) or kp.shape[2] < 1:
+        raise ValueError(f"kpts must be [F={F}, C={C}, Pmax >= 1, kn={kn}, 3] (got shape {kp.shape})")
+    Pmax = kp.shape[2]
+    if det_of is None:
+        if P > Pmax:
+            raise ValueError("det_of=None pairs person p with detection p: P must not exceed Pmax")
+        q = np.broadcast_to(np.arange(P, dtype=np.int64), (F, C, P))
+    else:
+        q = np.asarray(det_of).astype(np.int64).reshape(F, C, P)
+    nq = np.full((F, C), Pmax, dtype=np.int64) if n_persons is None else np.asarray(n_persons).astype(np.int64).reshape(F, C)
+    N = F * P * kn
+    x4 = xin.astype(np.float64)
+    measured = ~missing_records(x4).reshape(N)
+    listed = (q >= 0) & (q < nq[..., None]) & (q < Pmax)                                               # [F, C, P]
+    obs = np.take_along_axis(kp, np.where(listed, q, 0)[..., None, None], axis=2) if N else np.zeros((F, C, P, kn, 3))
+    obs = np.moveaxis(obs, 1, 0).reshape(C, N, 3)                                                      # [C, N, (u, v, s)]
+    listed = np.moveaxis(np.broadcast_to(listed[..., None], (F, C, P, kn)), 1, 0).reshape(C, N)
+    allowed = np.full(N, 0xffffffff, dtype=np.uint32) if views is None else np.asarray(views).astype(np.uint32).reshape(N)
+
+    def project(X):
+        """X [n, 3] -> x, y, pc2, u, v, ok [C, n] (rules 1, 3 and the geometric half of rule 4 of "Reprojection")."""
+        out = []
+        for c in range(C):
+            d0, d1, d2 = X[:, 0] - t[c, 0], X[:, 1] - t[c, 1], X[:, 2] - t[c, 2]
+            pc0 = (R[c, 0, 0] * d0 + R[c, 1, 0] * d1) + R[c, 2, 0] * d2
+            pc1 = (R[c, 0, 1] * d0 + R[c, 1, 1] * d1) + R[c, 2, 1] * d2
+            pc2 = (R[c, 0, 2] * d0 + R[c, 1, 2] * d1) + R[c, 2, 2] * d2
+            x, y = pc0 / pc2, pc1 / pc2
+            u = K[c, 0, 0] * x + K[c, 0, 1] * y + K[c, 0, 2]
+            v = K[c, 1, 1] * y + K[c, 1, 2]
+            out.append((x, y, pc2, u, v, (pc2 > 0) & np.isfinite(u) & np.isfinite(v)))
+        return [np.stack(a) for a in zip(*out)] if out else [np.zeros((0, X.shape[0]))] * 6
+
+    def evaluate(X, V, ou, ov, w):
+        """-> E [n], H [n, 6] (00, 10, 11, 20, 21, 22), g [n, 3], every view of V valid [n]; the views summed in camera order."""
+        n = X.shape[0]
+        x, y, pc2, u, v, ok = project(X)
+        E, H, g = np.zeros(n), np.zeros((n, 6)), np.zeros((n, 3))
+        valid = np.ones(n, dtype=bool)
+        for c in range(C):
+            ru, rv = u[c] - ou[c], v[c] - ov[c]
+            dx = [(R[c, k, 0] - x[c] * R[c, k, 2]) / pc2[c] for k in range(3)]
+            dy = [(R[c, k, 1] - y[c] * R[c, k, 2]) / pc2[c] for k in range(3)]
+            du = [K[c, 0, 0] * dx[k] + K[c, 0, 1] * dy[k] for k in range(3)]
+            dv = [K[c, 1, 1] * dy[k] for k in range(3)]
+            in_ = V[c]
+            E = E + np.where(in_, w[c] * (ru * ru + rv * rv), 0.0)
+            for m, (a, b) in enumerate(((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))):
+                H[:, m] = H[:, m] + np.where(in_, w[c] * (du[a] * du[b] + dv[a] * dv[b]), 0.0)
+            for k in range(3):
+                g[:, k] = g[:, k] + np.where(in_, w[c] * (du[k] * ru + dv[k] * rv), 0.0)
+            valid &= ok[c] | ~in_
+        return E, H, g, valid
+
+    def solve(H, g):
+        """H d = -g by LDL^T -> d [n, 3], every pivot finite and > 0 [n]."""
+        p0 = H[:, 0]
+        l10, l20 = H[:, 1] / p0, H[:, 3] / p0
+        p1 = H[:, 2] - l10 * H[:, 1]
+        m21 = H[:, 4] - l20 * H[:, 1]
+        l21 = m21 / p1
+        p2 = (H[:, 5] - l20 * H[:, 3]) - l21 * m21
+        y0 = -g[:, 0]
+        y1 = -g[:, 1] - l10 * y0
+        y2 = (-g[:, 2] - l20 * y0) - l21 * y1
+        s2 = y2 / p2
+        s1 = y1 / p1 - l21 * s2
+        s0 = (y0 / p0 - l10 * s1) - l20 * s2
+        pd = (p0 > 0) & np.isfinite(p0) & (p1 > 0) & np.isfinite(p1) & (p2 > 0) & np.isfinite(p2)
+        return np.stack([s0, s1, s2], axis=1), pd
+
+    with np.errstate(all="ignore"):
+        X = np.where(measured[:, None], x4.reshape(N, 4)[:, :3], 0.0)
+        ok0 = project(X)[5]
+        bit = ((allowed[None, :] >> np.arange(C, dtype=np.uint32)[:, None]) & 1).astype(bool)
+        V = measured[None, :] & listed & np.isfinite(obs[..., 0]) & np.isfinite(obs[..., 1]) & ~(obs[..., 2] < thr) & bit & ok0
+        few = V.sum(axis=0) < 2
+        V &= ~few[None, :]
+        ou, ov = np.where(V, obs[..., 0], 0.0), np.where(V, obs[..., 1], 0.0)
+        w = np.where(V, obs[..., 2] if score_weights else 1.0, 0.0)
+        E, H, g, _ = evaluate(X, V, ou, ov, w)
+        E0 = E.copy()
+        active = measured & ~few
+        moved = np.zeros(N, dtype=bool)
+        for _ in range(iters):
+            idx = np.nonzero(active)[0]
+            if not len(idx):
+                break
+            d, pd = solve(H[idx], g[idx])
+            Xt = X[idx] + d
+            Et, Ht, gt, valid = evaluate(Xt, V[:, idx], ou[:, idx], ov[:, idx], w[:, idx])
+            accept = pd & valid & (Et < E[idx])
+            a = idx[accept]
+            X[a], E[a], H[a], g[a] = Xt[accept], Et[accept], Ht[accept], gt[accept]
+            moved[a] = True
+            active[:] = False
+            active[a] = True
+    out = xin.copy().reshape(N, 4)
+    out[moved, :3] = X[moved].astype(xin.dtype)
+    copied = ~measured | few
+    cost = np.stack([np.where(copied, 0.0, E0), np.where(copied, 0.0, E)], axis=1)
+    codes = np.where(~measured, REFINE_MISSING, np.where(few, REFINE_FEW_VIEWS, np.where(moved, REFINE_MOVED, REFINE_KEPT))).astype(np.uint8)
+    res = (out.reshape(xin.shape), cost.reshape(F, P, kn, 2), codes.reshape(F, P, kn))
+    if return_views:
+        mask = np.zeros(N, dtype=np.uint32)
+        for c in range(C):
+            mask |= V[c].astype(np.uint32) << np.uint32(c)
+        res += (mask.reshape(F, P, kn),)
+    return res
+
+
+def refine_joints(ctx, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4, score_weights=False,
+                  diagnostics=False, stream=None):
+    """k_refine through the context of the rig (_lib.Context): Context.refine_joints.  -> the refined records, or
+    (records, cost, codes) with diagnostics=True."""
+    return ctx.refine_joints(xyzs, kpts, det_of=det_of, n_persons=n_persons, views=views, keypoint_score_threshold=keypoint_score_threshold,
+                             iters=iters, score_weights=score_weights, diagnostics=diagnostics, stream=stream)
+
+
+__all__ = ["refine_joints", "refine_joints_reference", "refine_args", "REFINE_MISSING", "REFINE_FEW_VIEWS", "REFINE_KEPT", "REFINE_MOVED"]
