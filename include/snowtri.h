@@ -297,13 +297,29 @@ int snowtri_triangulate_robust(snowtri_ctx *ctx, int64_t F, int32_t J, const voi
  * x[T][n] fp64, frame-major, n = persons * joints * 3 lanes (persons matched by index, as the reference does)
  * -> y[T][n].  Frame 0 passes through and seeds xp = y = x0, yd = 0; f, z, r, dt as in the reference
  * (main.py:72-77).  Evaluated as ONE pass over HBM -- a chained scan over 256-frame blocks with decoupled look-back: x is read
- * once, y written once (results equal the sequential recurrence to rounding: ~1e-13 m).  T <= 1 + 256 * 65535 frames, n <= 2^22 lanes. */
+ * once, y written once.  T <= 1 + 256 * 65535 frames, n <= 2^22 lanes.
+ * ACCURACY AND REPEATABILITY OF THE SCAN (this entry and every other one that runs k_smooth_scan: snowtri_smooth_joint_track,
+ * snowtri_smooth_shard_reduce / _scan, snowtri_blender_smooth, snowtri_blender_smooth_shard_reduce / _scan).  The scan is a
+ * re-association of the recurrence's sum: the state crosses a 32-frame wave through R = A^32 and a 256-frame block through
+ * P = A^256 (A: the one-frame update, snowtri_smooth_coeffs).  For every STABLE filter (spectral radius of A at most 1: slow,
+ * overdamped and undamped ones, high frame rates) the result equals the recurrence evaluated in exact arithmetic on the same
+ * fp64 inputs and coefficients within 16 x the rounding error the sequential fp64 recurrence itself makes on that track;
+ * measured: at most 2.3 x that error, 2.6e-14 m on tracks of metres and up to 2100 frames, from f = 0.05 Hz at 30 fps (max|P| = 1.1)
+ * and an undamped filter (max|P| = 3.1) to the reference's profiles at 240 fps (tests/test_gpu_smooth_carry.py).  The "~1e-13 m"
+ * this header used to quote was measured at the reference's 30 fps profiles only (f = 1.5 ... 4.5 Hz), where max|P| < 1e-20.
+ * A block's look-back adds up either the aggregates of the blocks before it or an inclusive state one of them has already
+ * published -- whichever it finds -- and the two orders agree in exact arithmetic only.  So two calls on the same input are
+ * BIT-FOR-BIT equal where P underflows against the state (max|P| below ~1e-17: the reference's 30 fps profiles, tested over
+ * 782 chained blocks), and otherwise equal to the bound above: each within it, any two within twice it (measured spread:
+ * 2.7e-15 m at max|P| = 3.1).  A caller that needs bitwise repeatability at a slow filter has the five-pass shard form
+ * (_shard_local / _combine / _fix, also on one shard), whose order is fixed.  An unstable filter overflows, here as in the reference. */
 int snowtri_smooth_track(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, double f, double z, double r,
                          double dt, double *y, int memspace, void *stream);
 /* The same on a track of JOINT RECORDS as snowtri_triangulate_condense writes them with SNOWTRI_F64 outputs: xyzs[T][m][4] =
  * (x, y, z, score), m = persons * keypoint_num -> out[T][m][4] with the three coordinates filtered and the score COPIED (the
  * reference filters the points only, triangulation.py:169-184: a caller of snowtri_smooth_track had to filter the score lane
- * for nothing and copy the scores over afterwards).  out may not alias xyzs. */
+ * for nothing and copy the scores over afterwards).  out may not alias xyzs.  Accuracy and repeatability: as stated at
+ * snowtri_smooth_track (the same scan). */
 int snowtri_smooth_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const double *xyzs, double f, double z, double r,
                                double dt, double *out, int memspace, void *stream);
 
@@ -337,7 +353,10 @@ int snowtri_smooth_shard_combine(snowtri_ctx *ctx, int32_t world, int32_t rank, 
  *                                without writing a track;
  *   (the all-gather and snowtri_smooth_shard_combine as above)
  *   snowtri_smooth_shard_scan    y = the shard filtered from its true entering state start_state[2n]: x read once, y written once.
- * 24 bytes moved per lane-frame against the 40 of _local + _fix; same `first` contract; results equal to rounding (~1e-13 m).
+ * 24 bytes moved per lane-frame against the 40 of _local + _fix; same `first` contract.  Both run the scan of snowtri_smooth_track:
+ * its accuracy and repeatability statement holds for the entering states snowtri_smooth_shard_combine returns (y and yd, each
+ * against 16 x the sequential recurrence's own error on that component; A^m with m up to 700 at max|P| = 3.1 tested) and for the
+ * assembled track -- bit-for-bit repeatable where P = A^256 underflows against the state, to that bound otherwise.
  * snowmocap_amd/sharded.py::smooth_exchange2 drives it. */
 int snowtri_smooth_shard_reduce(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, int first, double f, double z, double r,
                                 double dt, double *end_state, void *stream);
@@ -363,7 +382,9 @@ int snowtri_blender_points(snowtri_ctx *ctx, int64_t n, int32_t keypoint_num, co
  *   points [T][n_persons][24][4] fp64, valid [T][n_persons][24], fzr [24][3] = per-point (f, z, r) of
  *   configs/blender_smooth_profile.json, dt = delta_time  ->  out [T][n_persons][24][4].
  * Frame 0 is returned as given (NaNs included) and seeds every filter with the point, or with zeros when it is
- * invalid; a later invalid point feeds the filter its previous input.  Evaluated as chunked scans over frames. */
+ * invalid; a later invalid point feeds the filter its previous input.  Evaluated as chunked scans over frames: the hold first,
+ * then the scan of snowtri_smooth_track with per-point coefficients -- its accuracy and repeatability statement holds per
+ * control point (bit-for-bit repeatable for the points whose P = A^256 underflows, to the rounding bound for slower ones). */
 int snowtri_blender_smooth(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *points,
                            const uint8_t *valid, const double *fzr, double dt, double *out, int memspace,
                            void *stream);
@@ -392,7 +413,8 @@ int snowtri_blender_smooth_shard_combine(snowtri_ctx *ctx, int32_t world, int32_
                                          const double *fzr, double dt, double *start_state, void *stream);
 int snowtri_blender_smooth_shard_fix(snowtri_ctx *ctx, int64_t T, int64_t n_persons, int first, const double *start_state, const double *fzr,
                                      double dt, double *y, void *stream);
-/* ... and its two-pass form on `held` (snowtri_smooth_shard_reduce / _scan with the per-point coefficients). */
+/* ... and its two-pass form on `held` (snowtri_smooth_shard_reduce / _scan with the per-point coefficients; the same accuracy
+ * and repeatability statement, per control point). */
 int snowtri_blender_smooth_shard_reduce(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *held, int first, const double *fzr,
                                         double dt, double *end_state, void *stream);
 int snowtri_blender_smooth_shard_scan(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *held, int first, const double *start_state,
