@@ -1358,6 +1358,17 @@ namespace {
 
 constexpr int kSmoothChunk = 256;
 
+// p = A^L by repeated multiplication (fp64), row-major
+void smooth_power(const SmoothCoef &k, int L, double p[4]) {
+    p[0] = p[3] = 1.0;
+    p[1] = p[2] = 0.0;
+    for (int i = 0; i < L; i++) {
+        const double q0 = k.a00 * p[0] + k.a01 * p[2], q1 = k.a00 * p[1] + k.a01 * p[3];
+        const double q2 = k.a10 * p[0] + k.a11 * p[2], q3 = k.a10 * p[1] + k.a11 * p[3];
+        p[0] = q0; p[1] = q1; p[2] = q2; p[3] = q3;
+    }
+}
+
 SmoothCoef smooth_coef(double f, double z, double r, double dt) {
     const double pi = 3.141592653589793;
     const double k1 = z / (pi * f), k2 = 1.0 / ((2 * pi * f) * (2 * pi * f)), k3 = r * z / (2 * pi * f);
@@ -1368,20 +1379,11 @@ SmoothCoef smooth_coef(double f, double z, double r, double dt) {
     k.a11 = 1.0 - dt * dt / k2 - dt * k1 / k2;
     k.cx = dt / k2;
     k.cxd = k3 / k2;  // (T/k2) * k3 * (x - xp)/T
-    double p[4] = {1, 0, 0, 1};  // A^L by repeated multiplication (fp64)
-    for (int i = 0; i < kSmoothChunk; i++) {
-        const double q0 = k.a00 * p[0] + k.a01 * p[2], q1 = k.a00 * p[1] + k.a01 * p[3];
-        const double q2 = k.a10 * p[0] + k.a11 * p[2], q3 = k.a10 * p[1] + k.a11 * p[3];
-        p[0] = q0; p[1] = q1; p[2] = q2; p[3] = q3;
-    }
+    double p[4];
+    smooth_power(k, kSmoothChunk, p);
     k.p00 = p[0]; k.p01 = p[1]; k.p10 = p[2]; k.p11 = p[3];
-    double q[4] = {1, 0, 0, 1};  // A^32: the frames one wave of the one-pass scan holds (k_smooth_scan)
-    for (int i = 0; i < kScanL; i++) {
-        const double q0 = k.a00 * q[0] + k.a01 * q[2], q1 = k.a00 * q[1] + k.a01 * q[3];
-        const double q2 = k.a10 * q[0] + k.a11 * q[2], q3 = k.a10 * q[1] + k.a11 * q[3];
-        q[0] = q0; q[1] = q1; q[2] = q2; q[3] = q3;
-    }
-    k.r00 = q[0]; k.r01 = q[1]; k.r10 = q[2]; k.r11 = q[3];
+    smooth_power(k, kScanL, p);  // A^32: the frames one wave of the one-pass scan holds (k_smooth_scan)
+    k.r00 = p[0]; k.r01 = p[1]; k.r10 = p[2]; k.r11 = p[3];
     return k;
 }
 
@@ -1480,11 +1482,149 @@ int smooth_whole_dev(snowtri_ctx *ctx, hipStream_t st, int64_t T, int64_t n, con
     return SNOWTRI_OK;
 }
 
-bool smooth_args_ok(snowtri_ctx *ctx, int64_t T, int64_t n, double f, double dt, int memspace) {
-    return ctx && T >= 0 && n >= 0 && f > 0.0 && dt > 0.0 && (memspace == SNOWTRI_HOST || memspace == SNOWTRI_DEVICE);
+// per-bone coefficient table of the context, as the filters take it (*k): rebuilt and uploaded only when (fzr, dt) change -- the
+// common caller passes the same smooth profile every time, and an upload has to drain the stream first
+int blender_table(snowtri_ctx *ctx, hipStream_t st, const double *fzr, double dt, TableCoef *k) {
+    std::vector<double> key(fzr, fzr + 3 * kBlenderPoints);
+    key.push_back(dt);
+    if (!ctx->dBlenderTab) HIP_TRY(hipMalloc(&ctx->dBlenderTab, sizeof(SmoothCoef) * kBlenderPoints));
+    if (key != ctx->blender_key) {
+        SmoothCoef tab[kBlenderPoints];
+        for (int i = 0; i < kBlenderPoints; i++) tab[i] = smooth_coef(fzr[3 * i], fzr[3 * i + 1], fzr[3 * i + 2], dt);
+        HIP_TRY(hipStreamSynchronize(st));   // kernels of an earlier call may still read the old table
+        HIP_TRY(hipMemcpy(ctx->dBlenderTab, tab, sizeof(tab), hipMemcpyHostToDevice));
+        ctx->blender_key = key;
+    }
+    *k = TableCoef{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
+    return SNOWTRI_OK;
 }
-int smooth_track_impl(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, double f, double z, double r, double dt, double *y, int memspace,
-                      void *stream, bool skip4);
+
+// ---- The smoothing entry layer.  A FILTER SOURCE says where a call's coefficients come from: one (f, z, r) for every lane
+// (row N1) or the per-bone table of row N2.  Both have one shape -- ok(), Coef, coef() -- and every pass of the C ABI is
+// written once over it; the exported entries below and in the N2 section only name their source and their lane count.
+struct UniformFilter {
+    using Coef = UniformCoef;
+    double f, z, r, dt;
+    bool ok() const { return f > 0.0 && dt > 0.0; }
+    int coef(snowtri_ctx *, hipStream_t, Coef *k) const {
+        *k = UniformCoef{smooth_coef(f, z, r, dt)};
+        return SNOWTRI_OK;
+    }
+};
+struct BoneFilter {
+    using Coef = TableCoef;
+    const double *fzr;   // [kBlenderPoints][3]
+    double dt;
+    bool ok() const {
+        if (!fzr || !(dt > 0.0)) return false;
+        for (int i = 0; i < kBlenderPoints; i++)
+            if (!(fzr[3 * i] > 0.0)) return false;
+        return true;
+    }
+    int coef(snowtri_ctx *ctx, hipStream_t st, Coef *k) const { return blender_table(ctx, st, fzr, dt, k); }
+};
+int64_t blender_lanes(int64_t n_persons) { return n_persons * kBlenderPoints * 4; }
+
+// Every pass checks in this order: the arguments (below), an empty shard (SNOWTRI_OK before any pointer is looked at), the
+// required pointers; then it enters the device, takes its coefficients, stages host arrays (a SNOWTRI_DEVICE call stages
+// nothing) and runs its device function.
+template <typename F>
+bool smooth_args_ok(snowtri_ctx *ctx, int64_t T, int64_t n, const F &src, int memspace) {
+    return ctx && T >= 0 && n >= 0 && src.ok() && (memspace == SNOWTRI_HOST || memspace == SNOWTRI_DEVICE);
+}
+
+template <typename F>
+int smooth_pass_local(snowtri_ctx *ctx, const F &src, int64_t T, int64_t n, const double *x, int first, double *y, double *end_state,
+                      int memspace, void *stream) {
+    if (!smooth_args_ok(ctx, T, n, src, memspace)) return SNOWTRI_ERR_BAD_ARG;
+    if (T == 0 || n == 0) return SNOWTRI_OK;
+    if (!x || !y) return SNOWTRI_ERR_BAD_ARG;
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    typename F::Coef k;
+    if (int rc = src.coef(ctx, st, &k)) return rc;
+    const size_t bytes = sizeof(double) * (size_t)T * n;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&x, bytes);
+    sg.out(&y, bytes);
+    sg.out(&end_state, sizeof(double) * 2 * n);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = smooth_local_dev(ctx, st, T, n, x, y, first != 0, k, end_state)) return rc;
+    return sg.end();
+}
+
+template <typename F>
+int smooth_pass_fix(snowtri_ctx *ctx, const F &src, int64_t T, int64_t n, int first, const double *start_state, double *y, int memspace,
+                    void *stream) {
+    if (!smooth_args_ok(ctx, T, n, src, memspace)) return SNOWTRI_ERR_BAD_ARG;
+    if (T == 0 || n == 0) return SNOWTRI_OK;
+    if (!start_state || !y) return SNOWTRI_ERR_BAD_ARG;
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    typename F::Coef k;
+    if (int rc = src.coef(ctx, st, &k)) return rc;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.inout(&y, sizeof(double) * (size_t)T * n);
+    sg.in(&start_state, sizeof(double) * 2 * n);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = smooth_fix_dev(ctx, st, T, n, y, first != 0, start_state, k)) return rc;
+    return sg.end();
+}
+
+// The two-pass form of the sharded protocol (round 6), one k_smooth_scan pass each, device pointers.  _reduce (y and start_state
+// null): the shard's zero-state end state from ONE read of x.  _scan (end_state null): the shard filtered from its true entering
+// state in one more pass.
+template <typename F>
+int smooth_pass_scan(snowtri_ctx *ctx, const F &src, bool reduce, int64_t T, int64_t n, const double *x, int first,
+                     const double *start_state, double *y, double *end_state, void *stream) {
+    if (!smooth_args_ok(ctx, T, n, src, SNOWTRI_DEVICE)) return SNOWTRI_ERR_BAD_ARG;
+    if (T == 0 || n == 0) return SNOWTRI_OK;
+    if (!x || (reduce ? !end_state : (!y || !start_state))) return SNOWTRI_ERR_BAD_ARG;
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    typename F::Coef k;
+    if (int rc = src.coef(ctx, st, &k)) return rc;
+    return smooth_whole_dev(ctx, st, T, n, x, y, (const double *)nullptr, k, NoHold{}, false, first ? 1 : 0, start_state, end_state);
+}
+
+template <typename F>
+int smooth_pass_combine(snowtri_ctx *ctx, const F &src, int32_t world, int32_t rank, int64_t n, const double *gathered,
+                        double *start_state, int memspace, void *stream) {
+    if (!smooth_args_ok(ctx, 0, n, src, memspace) || world < 1 || rank < 0 || rank >= world) return SNOWTRI_ERR_BAD_ARG;
+    if (n == 0) return SNOWTRI_OK;
+    if (!gathered || !start_state) return SNOWTRI_ERR_BAD_ARG;
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    typename F::Coef k;
+    if (int rc = src.coef(ctx, st, &k)) return rc;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&gathered, sizeof(double) * (size_t)world * (4 * (size_t)n + 1));
+    sg.out(&start_state, sizeof(double) * 2 * (size_t)n);
+    if (int rc = sg.begin()) return rc;
+    hipLaunchKernelGGL(k_smooth_combine<typename F::Coef>, dim3((unsigned)((n + kSmoothBlock - 1) / kSmoothBlock)), dim3(kSmoothBlock), 0, st,
+                       (int)world, (int)rank, n, gathered, k, start_state);
+    HIP_TRY(hipGetLastError());
+    return sg.end();
+}
+
+// A whole uniform track (snowtri_smooth_track; skip4: the joint records of snowtri_smooth_joint_track)
+int smooth_track_impl(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, const UniformFilter &src, double *y, int memspace,
+                      void *stream, bool skip4) {
+    if (!smooth_args_ok(ctx, T, n, src, memspace)) return SNOWTRI_ERR_BAD_ARG;
+    if (T == 0 || n == 0) return SNOWTRI_OK;
+    if (!x || !y) return SNOWTRI_ERR_BAD_ARG;
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    UniformCoef k;
+    if (int rc = src.coef(ctx, st, &k)) return rc;
+    const size_t bytes = sizeof(double) * (size_t)T * n;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&x, bytes);
+    sg.out(&y, bytes);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = smooth_whole_dev(ctx, st, T, n, x, y, x, k, NoHold{}, skip4)) return rc;
+    return sg.end();
+}
 
 }  // namespace
 
@@ -1500,119 +1640,41 @@ int snowtri_smooth_coeffs(double f, double z, double r, double dt, double out[6]
 int snowtri_smooth_shard_local(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, int first, double f,
                                double z, double r, double dt, double *y, double *end_state, int memspace,
                                void *stream) {
-    if (!smooth_args_ok(ctx, T, n, f, dt, memspace)) return SNOWTRI_ERR_BAD_ARG;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!x || !y) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    const UniformCoef k{smooth_coef(f, z, r, dt)};
-    const size_t bytes = sizeof(double) * (size_t)T * n;
-    const double *dx = x;
-    double *dy = y, *dend = end_state;
-    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
-    sg.in(&dx, bytes);
-    sg.out(&dy, bytes);
-    sg.out(&dend, sizeof(double) * 2 * n);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = smooth_local_dev(ctx, st, T, n, dx, dy, first != 0, k, dend)) return rc;
-    return sg.end();
+    return smooth_pass_local(ctx, UniformFilter{f, z, r, dt}, T, n, x, first, y, end_state, memspace, stream);
 }
 
 int snowtri_smooth_shard_fix(snowtri_ctx *ctx, int64_t T, int64_t n, int first, const double *start_state, double f,
                              double z, double r, double dt, double *y, int memspace, void *stream) {
-    if (!smooth_args_ok(ctx, T, n, f, dt, memspace)) return SNOWTRI_ERR_BAD_ARG;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!start_state || !y) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    const UniformCoef k{smooth_coef(f, z, r, dt)};
-    const size_t bytes = sizeof(double) * (size_t)T * n;
-    double *dy = y;
-    const double *dstart = start_state;
-    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
-    sg.inout(&dy, bytes);
-    sg.in(&dstart, sizeof(double) * 2 * n);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = smooth_fix_dev(ctx, st, T, n, dy, first != 0, dstart, k)) return rc;
-    return sg.end();
+    return smooth_pass_fix(ctx, UniformFilter{f, z, r, dt}, T, n, first, start_state, y, memspace, stream);
 }
 
-// The two-pass form of the sharded protocol (round 6): _reduce = the shard's zero-state end state from ONE read of x, _scan = the
-// shard filtered from its true entering state in one more pass (k_smooth_scan both times); device pointers.
 int snowtri_smooth_shard_reduce(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, int first, double f, double z, double r,
                                 double dt, double *end_state, void *stream) {
-    if (!smooth_args_ok(ctx, T, n, f, dt, SNOWTRI_DEVICE)) return SNOWTRI_ERR_BAD_ARG;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!x || !end_state) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    return smooth_whole_dev(ctx, (hipStream_t)stream, T, n, x, (double *)nullptr, (const double *)nullptr, UniformCoef{smooth_coef(f, z, r, dt)}, NoHold{}, false,
-                            first ? 1 : 0, (const double *)nullptr, end_state);
+    return smooth_pass_scan(ctx, UniformFilter{f, z, r, dt}, true, T, n, x, first, nullptr, nullptr, end_state, stream);
 }
 
 int snowtri_smooth_shard_scan(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, int first, const double *start_state, double f,
                               double z, double r, double dt, double *y, void *stream) {
-    if (!smooth_args_ok(ctx, T, n, f, dt, SNOWTRI_DEVICE)) return SNOWTRI_ERR_BAD_ARG;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!x || !y || !start_state) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    return smooth_whole_dev(ctx, (hipStream_t)stream, T, n, x, y, (const double *)nullptr, UniformCoef{smooth_coef(f, z, r, dt)}, NoHold{}, false,
-                            first ? 1 : 0, start_state, (double *)nullptr);
+    return smooth_pass_scan(ctx, UniformFilter{f, z, r, dt}, false, T, n, x, first, start_state, y, nullptr, stream);
 }
 
 int snowtri_smooth_shard_combine(snowtri_ctx *ctx, int32_t world, int32_t rank, int64_t n, const double *gathered, double f,
                                  double z, double r, double dt, double *start_state, int memspace, void *stream) {
-    if (!smooth_args_ok(ctx, 0, n, f, dt, memspace) || world < 1 || rank < 0 || rank >= world) return SNOWTRI_ERR_BAD_ARG;
-    if (n == 0) return SNOWTRI_OK;
-    if (!gathered || !start_state) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    const SmoothCoef k = smooth_coef(f, z, r, dt);
-    const size_t gbytes = sizeof(double) * (size_t)world * (4 * (size_t)n + 1), sbytes = sizeof(double) * 2 * (size_t)n;
-    const double *dg = gathered;
-    double *ds = start_state;
-    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
-    sg.in(&dg, gbytes);
-    sg.out(&ds, sbytes);
-    if (int rc = sg.begin()) return rc;
-    hipLaunchKernelGGL(k_smooth_combine<UniformCoef>, dim3((unsigned)((n + kSmoothBlock - 1) / kSmoothBlock)), dim3(kSmoothBlock), 0, st, (int)world,
-                       (int)rank, n, dg, UniformCoef{k}, ds);
-    HIP_TRY(hipGetLastError());
-    return sg.end();
+    return smooth_pass_combine(ctx, UniformFilter{f, z, r, dt}, world, rank, n, gathered, start_state, memspace, stream);
 }
 
 int snowtri_smooth_joint_track(snowtri_ctx *ctx, int64_t T, int64_t m, const double *xyzs, double f, double z, double r,
                                double dt, double *out, int memspace, void *stream) {
     if (m < 0 || m > ((int64_t)1 << 40)) return SNOWTRI_ERR_BAD_ARG;
-    return smooth_track_impl(ctx, T, 4 * m, xyzs, f, z, r, dt, out, memspace, stream, true);
+    return smooth_track_impl(ctx, T, 4 * m, xyzs, UniformFilter{f, z, r, dt}, out, memspace, stream, true);
 }
 
 int snowtri_smooth_track(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, double f, double z, double r,
                          double dt, double *y, int memspace, void *stream) {
-    return smooth_track_impl(ctx, T, n, x, f, z, r, dt, y, memspace, stream, false);
+    return smooth_track_impl(ctx, T, n, x, UniformFilter{f, z, r, dt}, y, memspace, stream, false);
 }
 
 }  // extern "C"
-
-namespace {
-int smooth_track_impl(snowtri_ctx *ctx, int64_t T, int64_t n, const double *x, double f, double z, double r,
-                      double dt, double *y, int memspace, void *stream, bool skip4) {
-    if (!smooth_args_ok(ctx, T, n, f, dt, memspace)) return SNOWTRI_ERR_BAD_ARG;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!x || !y) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    const UniformCoef k{smooth_coef(f, z, r, dt)};
-    const size_t bytes = sizeof(double) * (size_t)T * n;
-    const double *dx = x;
-    double *dy = y;
-    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
-    sg.in(&dx, bytes);
-    sg.out(&dy, bytes);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = smooth_whole_dev(ctx, st, T, n, dx, dy, dx, k, NoHold{}, skip4)) return rc;
-    return sg.end();
-}
-}  // namespace
 
 extern "C" {
 
@@ -1699,30 +1761,6 @@ int snowtri_blender_points(snowtri_ctx *ctx, int64_t n, int32_t keypoint_num, co
     return sg.end();
 }
 
-// per-bone coefficient table of the context, as the filters take it (*k): rebuilt and uploaded only when (fzr, dt) change -- the
-// common caller passes the same smooth profile every time, and an upload has to drain the stream first
-static int blender_table(snowtri_ctx *ctx, hipStream_t st, const double *fzr, double dt, TableCoef *k) {
-    std::vector<double> key(fzr, fzr + 3 * kBlenderPoints);
-    key.push_back(dt);
-    if (!ctx->dBlenderTab) HIP_TRY(hipMalloc(&ctx->dBlenderTab, sizeof(SmoothCoef) * kBlenderPoints));
-    if (key != ctx->blender_key) {
-        SmoothCoef tab[kBlenderPoints];
-        for (int i = 0; i < kBlenderPoints; i++) tab[i] = smooth_coef(fzr[3 * i], fzr[3 * i + 1], fzr[3 * i + 2], dt);
-        HIP_TRY(hipStreamSynchronize(st));   // kernels of an earlier call may still read the old table
-        HIP_TRY(hipMemcpy(ctx->dBlenderTab, tab, sizeof(tab), hipMemcpyHostToDevice));
-        ctx->blender_key = key;
-    }
-    *k = TableCoef{(const SmoothCoef *)ctx->dBlenderTab, 4, kBlenderPoints};
-    return SNOWTRI_OK;
-}
-static bool blender_shard_args_ok(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *fzr, double dt) {
-    if (!ctx || T < 0 || n_persons < 0 || (fzr && !(dt > 0.0))) return false;
-    if (fzr)
-        for (int i = 0; i < kBlenderPoints; i++)
-            if (!(fzr[3 * i] > 0.0)) return false;
-    return true;
-}
-
 // The hold's scratch in ctx->aux for n lanes over the filter's nchunks chunks: [4096 bytes | H | start | Hf | entering], with
 // H and start [max(1, nchunks)][n] doubles, Hf as many bytes and entering [n] doubles on a 256-byte boundary.
 struct HoldScratch {
@@ -1744,8 +1782,8 @@ static int hold_scratch(snowtri_ctx *ctx, int64_t nchunks, int64_t n, HoldScratc
 // ---- N2 on a FRAME-SHARDED track (device pointers only; include/snowtri.h describes the protocol)
 int snowtri_blender_hold_shard_last(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *points, const uint8_t *valid,
                                     double *payload, void *stream) {
-    if (!blender_shard_args_ok(ctx, T, n_persons, nullptr, 0.0) || !payload) return SNOWTRI_ERR_BAD_ARG;
-    const int64_t n = n_persons * kBlenderPoints * 4;
+    if (!ctx || T < 0 || n_persons < 0 || !payload) return SNOWTRI_ERR_BAD_ARG;
+    const int64_t n = blender_lanes(n_persons);
     if (n == 0) return SNOWTRI_OK;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
@@ -1761,8 +1799,8 @@ int snowtri_blender_hold_shard_last(snowtri_ctx *ctx, int64_t T, int64_t n_perso
 
 int snowtri_blender_hold_shard_apply(snowtri_ctx *ctx, int32_t world, int32_t rank, int64_t T, int64_t n_persons, const double *points,
                                      const uint8_t *valid, const double *gathered, double *held, void *stream) {
-    if (!blender_shard_args_ok(ctx, T, n_persons, nullptr, 0.0) || world < 1 || rank < 0 || rank >= world) return SNOWTRI_ERR_BAD_ARG;
-    const int64_t n = n_persons * kBlenderPoints * 4;
+    if (!ctx || T < 0 || n_persons < 0 || world < 1 || rank < 0 || rank >= world) return SNOWTRI_ERR_BAD_ARG;
+    const int64_t n = blender_lanes(n_persons);
     if (T == 0 || n == 0) return SNOWTRI_OK;
     if (!points || !valid || !gathered || !held) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
@@ -1783,91 +1821,49 @@ int snowtri_blender_hold_shard_apply(snowtri_ctx *ctx, int32_t world, int32_t ra
     return SNOWTRI_OK;
 }
 
+// the per-bone passes: the smoothing entry layer of row N1 over BoneFilter, device pointers
 int snowtri_blender_smooth_shard_local(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *held, int first, const double *fzr,
                                        double dt, double *y, double *end_state, void *stream) {
-    if (!fzr || !blender_shard_args_ok(ctx, T, n_persons, fzr, dt)) return SNOWTRI_ERR_BAD_ARG;
-    const int64_t n = n_persons * kBlenderPoints * 4;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!held || !y) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    TableCoef k;
-    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
-    return smooth_local_dev(ctx, st, T, n, held, y, first != 0, k, end_state);
+    return smooth_pass_local(ctx, BoneFilter{fzr, dt}, T, blender_lanes(n_persons), held, first, y, end_state, SNOWTRI_DEVICE, stream);
 }
 
 int snowtri_blender_smooth_shard_reduce(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *held, int first, const double *fzr,
                                         double dt, double *end_state, void *stream) {
-    if (!fzr || !blender_shard_args_ok(ctx, T, n_persons, fzr, dt)) return SNOWTRI_ERR_BAD_ARG;
-    const int64_t n = n_persons * kBlenderPoints * 4;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!held || !end_state) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    TableCoef k;
-    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
-    return smooth_whole_dev(ctx, st, T, n, held, (double *)nullptr, (const double *)nullptr, k, NoHold{}, false, first ? 1 : 0, (const double *)nullptr, end_state);
+    return smooth_pass_scan(ctx, BoneFilter{fzr, dt}, true, T, blender_lanes(n_persons), held, first, nullptr, nullptr, end_state, stream);
 }
 
 int snowtri_blender_smooth_shard_scan(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *held, int first, const double *start_state,
                                       const double *fzr, double dt, double *y, void *stream) {
-    if (!fzr || !blender_shard_args_ok(ctx, T, n_persons, fzr, dt)) return SNOWTRI_ERR_BAD_ARG;
-    const int64_t n = n_persons * kBlenderPoints * 4;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!held || !y || !start_state) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    TableCoef k;
-    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
-    return smooth_whole_dev(ctx, st, T, n, held, y, (const double *)nullptr, k, NoHold{}, false, first ? 1 : 0, start_state, (double *)nullptr);
+    return smooth_pass_scan(ctx, BoneFilter{fzr, dt}, false, T, blender_lanes(n_persons), held, first, start_state, y, nullptr, stream);
 }
 
 int snowtri_blender_smooth_shard_combine(snowtri_ctx *ctx, int32_t world, int32_t rank, int64_t n_persons, const double *gathered,
                                          const double *fzr, double dt, double *start_state, void *stream) {
-    if (!fzr || !blender_shard_args_ok(ctx, 0, n_persons, fzr, dt) || world < 1 || rank < 0 || rank >= world) return SNOWTRI_ERR_BAD_ARG;
-    const int64_t n = n_persons * kBlenderPoints * 4;
-    if (n == 0) return SNOWTRI_OK;
-    if (!gathered || !start_state) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    TableCoef k;
-    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
-    hipLaunchKernelGGL(k_smooth_combine<TableCoef>, dim3((unsigned)((n + kSmoothBlock - 1) / kSmoothBlock)), dim3(kSmoothBlock), 0, st, (int)world,
-                       (int)rank, n, gathered, k, start_state);
-    HIP_TRY(hipGetLastError());
-    return SNOWTRI_OK;
+    return smooth_pass_combine(ctx, BoneFilter{fzr, dt}, world, rank, blender_lanes(n_persons), gathered, start_state, SNOWTRI_DEVICE, stream);
 }
 
 int snowtri_blender_smooth_shard_fix(snowtri_ctx *ctx, int64_t T, int64_t n_persons, int first, const double *start_state, const double *fzr,
                                      double dt, double *y, void *stream) {
-    if (!fzr || !blender_shard_args_ok(ctx, T, n_persons, fzr, dt)) return SNOWTRI_ERR_BAD_ARG;
-    const int64_t n = n_persons * kBlenderPoints * 4;
-    if (T == 0 || n == 0) return SNOWTRI_OK;
-    if (!start_state || !y) return SNOWTRI_ERR_BAD_ARG;
-    ENTER_DEVICE(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
-    TableCoef k;
-    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
-    return smooth_fix_dev(ctx, st, T, n, y, first != 0, start_state, k);
+    return smooth_pass_fix(ctx, BoneFilter{fzr, dt}, T, blender_lanes(n_persons), first, start_state, y, SNOWTRI_DEVICE, stream);
 }
 
 int snowtri_blender_smooth(snowtri_ctx *ctx, int64_t T, int64_t n_persons, const double *points,
                            const uint8_t *valid, const double *fzr, double dt, double *out, int memspace,
                            void *stream) {
-    if (!fzr || !blender_shard_args_ok(ctx, T, n_persons, fzr, dt) || (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE))
-        return SNOWTRI_ERR_BAD_ARG;
-    if (T == 0 || n_persons == 0) return SNOWTRI_OK;
+    const BoneFilter src{fzr, dt};
+    const int64_t n = blender_lanes(n_persons), nv = n_persons * kBlenderPoints;
+    if (!smooth_args_ok(ctx, T, n, src, memspace)) return SNOWTRI_ERR_BAD_ARG;
+    if (T == 0 || n == 0) return SNOWTRI_OK;
     if (!points || !valid || !out) return SNOWTRI_ERR_BAD_ARG;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t n = n_persons * kBlenderPoints * 4, nv = n_persons * kBlenderPoints;
     const int64_t nchunks = (T - 1 + kSmoothChunk - 1) / kSmoothChunk;  // the filter's chunks: frames 1..T-1
     if (nchunks > 65535) return SNOWTRI_ERR_BAD_ARG;
     const size_t bytes = sizeof(double) * (size_t)T * n;
     HoldScratch h;
     if (int rc = hold_scratch(ctx, nchunks, n, &h)) return rc;
     TableCoef k;
-    if (int rc = blender_table(ctx, st, fzr, dt, &k)) return rc;
+    if (int rc = src.coef(ctx, st, &k)) return rc;
     const double *dx = points;
     const uint8_t *dv = valid;
     double *dy = out;

@@ -150,15 +150,6 @@ __global__ __launch_bounds__(kSmoothBlock) void k_smooth_carry(int64_t n, int64_
     for (; c < nchunks; c++) step(c, E ? E[(c * n + lane) * 2] : 0.0, E ? E[(c * n + lane) * 2 + 1] : 0.0);
 }
 
-// seed state of a track: (x0, 0) per lane (:11-13)
-__global__ __launch_bounds__(kSmoothBlock) void k_smooth_seed(int64_t n, const double *__restrict__ x0,
-                                                              double *__restrict__ st) {
-    const int64_t lane = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (lane >= n) return;
-    st[2 * lane] = x0[lane];
-    st[2 * lane + 1] = 0.0;
-}
-
 // y_t += (A^{t-t0+1} S_c).y ; the last chunk (optionally) also reports the propagated state (end_out, [2n])
 template <typename KS>
 __global__ __launch_bounds__(kSmoothBlock) void k_smooth_fix(int64_t T, int64_t n, int L, int tb, KS ks,

@@ -23,6 +23,25 @@ def shard_bounds(F, world, rank):
     return lo, min(F, lo + per), per
 
 
+def _starts_track(who, T, F_total, group):
+    """Checks that a block of T frames is this rank's shard_bounds block of a track of F_total frames (ValueError in the name of
+    `who` otherwise); returns whether the block starts the track, i.e. holds frame 0."""
+    import torch.distributed as dist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    lo, hi, _ = shard_bounds(int(F_total), world, rank)
+    if hi - lo != T:
+        raise ValueError(f"{who}: rank {rank} holds {T} frames, shard_bounds gives it [{lo}, {hi})")
+    return lo == 0 and hi > lo
+
+
+def _lanes(block):
+    """Lanes of a frame-major block [T, ...]: the product of the trailing dimensions."""
+    n = 1
+    for d in block.shape[1:]:
+        n *= int(d)
+    return n
+
+
 def gather_track(local, F_total, group=None):
     """local: this rank's [n_local, ...] block (n_local <= per).  Returns the full [F_total, ...]
     tensor on every rank with ONE all_gather_into_tensor of equal, zero-padded blocks."""
@@ -485,13 +504,11 @@ def tracked_counts(count_local, F_total, n_slots, group=None, flag_bits=0):
     left waiting in a collective.  Raises ValueError on every rank if frame 0 holds more persons than the track has slots."""
     import torch
     import torch.distributed as dist
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    lo, hi, _ = shard_bounds(int(F_total), world, rank)
-    if hi - lo != int(count_local.shape[0]):
-        raise ValueError(f"tracked_counts: rank {rank} holds {int(count_local.shape[0])} frames, shard_bounds gives it [{lo}, {hi})")
+    world = dist.get_world_size(group)
+    first = _starts_track("tracked_counts", int(count_local.shape[0]), F_total, group)
     dev = count_local.device
     mine = torch.zeros(3, dtype=torch.int32, device=dev)
-    if lo == 0 and hi > 0:
+    if first:
         mine[0] = 1
         mine[1] = count_local[0]
     mine[2] = flag_bits.to(device=dev, dtype=torch.int32) if torch.is_tensor(flag_bits) else int(flag_bits)
@@ -568,30 +585,32 @@ def smooth_exchange(x_local, local_fn, combine_fn, fix_fn, group=None, first=Non
     layout of shard_bounds, where only TRAILING blocks can be empty.  snowtri_smooth_shard_combine treats the first
     NON-EMPTY payload as the start of the track, so a caller with an empty leading block must pass first=True on the
     rank that holds the first frames (include/snowtri.h states the same contract)."""
+    return _smooth_exchange(x_local, lambda is_first, y, payload: local_fn(x_local, is_first, y, payload), combine_fn,
+                            lambda is_first, start, y: fix_fn(y, is_first, start), group, first)
+
+
+def _smooth_exchange(x_local, before_fn, combine_fn, after_fn, group, first):
+    """The exchange under both forms of the protocol: before_fn(first, y, payload) leaves the block's zero-state end state in
+    payload[:2n] (and may write y), ONE all-gather, combine_fn(allp, rank, start), after_fn(first, start, y) completes y."""
     import torch
     import torch.distributed as dist
     rank, world = dist.get_rank(group), dist.get_world_size(group)
-    T = int(x_local.shape[0])
-    n = 1
-    for d in x_local.shape[1:]:
-        n *= int(d)
-    if first is None:
-        first = rank == 0
+    T, n = int(x_local.shape[0]), _lanes(x_local)
+    first = rank == 0 if first is None else bool(first)
     y = torch.empty_like(x_local)
     payload = torch.zeros(4 * n + 1, dtype=torch.float64, device=x_local.device)
     payload[4 * n] = T
     if T > 0:
-        local_fn(x_local, bool(first), y, payload)
+        before_fn(first, y, payload)
         payload[2 * n:3 * n] = x_local[0].reshape(-1)
         payload[3 * n:4 * n] = x_local[-1].reshape(-1)
     flat = torch.empty(world * (4 * n + 1), dtype=torch.float64, device=x_local.device)
     all_gather_flat(flat, payload, group=group)                         # the one exchange: 4n+1 doubles per rank
-    allp = flat.view(world, 4 * n + 1)
     if T == 0:
         return y
     start = torch.empty((n, 2), dtype=torch.float64, device=x_local.device)
-    combine_fn(allp, rank, start)
-    fix_fn(y, bool(first), start)
+    combine_fn(flat.view(world, 4 * n + 1), rank, start)
+    after_fn(first, start, y)
     return y
 
 
@@ -604,30 +623,31 @@ def smooth_exchange2(x_local, reduce_fn, combine_fn, scan_fn, group=None, first=
         scan_fn(x_local, first, start, y)    y = the block filtered from its true entering state (x read once, y written once)
 
     Same payload, same ONE all-gather, same `first` contract as smooth_exchange."""
-    import torch
-    import torch.distributed as dist
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    T = int(x_local.shape[0])
-    n = 1
-    for d in x_local.shape[1:]:
-        n *= int(d)
-    if first is None:
-        first = rank == 0
-    y = torch.empty_like(x_local)
-    payload = torch.zeros(4 * n + 1, dtype=torch.float64, device=x_local.device)
-    payload[4 * n] = T
-    if T > 0:
-        reduce_fn(x_local, bool(first), payload)
-        payload[2 * n:3 * n] = x_local[0].reshape(-1)
-        payload[3 * n:4 * n] = x_local[-1].reshape(-1)
-    flat = torch.empty(world * (4 * n + 1), dtype=torch.float64, device=x_local.device)
-    all_gather_flat(flat, payload, group=group)
-    if T == 0:
-        return y
-    start = torch.empty((n, 2), dtype=torch.float64, device=x_local.device)
-    combine_fn(flat.view(world, 4 * n + 1), rank, start)
-    scan_fn(x_local, bool(first), start, y)
-    return y
+    return _smooth_exchange(x_local, lambda is_first, y, payload: reduce_fn(x_local, is_first, payload), combine_fn,
+                            lambda is_first, start, y: scan_fn(x_local, is_first, start, y), group, first)
+
+
+def _bind_shard_passes(ctx, prefix, lanes, coef, world, stream, memspace=()):
+    """(reduce_fn, combine_fn, scan_fn) of smooth_exchange2 bound to the C ABI entries `prefix`_reduce / _combine / _scan on the
+    shard's GPU.  lanes: the entries' lane argument (n, or n_persons); coef: their coefficient arguments, which both families
+    take in the same slot of every pass; memspace: (DEVICE,) for the uniform _combine, the one entry here that takes one."""
+    from . import _lib
+
+    def call(name, *args):
+        _lib.check(getattr(ctx.L, prefix + name)(ctx.handle, *args), prefix + name)
+
+    def reduce_fn(x, is_first, payload):
+        call("_reduce", int(x.shape[0]), lanes, _lib.ptr(x), 1 if is_first else 0, *coef, _lib.ptr(payload), stream)
+
+    def combine_fn(allp, rk, start):
+        # the entering state of this shard from the gathered carries, ON the device and the stream (k_smooth_combine: no host
+        # round trip between the all-gather and the scan; combine_carries above is its host twin)
+        call("_combine", world, rk, lanes, _lib.ptr(allp), *coef, _lib.ptr(start), *memspace, stream)
+
+    def scan_fn(x, is_first, start, y):
+        call("_scan", int(x.shape[0]), lanes, _lib.ptr(x), 1 if is_first else 0, _lib.ptr(start), *coef, _lib.ptr(y), stream)
+
+    return reduce_fn, combine_fn, scan_fn
 
 
 def smooth_track_sharded(x_local, f=2, z=0.75, r=0, delta_time=1 / 30, group=None, ctx=None, F_total=None, first=None):
@@ -640,35 +660,13 @@ def smooth_track_sharded(x_local, f=2, z=0.75, r=0, delta_time=1 / 30, group=Non
     import torch.distributed as dist
     from . import _lib
     assert x_local.is_cuda and x_local.dtype == torch.float64 and x_local.is_contiguous()
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
     if F_total is not None:
-        lo, hi, _ = shard_bounds(int(F_total), world, rank)
-        if hi - lo != int(x_local.shape[0]):
-            raise ValueError(f"smooth_track_sharded: rank {rank} holds {int(x_local.shape[0])} frames, shard_bounds gives it [{lo}, {hi})")
-        first = lo == 0 and hi > lo
-    n = 1
-    for d in x_local.shape[1:]:
-        n *= int(d)
+        first = _starts_track("smooth_track_sharded", int(x_local.shape[0]), F_total, group)
     ctx = ctx or _lib.scratch_context(x_local.device.index)     # scratch and kernels on the GPU that holds the shard
     stream = _lib.ptr(torch.cuda.current_stream(x_local.device).cuda_stream)
-    L = ctx.L
-    fzrd = (float(f), float(z), float(r), float(delta_time))
-
-    def reduce_fn(x, is_first, payload):
-        _lib.check(L.snowtri_smooth_shard_reduce(ctx.handle, int(x.shape[0]), n, _lib.ptr(x), 1 if is_first else 0, *fzrd,
-                                                 _lib.ptr(payload), stream), "snowtri_smooth_shard_reduce")
-
-    def combine_fn(allp, rk, start):
-        # the entering state of this shard from the gathered carries, ON the device and the stream (k_smooth_combine: no host
-        # round trip between the all-gather and the fix; combine_carries above is its host twin)
-        _lib.check(L.snowtri_smooth_shard_combine(ctx.handle, world, rk, n, _lib.ptr(allp), *fzrd,
-                                                  _lib.ptr(start), _lib.DEVICE, stream), "snowtri_smooth_shard_combine")
-
-    def scan_fn(x, is_first, start, y):
-        _lib.check(L.snowtri_smooth_shard_scan(ctx.handle, int(x.shape[0]), n, _lib.ptr(x), 1 if is_first else 0,
-                                               _lib.ptr(start), *fzrd, _lib.ptr(y), stream), "snowtri_smooth_shard_scan")
-
-    return smooth_exchange2(x_local, reduce_fn, combine_fn, scan_fn, group=group, first=first)
+    passes = _bind_shard_passes(ctx, "snowtri_smooth_shard", _lanes(x_local), (float(f), float(z), float(r), float(delta_time)),
+                                dist.get_world_size(group), stream, memspace=(_lib.DEVICE,))
+    return smooth_exchange2(x_local, *passes, group=group, first=first)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -711,10 +709,7 @@ def blender_smooth_sharded(pts_local, val_local, fzr, delta_time=1 / 30, group=N
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     T, P = int(pts_local.shape[0]), int(pts_local.shape[1])
     if F_total is not None:
-        lo, hi, _ = shard_bounds(int(F_total), world, rank)
-        if hi - lo != T:
-            raise ValueError(f"blender_smooth_sharded: rank {rank} holds {T} frames, shard_bounds gives it [{lo}, {hi})")
-        first = lo == 0 and hi > lo
+        first = _starts_track("blender_smooth_sharded", T, F_total, group)
     ctx = ctx or _lib.scratch_context(pts_local.device.index)
     stream = _lib.ptr(torch.cuda.current_stream(pts_local.device).cuda_stream)
     L = ctx.L
@@ -732,20 +727,8 @@ def blender_smooth_sharded(pts_local, val_local, fzr, delta_time=1 / 30, group=N
 
     held = hold_exchange(pts_local, val_local, last_fn, apply_fn, group=group)
 
-    def reduce_fn(x, is_first, payload):
-        _lib.check(L.snowtri_blender_smooth_shard_reduce(ctx.handle, int(x.shape[0]), P, _lib.ptr(x), 1 if is_first else 0,
-                                                         _lib.ptr(fzr), dt, _lib.ptr(payload), stream), "snowtri_blender_smooth_shard_reduce")
-
-    def combine_fn(allp, rk, start):
-        _lib.check(L.snowtri_blender_smooth_shard_combine(ctx.handle, world, rk, P, _lib.ptr(allp), _lib.ptr(fzr), dt,
-                                                          _lib.ptr(start), stream), "snowtri_blender_smooth_shard_combine")
-
-    def scan_fn(x, is_first, start, y):
-        _lib.check(L.snowtri_blender_smooth_shard_scan(ctx.handle, int(x.shape[0]), P, _lib.ptr(x), 1 if is_first else 0,
-                                                       _lib.ptr(start), _lib.ptr(fzr), dt, _lib.ptr(y), stream),
-                   "snowtri_blender_smooth_shard_scan")
-
-    y = smooth_exchange2(held, reduce_fn, combine_fn, scan_fn, group=group, first=first)
+    passes = _bind_shard_passes(ctx, "snowtri_blender_smooth_shard", P, (_lib.ptr(fzr), dt), world, stream)
+    y = smooth_exchange2(held, *passes, group=group, first=first)
     is_first = (rank == 0) if first is None else first
     if is_first and T > 0:
         y[0].copy_(pts_local[0])       # frame 0 of the track is returned as given, NaNs included (blender.py:176)

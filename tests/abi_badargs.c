@@ -7,7 +7,8 @@
  *   - with a GPU (tests/test_gpu_parity.py runs it against libsnowtri.so): the same plus, on a real context,
  *     wrong shapes / dtype codes / memory spaces / method, center_point_index and keypoint_num out of range,
  *     missing required pointers, a camera index out of range, too few Blender joints, a singular K, and every refusal of
- *     the two record passes (gap filling, despiking) that comes before a launch.
+ *     the two record passes (gap filling, despiking) and of the smoothing passes (uniform and per-bone) that comes before
+ *     a launch.
  * Exit code = number of failed expectations; prints each failure.
  */
 #include <stdint.h>
@@ -274,6 +275,155 @@ int main(void) {
 #undef FILL
 #undef DESPIKE
             EXPECT(out[0] == 0.0f && bbuf[0] == 0, 1);   /* nothing was written */
+        }
+        {   /* the smoothing passes, uniform (N1) and per-bone (N2): every refusal comes before anything is enqueued or written,
+               and an empty shard is SNOWTRI_OK before a pointer is looked at.  (Every call below is refused or empty: the
+               per-bone entries take DEVICE pointers, and these are host arrays.) */
+            double *x = buf, *y = buf + 1024, *st = buf + 2048, *g = buf + 2560;   /* track in, track out, a state, gathered payloads */
+            const int H = SNOWTRI_HOST;
+            const int BAD = SNOWTRI_ERR_BAD_ARG;
+            const double dt = 1.0 / 30;
+            volatile double zero = 0.0;
+            const double nan = zero / zero;
+            double good[72], bad0[72], badnan[72];
+            int i;
+            memset(buf, 0, sizeof buf);
+            for (i = 0; i < 24; i++) {
+                good[3 * i] = 2.5;
+                good[3 * i + 1] = 0.75;
+                good[3 * i + 2] = 0.0;
+            }
+            memcpy(bad0, good, sizeof good);
+            memcpy(badnan, good, sizeof good);
+            bad0[3 * 7] = 0.0;
+            badnan[3 * 23] = nan;
+#define UL(T_, n_, x_, f_, dt_, y_, e_, ms_) snowtri_smooth_shard_local(ctx, T_, n_, x_, 1, f_, 0.75, 0.0, dt_, y_, e_, ms_, NULL)
+#define UF(T_, n_, s_, f_, dt_, y_, ms_) snowtri_smooth_shard_fix(ctx, T_, n_, 1, s_, f_, 0.75, 0.0, dt_, y_, ms_, NULL)
+#define UR(T_, n_, x_, f_, dt_, e_) snowtri_smooth_shard_reduce(ctx, T_, n_, x_, 1, f_, 0.75, 0.0, dt_, e_, NULL)
+#define US(T_, n_, x_, s_, f_, dt_, y_) snowtri_smooth_shard_scan(ctx, T_, n_, x_, 1, s_, f_, 0.75, 0.0, dt_, y_, NULL)
+#define UC(w_, r_, n_, g_, f_, dt_, s_, ms_) snowtri_smooth_shard_combine(ctx, w_, r_, n_, g_, f_, 0.75, 0.0, dt_, s_, ms_, NULL)
+#define BL(T_, P_, x_, fzr_, dt_, y_, e_) snowtri_blender_smooth_shard_local(ctx, T_, P_, x_, 1, fzr_, dt_, y_, e_, NULL)
+#define BF(T_, P_, s_, fzr_, dt_, y_) snowtri_blender_smooth_shard_fix(ctx, T_, P_, 1, s_, fzr_, dt_, y_, NULL)
+#define BR(T_, P_, x_, fzr_, dt_, e_) snowtri_blender_smooth_shard_reduce(ctx, T_, P_, x_, 1, fzr_, dt_, e_, NULL)
+#define BS(T_, P_, x_, s_, fzr_, dt_, y_) snowtri_blender_smooth_shard_scan(ctx, T_, P_, x_, 1, s_, fzr_, dt_, y_, NULL)
+#define BC(w_, r_, P_, g_, fzr_, dt_, s_) snowtri_blender_smooth_shard_combine(ctx, w_, r_, P_, g_, fzr_, dt_, s_, NULL)
+#define BW(T_, P_, p_, v_, fzr_, dt_, o_, ms_) snowtri_blender_smooth(ctx, T_, P_, p_, v_, fzr_, dt_, o_, ms_, NULL)
+/* the per-bone entries with every array given: (T, persons, table, dt) must be what is wrong */
+#define BONE_REFUSE(T_, P_, fzr_, dt_)                                                                       \
+    do {                                                                                                     \
+        EXPECT(BL(T_, P_, x, fzr_, dt_, y, st), BAD);                                                        \
+        EXPECT(BF(T_, P_, st, fzr_, dt_, y), BAD);                                                           \
+        EXPECT(BR(T_, P_, x, fzr_, dt_, st), BAD);                                                           \
+        EXPECT(BS(T_, P_, x, st, fzr_, dt_, y), BAD);                                                        \
+        EXPECT(BW(T_, P_, x, bbuf, fzr_, dt_, y, H), BAD);                                                   \
+    } while (0)
+/* ... and the uniform ones beside them: (T, n / persons, f / table, dt) must be wrong for BOTH families */
+#define BOTH_REFUSE(T_, n_, P_, f_, fzr_, dt_)                                                               \
+    do {                                                                                                     \
+        EXPECT(UL(T_, n_, x, f_, dt_, y, st, H), BAD);                                                       \
+        EXPECT(UF(T_, n_, st, f_, dt_, y, H), BAD);                                                          \
+        EXPECT(UR(T_, n_, x, f_, dt_, st), BAD);                                                             \
+        EXPECT(US(T_, n_, x, st, f_, dt_, y), BAD);                                                          \
+        BONE_REFUSE(T_, P_, fzr_, dt_);                                                                      \
+    } while (0)
+/* the two _combine entries (they take no T) */
+#define COMBINE_REFUSE(w_, r_, n_, P_, f_, fzr_, dt_)                                                        \
+    do {                                                                                                     \
+        EXPECT(UC(w_, r_, n_, g, f_, dt_, st, H), BAD);                                                      \
+        EXPECT(BC(w_, r_, P_, g, fzr_, dt_, st), BAD);                                                       \
+    } while (0)
+            BOTH_REFUSE(-1, 3, 1, 2.5, good, dt);                                /* T < 0 */
+            BOTH_REFUSE(4, -1, -1, 2.5, good, dt);                               /* n, n_persons < 0 */
+            COMBINE_REFUSE(2, 1, -1, -1, 2.5, good, dt);
+            BOTH_REFUSE(4, 3, 1, 0.0, bad0, dt);                                 /* f <= 0 (one row of the table) */
+            COMBINE_REFUSE(2, 1, 3, 1, 0.0, bad0, dt);
+            BOTH_REFUSE(4, 3, 1, -2.0, bad0, dt);
+            BOTH_REFUSE(4, 3, 1, nan, badnan, dt);                               /* f is NaN */
+            COMBINE_REFUSE(2, 1, 3, 1, nan, badnan, dt);
+            BOTH_REFUSE(4, 3, 1, 2.5, good, 0.0);                                /* dt <= 0 */
+            COMBINE_REFUSE(2, 1, 3, 1, 2.5, good, 0.0);
+            BOTH_REFUSE(4, 3, 1, 2.5, good, -dt);
+            COMBINE_REFUSE(2, 1, 3, 1, 2.5, good, -dt);
+            BONE_REFUSE(4, 1, NULL, dt);                                         /* no table */
+            EXPECT(BC(2, 1, 1, g, NULL, dt, st), BAD);
+            BONE_REFUSE(0, 1, NULL, dt);                                         /* no table / a bad row even on an empty shard */
+            BONE_REFUSE(4, 0, NULL, dt);
+            BONE_REFUSE(0, 1, bad0, dt);
+            BONE_REFUSE(4, 0, bad0, dt);
+            EXPECT(BC(2, 1, 0, g, NULL, dt, st), BAD);
+            EXPECT(BC(2, 1, 0, g, bad0, dt, st), BAD);
+            EXPECT(UL(4, 3, x, 2.5, dt, y, st, 5), BAD);                         /* an unknown memory space */
+            EXPECT(UF(4, 3, st, 2.5, dt, y, 5), BAD);
+            EXPECT(UC(2, 1, 3, g, 2.5, dt, st, 5), BAD);
+            EXPECT(BW(4, 1, x, bbuf, good, dt, y, 5), BAD);
+            COMBINE_REFUSE(0, 0, 3, 1, 2.5, good, dt);                           /* world < 1, rank outside [0, world) ... */
+            COMBINE_REFUSE(2, -1, 3, 1, 2.5, good, dt);
+            COMBINE_REFUSE(2, 2, 3, 1, 2.5, good, dt);
+            COMBINE_REFUSE(0, 0, 0, 0, 2.5, good, dt);                           /* ... with no lanes too */
+            COMBINE_REFUSE(2, -1, 0, 0, 2.5, good, dt);
+            COMBINE_REFUSE(2, 2, 0, 0, 2.5, good, dt);
+            /* an empty shard (no frames, or no lanes): no pointer is looked at */
+            EXPECT(UL(0, 3, NULL, 2.5, dt, NULL, NULL, H), SNOWTRI_OK);
+            EXPECT(UL(4, 0, NULL, 2.5, dt, NULL, NULL, H), SNOWTRI_OK);
+            EXPECT(UF(0, 3, NULL, 2.5, dt, NULL, H), SNOWTRI_OK);
+            EXPECT(UF(4, 0, NULL, 2.5, dt, NULL, H), SNOWTRI_OK);
+            EXPECT(UR(0, 3, NULL, 2.5, dt, NULL), SNOWTRI_OK);
+            EXPECT(UR(4, 0, NULL, 2.5, dt, NULL), SNOWTRI_OK);
+            EXPECT(US(0, 3, NULL, NULL, 2.5, dt, NULL), SNOWTRI_OK);
+            EXPECT(US(4, 0, NULL, NULL, 2.5, dt, NULL), SNOWTRI_OK);
+            EXPECT(UC(2, 1, 0, NULL, 2.5, dt, NULL, H), SNOWTRI_OK);
+            EXPECT(BL(0, 1, NULL, good, dt, NULL, NULL), SNOWTRI_OK);
+            EXPECT(BL(4, 0, NULL, good, dt, NULL, NULL), SNOWTRI_OK);
+            EXPECT(BF(0, 1, NULL, good, dt, NULL), SNOWTRI_OK);
+            EXPECT(BF(4, 0, NULL, good, dt, NULL), SNOWTRI_OK);
+            EXPECT(BR(0, 1, NULL, good, dt, NULL), SNOWTRI_OK);
+            EXPECT(BR(4, 0, NULL, good, dt, NULL), SNOWTRI_OK);
+            EXPECT(BS(0, 1, NULL, NULL, good, dt, NULL), SNOWTRI_OK);
+            EXPECT(BS(4, 0, NULL, NULL, good, dt, NULL), SNOWTRI_OK);
+            EXPECT(BC(2, 1, 0, NULL, good, dt, NULL), SNOWTRI_OK);
+            EXPECT(BW(0, 1, NULL, NULL, good, dt, NULL, H), SNOWTRI_OK);
+            EXPECT(BW(4, 0, NULL, NULL, good, dt, NULL, H), SNOWTRI_OK);
+            /* each required array missing */
+            EXPECT(UL(4, 3, NULL, 2.5, dt, y, st, H), BAD);
+            EXPECT(UL(4, 3, x, 2.5, dt, NULL, st, H), BAD);
+            EXPECT(UF(4, 3, NULL, 2.5, dt, y, H), BAD);
+            EXPECT(UF(4, 3, st, 2.5, dt, NULL, H), BAD);
+            EXPECT(UR(4, 3, NULL, 2.5, dt, st), BAD);
+            EXPECT(UR(4, 3, x, 2.5, dt, NULL), BAD);
+            EXPECT(US(4, 3, NULL, st, 2.5, dt, y), BAD);
+            EXPECT(US(4, 3, x, NULL, 2.5, dt, y), BAD);
+            EXPECT(US(4, 3, x, st, 2.5, dt, NULL), BAD);
+            EXPECT(UC(2, 1, 3, NULL, 2.5, dt, st, H), BAD);
+            EXPECT(UC(2, 1, 3, g, 2.5, dt, NULL, H), BAD);
+            EXPECT(BL(4, 1, NULL, good, dt, y, st), BAD);
+            EXPECT(BL(4, 1, x, good, dt, NULL, st), BAD);
+            EXPECT(BF(4, 1, NULL, good, dt, y), BAD);
+            EXPECT(BF(4, 1, st, good, dt, NULL), BAD);
+            EXPECT(BR(4, 1, NULL, good, dt, st), BAD);
+            EXPECT(BR(4, 1, x, good, dt, NULL), BAD);
+            EXPECT(BS(4, 1, NULL, st, good, dt, y), BAD);
+            EXPECT(BS(4, 1, x, NULL, good, dt, y), BAD);
+            EXPECT(BS(4, 1, x, st, good, dt, NULL), BAD);
+            EXPECT(BC(2, 1, 1, NULL, good, dt, st), BAD);
+            EXPECT(BC(2, 1, 1, g, good, dt, NULL), BAD);
+            EXPECT(BW(4, 1, NULL, bbuf, good, dt, y, H), BAD);
+            EXPECT(BW(4, 1, x, NULL, good, dt, y, H), BAD);
+            EXPECT(BW(4, 1, x, bbuf, good, dt, NULL, H), BAD);
+#undef UL
+#undef UF
+#undef UR
+#undef US
+#undef UC
+#undef BL
+#undef BF
+#undef BR
+#undef BS
+#undef BC
+#undef BW
+#undef BONE_REFUSE
+#undef BOTH_REFUSE
+#undef COMBINE_REFUSE
+            EXPECT(y[0] == 0.0 && st[0] == 0.0, 1);   /* nothing was written */
         }
         EXPECT(snowtri_ctx_destroy(ctx), SNOWTRI_OK);
     }
