@@ -79,7 +79,7 @@ class TrackPipeline:
         fill_gaps == 0 it becomes the window median (DESPIKE_REPLACE), since without a filler a marked spike would reach the filter
         as a position at the origin.  Adds spike_codes [F, P, kn] (uint8, despike.DESPIKE_*) and xyzs_despiked [F, P, kn, 4], the
         records the fill (or the filters) consumed; outside every filtered sequence: the records of xyzs, DESPIKE_MISSING or
-        DESPIKE_UNSUPPORTED (untested).  None (the default): off, nothing changes and no extra key appears.
+        DESPIKE_UNSUPPORTED.  None (the default): off, nothing changes and no extra key appears.
         reproject=gate_px: how the views agree with the result.  res["xyzs"] (whatever indexes it: list order, or slots with
         ragged="track") is projected back into every camera and compared with the keypoints the caller passed -- on the RAW frame
         when the pipeline was built with D, so no undistorted copy is made: reproject.match_detections on k_reproject_cost with
