@@ -24,6 +24,8 @@ DESPIKE_KEPT, DESPIKE_SPIKE, DESPIKE_MISSING, DESPIKE_UNSUPPORTED = 0, 1, 2, 3  
 REPROJECT_RAW = 1              # snowtri_reproject / snowtri_reproject_cost: flags -- pixels on the raw (distorted) frame
 REFINE_SCORE_WEIGHTS = 1       # snowtri_refine_joints: flags -- a view weighs its observation's score
 REFINE_MISSING, REFINE_FEW_VIEWS, REFINE_KEPT, REFINE_MOVED = 0, 1, 2, 3   # ... and its codes
+POSE_FIXED, POSE_FEW_OBS, POSE_KEPT, POSE_MOVED = 0, 1, 2, 3   # snowtri_refine_cameras: codes
+POSE_SWEEP_RECORDS = 1024 * 256   # ... and the records one sweep of k_pose_normal's grid covers (snowtri_pose_sweep_records)
 CALL_NO_ZERO_FILL = 1         # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
 TEST_LIB_PATH = os.path.join(_HERE, "libsnowtri_dbg.so")   # -DSNOWTRI_DEBUG_BOUNDS -DSNOWTRI_TEST_KNOBS (tests only: use_library)
 
@@ -143,6 +145,10 @@ _SIGNATURES = {
                                           ct.c_double, ct.c_uint32, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_refine_joints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                          ct.c_double, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_pose_sweep_records": (ct.c_int, []),
+    "snowtri_refine_cameras": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
+                                          ct.c_double, ct.c_uint32, ct.c_int32, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                          ct.c_int, _c_p]),
     "snowtri_last_kernel_ms": (ct.c_int, [_c_p, ct.POINTER(ct.c_float * 2)]),
     "snowtri_set_timing": (ct.c_int, [_c_p, ct.c_int]),
     "snowtri_timing_collect": (ct.c_int, [_c_p, _c_p, ct.c_int32]),
@@ -254,6 +260,31 @@ def host_floats(a):
     return np.ascontiguousarray(a)
 
 
+def free_mask(free, C):
+    """Which cameras may move, as snowtri_refine_cameras' bit mask: None (all C), an int mask, a sequence of C booleans, or a
+    sequence of camera indices."""
+    if free is None:
+        return (1 << C) - 1
+    if isinstance(free, (int, np.integer)) and not isinstance(free, (bool, np.bool_)):
+        mask = int(free)
+    else:
+        a = np.asarray(free)
+        if a.dtype == bool:
+            if a.shape != (C,):
+                raise ValueError(f"free as booleans must have one entry per camera ({C})")
+            idx = np.nonzero(a)[0]
+        else:
+            idx = a.astype(np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= C or (a != idx.reshape(a.shape)).any()):
+                raise ValueError(f"free names a camera outside 0..{C - 1}")
+        mask = 0
+        for c in idx:
+            mask |= 1 << int(c)
+    if mask < 0 or mask >> C:
+        raise ValueError(f"free has a bit at or above the number of cameras ({C})")
+    return mask
+
+
 class Space:
     """Where the arrays of one wrapper call live: on the host (NumPy arrays, staged by the library, synchronous) or on one CUDA device
     (torch tensors, used in place and asynchronously on `stream`, default torch's current stream of that device).  Made from the call's
@@ -300,7 +331,7 @@ class Space:
         return a
 
     def empty(self, shape, kind):
-        """An uninitialised output: kind = "float32", "float64", "int32", "uint8", or "flags" (uint32 on the host, int32 in torch)."""
+        """An uninitialised output: kind = "float32", "float64", "int32", "int64", "uint8", or "flags" (uint32 on the host, int32 in torch)."""
         if kind == "flags":
             kind = "uint32" if self.device is None else "int32"
         if self.device is None:
@@ -428,18 +459,9 @@ class Context:
         self._reproject_status(rc, "snowtri_reproject_cost")
         return cs, cn
 
-    def refine_joints(self, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4,
-                      score_weights=False, diagnostics=False, out=None, stream=None):
-        """Joint records xyzs [F, P, kn, 4] moved to a local minimum of their reprojection error against the detections kpts
-        [F, C, Pmax, kn, 3] on the undistorted frame (include/snowtri.h, "Refinement"; at most `iters` Gauss-Newton steps, a record's
-        cost never rises, scores untouched).  det_of [F, C, P]: the detection of camera c that shows person p (match_detections'
-        int64 is handed on as int32; -1: none; None: detection p).  n_persons [F, C] int32 or None.  views [F, P, kn]: bit c = camera
-        c may be used (the uint32 / torch int32 mask of DLT_ROBUST's diagnostics; None: every camera).  score_weights: a view weighs
-        its observation's score instead of 1.  Host arrays, or contiguous CUDA tensors (all of them) used in place and
-        asynchronously on `stream`.  out: xyzs itself refines in place (default: a new array).
-        -> the refined records, or (records, cost [F, P, kn, 2] float64: E before and after, codes [F, P, kn] uint8: REFINE_*)
-        with diagnostics=True."""
-        space = Space("Context.refine_joints", xyzs, kpts, n_persons, det_of, views, stream=stream)
+    def _refine_in(self, space, xyzs, kpts, n_persons, det_of, views, iters):
+        """The inputs refine_joints and refine_cameras share, checked in `space` ->
+        (xyzs, its dtype code, F, P, kn, kpts, its dtype code, Pmax, n_persons, det_of, views)."""
         xyzs, code, F, P, kn = self._records_in(space, xyzs)
         if len(kpts.shape) != 5 or tuple(kpts.shape[:2]) != (F, self.C) or tuple(kpts.shape[3:]) != (kn, 3):
             raise ValueError(f"kpts must be [F={F}, C={self.C}, Pmax, kn={kn}, 3] (got shape {tuple(kpts.shape)})")
@@ -457,9 +479,24 @@ class Context:
             if space.device is None:
                 views = np.ascontiguousarray(views)
                 if views.dtype not in (np.uint32, np.int32) or views.shape != (F, P, kn):
-                    raise ValueError(f"views given to Context.refine_joints must be uint32 of shape {(F, P, kn)} (got {views.dtype} {views.shape})")
+                    raise ValueError(f"views given to {space.who} must be uint32 of shape {(F, P, kn)} (got {views.dtype} {views.shape})")
             else:
                 views = space.ints(views, (F, P, kn), "views")
+        return xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views
+
+    def refine_joints(self, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4,
+                      score_weights=False, diagnostics=False, out=None, stream=None):
+        """Joint records xyzs [F, P, kn, 4] moved to a local minimum of their reprojection error against the detections kpts
+        [F, C, Pmax, kn, 3] on the undistorted frame (include/snowtri.h, "Refinement"; at most `iters` Gauss-Newton steps, a record's
+        cost never rises, scores untouched).  det_of [F, C, P]: the detection of camera c that shows person p (match_detections'
+        int64 is handed on as int32; -1: none; None: detection p).  n_persons [F, C] int32 or None.  views [F, P, kn]: bit c = camera
+        c may be used (the uint32 / torch int32 mask of DLT_ROBUST's diagnostics; None: every camera).  score_weights: a view weighs
+        its observation's score instead of 1.  Host arrays, or contiguous CUDA tensors (all of them) used in place and
+        asynchronously on `stream`.  out: xyzs itself refines in place (default: a new array).
+        -> the refined records, or (records, cost [F, P, kn, 2] float64: E before and after, codes [F, P, kn] uint8: REFINE_*)
+        with diagnostics=True."""
+        space = Space("Context.refine_joints", xyzs, kpts, n_persons, det_of, views, stream=stream)
+        xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views = self._refine_in(space, xyzs, kpts, n_persons, det_of, views, iters)
         if out is None:
             out = space.empty_like(xyzs)
         elif out is not xyzs:
@@ -471,6 +508,32 @@ class Context:
                                           ptr(cost), ptr(codes), *space.tail())
         self._reproject_status(rc, "snowtri_refine_joints")
         return (out, cost, codes) if diagnostics else out
+
+    def refine_cameras(self, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None, min_obs=64,
+                       iters=8, score_weights=False, diagnostics=False, stream=None):
+        """The rig's poses moved to a local minimum of every free camera's reprojection error against the detections kpts
+        [F, C, Pmax, kn, 3] on the undistorted frame, the joint records xyzs [F, P, kn, 4] held fixed (include/snowtri.h, "Camera pose
+        refinement"; at most `iters` Gauss-Newton steps on six parameters per camera, a camera's cost never rises).  det_of, n_persons,
+        views, keypoint_score_threshold, score_weights: as for refine_joints.  free: the cameras that may move -- None (all), a bit
+        mask, or a sequence of camera indices / of C booleans; a camera with fewer than min_obs (>= 3) observations stays.  Host
+        arrays, or contiguous CUDA tensors (all of them) used in place and asynchronously on `stream`; ONE call in flight per context.
+        THE CONTEXT'S RIG IS NOT CHANGED: build a new Context from what is returned.
+        -> (R [C, 3, 3], t [C, 3]) float64, or (R, t, report) with diagnostics=True: report = dict(cost [C, 2]: E before and after,
+        n_obs [C] int64, codes [C] uint8: POSE_*, normal [C, 28]: E, g[6], H[21] at the input pose)."""
+        space = Space("Context.refine_cameras", xyzs, kpts, n_persons, det_of, views, stream=stream)
+        xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views = self._refine_in(space, xyzs, kpts, n_persons, det_of, views, iters)
+        if int(min_obs) != min_obs:
+            raise ValueError(f"min_obs must be an integer >= 3 (got {min_obs})")
+        mask = free_mask(free, self.C)
+        R, t = space.empty((self.C, 3, 3), "float64"), space.empty((self.C, 3), "float64")
+        rep = dict(cost=space.empty((self.C, 2), "float64"), n_obs=space.empty((self.C,), "int64"), codes=space.empty((self.C,), "uint8"),
+                   normal=space.empty((self.C, 28), "float64")) if diagnostics else dict(cost=None, n_obs=None, codes=None, normal=None)
+        rc = self.L.snowtri_refine_cameras(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of), ptr(views),
+                                           float(keypoint_score_threshold), mask, int(min_obs), int(iters),
+                                           REFINE_SCORE_WEIGHTS if score_weights else 0, ptr(R), ptr(t), ptr(rep["cost"]), ptr(rep["n_obs"]),
+                                           ptr(rep["codes"]), ptr(rep["normal"]), *space.tail())
+        self._reproject_status(rc, "snowtri_refine_cameras")
+        return (R, t, rep) if diagnostics else (R, t)
 
     def set_timing(self, enabled=True, attach=False):
         """attach: single-kernel calls carry the event pair on their dispatch (the kernel's own begin / end) instead of being bracketed."""

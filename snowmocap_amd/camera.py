@@ -134,6 +134,26 @@ class CameraGroup:
         out = ctx.reproject(a[None] if single else a, raw=raw)
         return out[0] if single else out
 
+    def refine_poses(self, xyzs, kpts, **kwargs):
+        """Camera pose refinement (additive; include/snowtri.h, "Camera pose refinement"): a NEW CameraGroup whose R and t are this
+        rig's moved to a local minimum of every free camera's reprojection error of the joint records xyzs [F, P, kn, 4] against
+        the detections kpts [F, C, Pmax, kn, 3] on the UNDISTORTED frame; K, D and everything else are copied.  This group is left
+        untouched.  kwargs: those of pose.refine_cameras (det_of, n_persons, views, keypoint_score_threshold, free, min_obs, iters,
+        score_weights); with diagnostics=True -> (group, report).  Host arrays, like the other methods of the group."""
+        diagnostics = bool(kwargs.pop("diagnostics", False))
+        R, t, report = self.native_context().refine_cameras(np.asarray(xyzs), np.asarray(kpts), diagnostics=True, **kwargs)
+        n = self.camera_num
+        info = self.camera_group_info_dict()
+        group = CameraGroup(cap_ids=[], resolutions=[])
+        group.camera_num = n
+        group.cameras = [Camera(camera_info_dict=d) for d in info["camera_group_info"]]
+        for i, cam in enumerate(group.cameras):
+            cam._group, cam._index = group, i
+        for i, cam in enumerate(group.cameras[:n]):       # (the context holds the first camera_num cameras)
+            cam.R = np.array(R[i], dtype=np.float64).reshape(np.asarray(self.cameras[i].R).shape)
+            cam.t = np.array(t[i], dtype=np.float64).reshape(np.asarray(self.cameras[i].t).shape)
+        return (group, report) if diagnostics else group
+
     def camera_group_info_dict(self):
         return {"camera_num": self.camera_num,
                 "camera_group_info": [c.camera_info_dict() for c in self.cameras]}

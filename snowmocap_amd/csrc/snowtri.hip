@@ -34,6 +34,7 @@
 #include "snowtri_undistort.hpp"
 #include "snowtri_reproject.hpp"
 #include "snowtri_refine.hpp"
+#include "snowtri_pose.hpp"
 #include "snowtri_track.hpp"
 #include "snowtri_fill.hpp"
 #include "snowtri_despike.hpp"
@@ -114,7 +115,7 @@ struct Staging {
         size_t bytes, off;
         Kind kind;
     };
-    static constexpr int kMaxArrays = 8;
+    static constexpr int kMaxArrays = 12;
     Scratch &ins, &outs;
     const bool host;
     const hipStream_t st;
@@ -277,6 +278,7 @@ struct snowtri_ctx {
     Scratch &desc = sets[0].desc;             // cluster descriptors handed from k_frame_recompute / k_associate to k_cluster_fuse
     Scratch &sums = sets[0].sums;             // candidate sums of k_candidate_sums [frames][Kc] + the frames k_associate left behind
     Scratch in, out, aux;
+    double *pose_ws = nullptr;                // workspace of snowtri_refine_cameras (pose_ws_doubles(C)): allocated by the first call, by no later one
     Scratch track;                            // centres [F][Pout_max][4] fp64 of snowtri_track_persons (k_track_centres -> k_track_chain)
     hipEvent_t track_ev[3] = {nullptr, nullptr, nullptr};   // with timing on: before k_track_centres | between | behind k_track_chain
     bool track_ev_valid = false;
@@ -464,6 +466,9 @@ const char *snowtri_build_info(void) {
 #ifdef SNOWTRI_DEV_EXPERIMENTS
         add("SNOWTRI_DEV_EXPERIMENTS");
 #endif
+#ifdef SNOWTRI_POSE_PER_RECORD
+        add("SNOWTRI_POSE_PER_RECORD");
+#endif
 #ifdef SNOWTRI_LEAN_TRACE
         add("SNOWTRI_LEAN_TRACE");
 #endif
@@ -634,6 +639,7 @@ int snowtri_ctx_destroy(snowtri_ctx *ctx) {
     if (ctx->dP) (void)hipFree(ctx->dP);
     if (ctx->dLens) (void)hipFree(ctx->dLens);
     if (ctx->dProj) (void)hipFree(ctx->dProj);
+    if (ctx->pose_ws) (void)hipFree(ctx->pose_ws);
     if (ctx->dBlenderTab) (void)hipFree(ctx->dBlenderTab);
     for (auto &S : ctx->sets) {
         if (S.d_counters) (void)hipFree(S.d_counters);
@@ -2290,6 +2296,115 @@ int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, co
     else if (C == 8) launch_refine<8>(REFINE_ARGS);
     else launch_refine<0>(REFINE_ARGS);
 #undef REFINE_ARGS
+    HIP_TRY(hipGetLastError());
+    return sg.end();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------- camera pose refinement
+namespace {
+
+void launch_pose_normal(int xyz_dtype, int kpts_dtype, dim3 grid, hipStream_t st, int64_t n_rec, int C, int P, int Pmax, int kn, double kthr,
+                        uint32_t flags, const double *base, const double *trial, const int32_t *active, const void *dx, const void *dk,
+                        const int32_t *dnp, const int32_t *ddet, const uint32_t *dviews, double *partials) {
+#ifdef SNOWTRI_POSE_PER_RECORD   // (a development build: the shape that lost, EXPERIMENTS.md round 22)
+#define POSE_NORMAL k_pose_normal_rec
+    grid = dim3(grid.x);
+#else
+#define POSE_NORMAL k_pose_normal
+#endif
+#define LAUNCH_POSE(TX, TK)                                                                                                               \
+    hipLaunchKernelGGL((POSE_NORMAL<TX, TK>), grid, dim3(kPoseBlock), 0, st, n_rec, C, P, Pmax, kn, kthr, flags, base, trial, active, \
+                       (const TX *)dx, (const TK *)dk, dnp, ddet, dviews, partials)
+    if (xyz_dtype == SNOWTRI_F32) {
+        if (kpts_dtype == SNOWTRI_F32) LAUNCH_POSE(float, float);
+        else LAUNCH_POSE(float, double);
+    } else {
+        if (kpts_dtype == SNOWTRI_F32) LAUNCH_POSE(double, float);
+        else LAUNCH_POSE(double, double);
+    }
+#undef LAUNCH_POSE
+#undef POSE_NORMAL
+}
+
+}  // namespace
+
+extern "C" {
+
+int snowtri_pose_sweep_records(void) { return kPoseGridCap * kPoseBlock; }
+
+int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
+                           int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                           double keypoint_score_threshold, uint32_t free_mask, int32_t min_obs, int32_t iters, uint32_t flags, double *R_out,
+                           double *t_out, double *cost, int64_t *n_obs, uint8_t *codes, double *normal, int memspace, void *stream) {
+    const char *who = "snowtri_refine_cameras";
+    if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, 0u, kpts_dtype, memspace)) return rc;
+    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (flags & ~(uint32_t)SNOWTRI_REFINE_SCORE_WEIGHTS) return refuse("unknown flag bit");
+    if (Pmax < 1) return refuse("Pmax < 1");
+    if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
+    if (iters < 1 || iters > kRefineMaxIters) return refuse("iters must lie in 1..16");
+    if (min_obs < 3) return refuse("min_obs must be at least 3 (six parameters, two equations per observation)");
+    if (ctx->C > kRefineMaxCams) return refuse("more than 32 cameras (free_mask is a 32-bit mask)");
+    if (ctx->C < 32 && (free_mask >> ctx->C)) return refuse("free_mask has a bit at or above the number of cameras");
+    if (!det_of && P > Pmax) return refuse("det_of == NULL pairs person p with detection p: P must not exceed Pmax");
+    if (!R_out || !t_out) return refuse("null array (R_out or t_out)");
+    if (memspace == SNOWTRI_DEVICE && (((uintptr_t)R_out | (uintptr_t)t_out | (uintptr_t)cost | (uintptr_t)n_obs | (uintptr_t)normal) & 7u))
+        return refuse("R_out, t_out, cost, n_obs and normal must be aligned to their element size");
+    const int C = ctx->C;
+    int64_t n_rec = 0;
+    size_t x_bytes = 0, k_bytes = 0;
+    if (F > 0) {
+        const int64_t max_rec = (int64_t)0x7fffffff * kRefineBlock, per_frame = (int64_t)P * kn;   // (two int32: no overflow)
+        if (F > max_rec / per_frame) return refuse("F * P * kn must not exceed (2^31 - 1) * 256 records");
+        const int64_t per_view = (int64_t)Pmax * kn, cp = (int64_t)C * std::max(P, Pmax);
+        if (F > (((int64_t)1 << 56) / per_view) / C || F > ((int64_t)1 << 56) / cp)
+            return refuse("F * C * Pmax * kn and F * C * P must not exceed 2^56 elements");
+        if (!xyzs || !kpts) return refuse("null array (xyzs or kpts)");
+        const size_t xs = dtype_size(xyz_dtype), ks = dtype_size(kpts_dtype);
+        if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) & (xs - 1)) || (((uintptr_t)kpts) & (ks - 1)) ||
+                                           (((uintptr_t)n_persons | (uintptr_t)det_of | (uintptr_t)views) & 3u)))
+            return refuse("xyzs, kpts, n_persons, det_of and views must be aligned to their element size");
+        n_rec = F * per_frame;
+        x_bytes = xs * 4 * (size_t)n_rec;
+        k_bytes = ks * 3 * (size_t)F * C * (size_t)per_view;
+    }
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (!ctx->pose_ws) HIP_TRY(hipMalloc(&ctx->pose_ws, sizeof(double) * pose_ws_doubles(C)));   // the first call on this context, and no later one
+    const void *dx = F ? xyzs : nullptr, *dk = F ? kpts : nullptr;   // (an empty batch looks at no input pointer)
+    const int32_t *dnp = F ? n_persons : nullptr, *ddet = F ? det_of : nullptr;
+    const uint32_t *dviews = F ? views : nullptr;
+    double *dR = R_out, *dt = t_out, *d_cost = cost, *d_normal = normal;
+    int64_t *d_nobs = n_obs;
+    uint8_t *d_codes = codes;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dx, x_bytes);
+    sg.in(&dk, k_bytes);
+    sg.in(&dnp, sizeof(int32_t) * (size_t)F * C);
+    sg.in(&ddet, sizeof(int32_t) * (size_t)F * C * P);
+    sg.in(&dviews, sizeof(uint32_t) * (size_t)n_rec);
+    sg.out(&dR, sizeof(double) * 9 * (size_t)C);
+    sg.out(&dt, sizeof(double) * 3 * (size_t)C);
+    sg.out(&d_cost, sizeof(double) * 2 * (size_t)C);
+    sg.out(&d_nobs, sizeof(int64_t) * (size_t)C);
+    sg.out(&d_codes, (size_t)C);
+    sg.out(&d_normal, sizeof(double) * 28 * (size_t)C);
+    if (int rc = sg.begin()) return rc;
+    double *ws = ctx->pose_ws;
+    const double *base = (const double *)ctx->dProj;
+    const int G = n_rec ? grid_for(n_rec, kPoseBlock, kPoseGridCap) : 0;
+    const int n_eval = n_rec ? (int)iters : 0;   // evaluations behind the one at the input pose: 2 (iters + 1) launches whatever the data does
+    for (int e = 0; e <= n_eval; e++) {
+        if (G)
+            launch_pose_normal(xyz_dtype, kpts_dtype, dim3((unsigned)G, (unsigned)C), st, n_rec, C, (int)P, (int)Pmax, (int)kn,
+                               keypoint_score_threshold, flags, base, e ? ws + pose_ws_trial(C) : base,
+                               e ? reinterpret_cast<const int32_t *>(ws + pose_ws_active(C)) : nullptr, dx, dk, dnp, ddet, dviews,
+                               ws + pose_ws_partials(C));
+        hipLaunchKernelGGL(k_pose_step, dim3(1), dim3(kPoseStepBlock), 0, st, C, G, e, e == n_eval ? 1 : 0, free_mask, (int)min_obs, base, ws, dR, dt,
+                           d_cost, d_nobs, d_codes, d_normal);
+    }
     HIP_TRY(hipGetLastError());
     return sg.end();
 }

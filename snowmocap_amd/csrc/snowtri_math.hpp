@@ -22,6 +22,11 @@ namespace snowtri {
 //   SNOWTRI_DEV_EXPERIMENTS  gate of everything that is a measurement aid: the wall-clock stamps of SNOWTRI_LEAN_TRACE /
 //                            _SUMS_TRACE / _ASSOC_TRACE.  Round 3's timing-only switches that produced WRONG outputs
 //                            (..._NOSOLVE, _NOFILL, _REPEAT, _NOLOOP, _NOEPI, _STOP_AFTER_*, _MEMTEST, _COMPUTETEST) are gone.
+//   SNOWTRI_POSE_PER_RECORD  (with SNOWTRI_DEV_EXPERIMENTS) snowtri_refine_cameras launches k_pose_normal_rec, the kernel shape that
+//                            lost to k_pose_normal (snowtri_pose.hpp; scripts/bench_pose.py measures either build)
+#if defined(SNOWTRI_POSE_PER_RECORD) && !defined(SNOWTRI_DEV_EXPERIMENTS)
+#error "the per-record pose kernel is a development experiment: add -DSNOWTRI_DEV_EXPERIMENTS"
+#endif
 #if (defined(SNOWTRI_LEAN_TRACE) || defined(SNOWTRI_SUMS_TRACE) || defined(SNOWTRI_ASSOC_TRACE)) && !defined(SNOWTRI_DEV_EXPERIMENTS)
 #error "trace stamps are development experiments: add -DSNOWTRI_DEV_EXPERIMENTS"
 #endif

@@ -54,6 +54,32 @@ __device__ __forceinline__ bool refine_view(const double *__restrict__ q, double
     return pc2 > 0.0 && finite_f64(u) && finite_f64(v);
 }
 
+// Camera c's observation of record (f, p, j): -> listed (rule 1, first item), and (u, v, s) -- of detection 0 when not listed.
+// kpts [F][C][Pmax][kn][3], n_persons [F][C] or null, det_of [F][C][P] or null.  Shared with snowtri_pose.hpp.
+template <typename TK>
+__device__ __forceinline__ bool refine_observation(const TK *__restrict__ kpts, const int32_t *__restrict__ n_persons,
+                                                   const int32_t *__restrict__ det_of, int64_t f, int c, int C, int P, int Pmax, int kn, int p,
+                                                   int j, double &ou, double &ov, double &os) {
+    const int64_t fc = f * C + c;
+    const int q = det_of ? det_of[fc * P + p] : p;
+    const int nq = n_persons ? n_persons[fc] : Pmax;
+    const bool listed = q >= 0 && q < nq && q < Pmax;   // (q < Pmax: an n_persons past the array is not followed)
+    SNOWTRI_DEV_CHECK(c >= 0 && c < C && Pmax >= 1, 98);
+    const Kp3<TK> o = reinterpret_cast<const Kp3<TK> *>(kpts)[(fc * Pmax + (listed ? q : 0)) * (int64_t)kn + j];
+    ou = (double)o.u;
+    ov = (double)o.v;
+    os = (double)o.s;
+    return listed;
+}
+
+// Rule 1 for one camera (q: its proj row): is the observation (ou, ov, os) of the measured point (X, Y, Z) a view of the record?
+__device__ __forceinline__ bool refine_admits(const double *__restrict__ q, bool measured, bool listed, double ou, double ov, double os, double kthr,
+                                              uint32_t allowed, int c, double X, double Y, double Z) {
+    double x, y, iz, pu, pv;
+    const bool front = refine_view(q, X, Y, Z, x, y, iz, pu, pv);
+    return measured && listed && finite_f64(ou) && finite_f64(ov) && !(os < kthr) && ((allowed >> c) & 1u) && front;
+}
+
 // One view's terms of E, H and g at X: w ((u - ou)^2 + (v - ov)^2), w J^T J, w J^T r with the 2 x 3 Jacobian
 // dx = (R^T row 0 - x R^T row 2) / pc2, dy likewise, du = fx dx + s dy, dv = fy dy.  in == false: exact zeros.
 __device__ __forceinline__ void refine_add_view(RefineEval &e, const double *__restrict__ q, bool in, double ou, double ov, double w, double X,
@@ -138,22 +164,11 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
     const bool measured = rs != 0.0 && finite_f64(rx) && finite_f64(ry) && finite_f64(rz) && finite_f64(rs);
     const uint32_t allowed = views ? views[i] : 0xffffffffu;
     const bool score_w = (flags & kRefineScoreWeights) != 0;
-    const Kp3<TK> *kp3 = reinterpret_cast<const Kp3<TK> *>(kpts);
     // the point every evaluation of a lane without a view set works on: finite, so that nothing it computes is ever a trap
     double X = measured ? rx : 0.0, Y = measured ? ry : 0.0, Z = measured ? rz : 0.0;
 
-    // camera c's observation of this record -> listed (rule 1, first item), and (u, v, s) -- of detection 0 when not listed
     auto observation = [&](int c, double &ou, double &ov, double &os) -> bool {
-        const int64_t fc = f * C + c;
-        const int q = det_of ? det_of[fc * P + p] : p;
-        const int nq = n_persons ? n_persons[fc] : Pmax;
-        const bool listed = q >= 0 && q < nq && q < Pmax;   // (q < Pmax: an n_persons past the array is not followed)
-        SNOWTRI_DEV_CHECK(c >= 0 && c < C && Pmax >= 1, 98);
-        const Kp3<TK> o = kp3[(fc * Pmax + (listed ? q : 0)) * (int64_t)kn + j];
-        ou = (double)o.u;
-        ov = (double)o.v;
-        os = (double)o.s;
-        return listed;
+        return refine_observation(kpts, n_persons, det_of, f, c, C, P, Pmax, kn, p, j, ou, ov, os);
     };
 
     // ---- rule 1: the view set, fixed once at X0
@@ -162,10 +177,9 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
 #pragma unroll
     for (int k = 0; k < kRegs; k++) ou[k] = ov[k] = ow[k] = 0.0;
     auto admit = [&](int c, double &u_, double &v_, double &w_) {
-        double s_, x, y, iz, pu, pv;
+        double s_;
         const bool listed = observation(c, u_, v_, s_);
-        const bool front = refine_view(proj + (size_t)c * kProjStride, X, Y, Z, x, y, iz, pu, pv);
-        const bool in = measured && listed && finite_f64(u_) && finite_f64(v_) && !(s_ < kthr) && ((allowed >> c) & 1u) && front;
+        const bool in = refine_admits(proj + (size_t)c * kProjStride, measured, listed, u_, v_, s_, kthr, allowed, c, X, Y, Z);
         V |= in ? (1u << c) : 0u;
         u_ = in ? u_ : 0.0;
         v_ = in ? v_ : 0.0;

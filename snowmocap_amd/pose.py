@@ -1,0 +1,403 @@
+"""Camera pose refinement: the rig's extrinsics repaired from the joints the rig itself tracked.
+
+K, R, t come from a calibration file and are trusted for a whole recording.  A rig does not hold still: a tripod is nudged, a mount
+sags, and one camera ends up half a degree off.  `view_residuals` shows it -- the nudged camera's RMS stands out -- and this module
+repairs it: the reprojection cost of `refine_joints`, minimised over the other block of unknowns, each camera's six pose parameters,
+with the joints held fixed.  Alternated with triangulation (`refine_rig`) that is block-coordinate bundle adjustment of the
+extrinsics.
+
+The rule is stated in include/snowtri.h ("Camera pose refinement").  `refine_cameras_reference` is that rule in NumPy: plain
+operations in its order (no fused multiply-add), a camera's observations summed in record order, no GPU, no library; it is what the
+host tests check and what the kernels k_pose_normal / k_pose_step (snowmocap_amd/csrc/snowtri_pose.hpp) are compared with.
+`refine_cameras` runs the kernels.
+
+What it buys, on a synthetic recipe (tests/pose_cases.py::recipe: synth.ring_rig(8), two persons on the 1.5 m circle, 40 frames x 17
+joints, 1 px of noise, camera 3 off by 0.5 degrees and 2 cm and the only free one; not footage), `refine_rig` driven by the NumPy
+rules with a plain DLT as the triangulation: that camera's view RMS goes from 3.90 px (the others: 1.35 .. 1.62 px) to 1.55 px after
+one round and 1.32 px after two (the others: 1.27 .. 1.34), its rotation error from 7.5e-3 over 1.3e-3 to 9.9e-4, its position error
+from 20.0 over 13.6 to 8.9 mm.
+
+THE GAUGE.  Joints and cameras together are determined only up to a rigid motion and a scale of the whole scene, so `refine_rig`
+requires at least one camera to stay.  With only ONE camera held (a user who does not know which one moved) the bad camera's RMS
+still falls in the first round, but the scale is then held by nothing but the noise and the rig creeps slowly round after round:
+hold every camera that is trusted, and do not run more rounds than the RMS needs.
+
+Not offered: intrinsics and lens coefficients, a robust loss (pass the `views` mask of DLT_ROBUST), damping, points and cameras
+adjusted in one system, ShardedTrackPipeline, more than 32 cameras.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from ._lib import POSE_FEW_OBS, POSE_FIXED, POSE_KEPT, POSE_MOVED, free_mask  # noqa: F401
+from .records import missing_records
+from .refine import MAX_CAMERAS, _check_iters
+from .reproject import _rig
+
+H_INDEX = [(a, b) for a in range(6) for b in range(a + 1)]      # normal[7 + k] = H[a][b]: the lower triangle row by row
+
+
+def _check_min_obs(min_obs):
+    if int(min_obs) != min_obs or int(min_obs) < 3:
+        raise ValueError(f"min_obs must be an integer >= 3 (got {min_obs})")
+    return int(min_obs)
+
+
+def _ordered_sum(a):
+    """The sum over axis 0 in index order (np.sum adds pairwise)."""
+    return np.cumsum(a, axis=0)[-1] if a.shape[0] else np.zeros(a.shape[1:])
+
+
+def rodrigues(omega):
+    """Exp(omega) [3, 3] by the rule's formula: a = sin(th) / th, b = 2 sin^2(th / 2) / th^2, a = 1 and b = 1/2 at th = 0."""
+    o0, o1, o2 = (float(v) for v in omega)
+    th2 = (o0 * o0 + o1 * o1) + o2 * o2
+    th = np.sqrt(th2)
+    a, b = 1.0, 0.5
+    if th > 0.0:
+        sh = np.sin(0.5 * th)
+        a = np.sin(th) / th
+        b = (2.0 * (sh * sh)) / th2
+    W = np.array([[0.0, -o2, o1], [o2, 0.0, -o0], [-o1, o0, 0.0]])
+    E = np.empty((3, 3))
+    for i in range(3):
+        for j in range(3):
+            w2 = (W[i, 0] * W[0, j] + W[i, 1] * W[1, j]) + W[i, 2] * W[2, j]
+            E[i, j] = ((1.0 if i == j else 0.0) + a * W[i, j]) + b * w2
+    return E
+
+
+def apply_delta(Rc, tc, delta):
+    """Rule 2: (Exp(omega) R_c, t_c + tau), every product-sum in plain operations."""
+    E = rodrigues(delta[:3])
+    Rn = np.empty((3, 3))
+    for i in range(3):
+        for j in range(3):
+            Rn[i, j] = (E[i, 0] * Rc[0, j] + E[i, 1] * Rc[1, j]) + E[i, 2] * Rc[2, j]
+    return Rn, np.array([tc[0] + delta[3], tc[1] + delta[4], tc[2] + delta[5]])
+
+
+def project_camera(Kc, Rc, tc, X):
+    """Rules 1 and 3 of "Reprojection" for one camera: X [n, 3] -> x, y, pc2, u, v, ok [n] (ok: pc2 > 0 and a finite pixel)."""
+    d0, d1, d2 = X[:, 0] - tc[0], X[:, 1] - tc[1], X[:, 2] - tc[2]
+    pc0 = (Rc[0, 0] * d0 + Rc[1, 0] * d1) + Rc[2, 0] * d2
+    pc1 = (Rc[0, 1] * d0 + Rc[1, 1] * d1) + Rc[2, 1] * d2
+    pc2 = (Rc[0, 2] * d0 + Rc[1, 2] * d1) + Rc[2, 2] * d2
+    x, y = pc0 / pc2, pc1 / pc2
+    u = (Kc[0, 0] * x + Kc[0, 1] * y) + Kc[0, 2]
+    v = Kc[1, 1] * y + Kc[1, 2]
+    return x, y, pc2, u, v, (pc2 > 0) & np.isfinite(u) & np.isfinite(v)
+
+
+def pose_jacobian(Kc, Rc, tc, X):
+    """Rule 3's analytic Jacobian at delta = 0: X [n, 3] -> du [n, 6], dv [n, 6] (columns: omega, tau)."""
+    x, y, pc2, _, _, _ = project_camera(Kc, Rc, tc, X)
+    d = [X[:, 0] - tc[0], X[:, 1] - tc[1], X[:, 2] - tc[2]]
+    du, dv = np.empty((X.shape[0], 6)), np.empty((X.shape[0], 6))
+    for k in range(6):
+        if k < 3:                                   # column k of R^T [d]x = R^T (d x e_k)
+            m, n = (k + 1) % 3, (k + 2) % 3
+            a = [Rc[m, i] * d[n] - Rc[n, i] * d[m] for i in range(3)]
+        else:                                       # column k - 3 of -R^T
+            a = [-Rc[k - 3, i] * np.ones_like(x) for i in range(3)]
+        dx, dy = (a[0] - x * a[2]) / pc2, (a[1] - y * a[2]) / pc2
+        du[:, k] = Kc[0, 0] * dx + Kc[0, 1] * dy
+        dv[:, k] = Kc[1, 1] * dy
+    return du, dv
+
+
+def normal_terms(Kc, Rc, tc, X, ou, ov, w):
+    """One camera's observations X [n, 3], (ou, ov, w) [n] at the pose (Rc, tc) -> terms [n, 28]: every observation's share of
+    E, g[6], H[21] (the lower triangle row by row), and valid [n]."""
+    _, _, _, u, v, ok = project_camera(Kc, Rc, tc, X)
+    du, dv = pose_jacobian(Kc, Rc, tc, X)
+    ru, rv = u - ou, v - ov
+    terms = np.empty((X.shape[0], 28))
+    terms[:, 0] = w * (ru * ru + rv * rv)
+    for a in range(6):
+        terms[:, 1 + a] = w * (du[:, a] * ru + dv[:, a] * rv)
+    for k, (a, b) in enumerate(H_INDEX):
+        terms[:, 7 + k] = w * (du[:, a] * du[:, b] + dv[:, a] * dv[:, b])
+    return terms, ok
+
+
+def evaluate_camera(Kc, Rc, tc, X, ou, ov, w):
+    """-> normal [28] = E, g[6], H[21], the terms summed in record order, and whether every observation is valid at that pose."""
+    terms, ok = normal_terms(Kc, Rc, tc, X, ou, ov, w)
+    return _ordered_sum(terms), bool(ok.all())
+
+
+def solve_normal(normal):
+    """H delta = -g by a 6 x 6 LDL^T in plain operations -> delta [6], every pivot finite and > 0."""
+    H = np.zeros((6, 6))
+    for k, (a, b) in enumerate(H_INDEX):
+        H[a, b] = normal[7 + k]
+    g = normal[1:7]
+    L, piv, y, delta = np.zeros((6, 6)), np.zeros(6), np.zeros(6), np.zeros(6)
+    pd = True
+    with np.errstate(all="ignore"):
+        for a in range(6):
+            for b in range(a + 1):
+                s = H[a, b]
+                for k in range(b):
+                    s = s - L[a, k] * (L[b, k] * piv[k])
+                if b < a:
+                    L[a, b] = s / piv[b]
+                else:
+                    piv[a] = s
+            pd = pd and bool(piv[a] > 0.0) and bool(np.isfinite(piv[a]))
+        for a in range(6):
+            s = -g[a]
+            for k in range(a):
+                s = s - L[a, k] * y[k]
+            y[a] = s
+        for a in range(5, -1, -1):
+            s = y[a] / piv[a]
+            for k in range(a + 1, 6):
+                s = s - L[k, a] * delta[k]
+            delta[a] = s
+    return delta, pd
+
+
+def observation_sets(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, score_weights=False):
+    """Rule 1 -> X [N, 3] (the records' points, (0, 0, 0) for a missing one), S [C, N] bool, obs [C, N, 3] = (u_obs, v_obs, w)."""
+    K, R, t, _, C = _rig(K, R, t, None)
+    if C > MAX_CAMERAS:
+        raise ValueError(f"more than {MAX_CAMERAS} cameras")
+    thr = float(keypoint_score_threshold)
+    if thr != thr:
+        raise ValueError("keypoint_score_threshold is NaN")
+    xin = _lib.host_floats(xyzs)
+    if xin.ndim != 4 or xin.shape[-1] != 4:
+        raise ValueError(f"xyzs must be [F, P, kn, 4] records (got shape {xin.shape})")
+    F, P, kn, _ = xin.shape
+    kp = np.asarray(kpts).astype(np.float64)
+    if kp.ndim != 5 or kp.shape[:2] != (F, C) or kp.shape[3:] != (kn, 3) or kp.shape[2] < 1:
+        raise ValueError(f"kpts must be [F={F}, C={C}, Pmax >= 1, kn={kn}, 3] (got shape {kp.shape})")
+    Pmax = kp.shape[2]
+    if det_of is None:
+        if P > Pmax:
+            raise ValueError("det_of=None pairs person p with detection p: P must not exceed Pmax")
+        q = np.broadcast_to(np.arange(P, dtype=np.int64), (F, C, P))
+    else:
+        q = np.asarray(det_of).astype(np.int64).reshape(F, C, P)
+    nq = np.full((F, C), Pmax, dtype=np.int64) if n_persons is None else np.asarray(n_persons).astype(np.int64).reshape(F, C)
+    N = F * P * kn
+    x4 = xin.astype(np.float64)
+    measured = ~missing_records(x4).reshape(N)
+    listed = (q >= 0) & (q < nq[..., None]) & (q < Pmax)
+    obs = np.take_along_axis(kp, np.where(listed, q, 0)[..., None, None], axis=2) if N else np.zeros((F, C, P, kn, 3))
+    obs = np.moveaxis(obs, 1, 0).reshape(C, N, 3).copy()
+    listed = np.moveaxis(np.broadcast_to(listed[..., None], (F, C, P, kn)), 1, 0).reshape(C, N)
+    allowed = np.full(N, 0xffffffff, dtype=np.uint32) if views is None else np.asarray(views).astype(np.uint32).reshape(N)
+    X = np.where(measured[:, None], x4.reshape(N, 4)[:, :3], 0.0)
+    S = np.zeros((C, N), dtype=bool)
+    with np.errstate(all="ignore"):
+        for c in range(C):
+            ok = project_camera(K[c], R[c], t[c], X)[5]
+            bit = ((allowed >> np.uint32(c)) & 1).astype(bool)
+            S[c] = measured & listed[c] & np.isfinite(obs[c, :, 0]) & np.isfinite(obs[c, :, 1]) & ~(obs[c, :, 2] < thr) & bit & ok
+    if not score_weights:
+        obs[..., 2] = 1.0
+    return X, S, obs
+
+
+def refine_cameras_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None,
+                             min_obs=64, iters=8, score_weights=False, return_sets=False):
+    """The rule in NumPy: xyzs [F, P, kn, 4], kpts [F, C, Pmax, kn, 3], det_of [F, C, P] or None, n_persons [F, C] or None, views
+    [F, P, kn] or None; free: None (all), a bit mask, C booleans or camera indices ->
+    (R [C, 3, 3], t [C, 3], report) with report = dict(cost [C, 2], n_obs [C] int64, codes [C] uint8, normal [C, 28], steps [C]: the
+    steps accepted); with return_sets also S [C, N] bool, the observation sets."""
+    K, R, t, _, C = _rig(K, R, t, None)
+    iters = _check_iters(iters)
+    min_obs = _check_min_obs(min_obs)
+    mask = free_mask(free, C)
+    X, S, obs = observation_sets(K, R, t, xyzs, kpts, det_of, n_persons, views, keypoint_score_threshold, score_weights)
+    R_out, t_out = np.array(R, copy=True), np.array(t, copy=True)
+    cost, n_obs = np.zeros((C, 2)), np.zeros(C, dtype=np.int64)
+    codes, normal, steps = np.zeros(C, dtype=np.uint8), np.zeros((C, 28)), np.zeros(C, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for c in range(C):
+            Xc, ou, ov, w = X[S[c]], obs[c, S[c], 0], obs[c, S[c], 1], obs[c, S[c], 2]
+            n_obs[c] = len(Xc)
+            cur, _ = evaluate_camera(K[c], R[c], t[c], Xc, ou, ov, w)
+            normal[c] = cur
+            if not (mask >> c) & 1:
+                codes[c] = POSE_FIXED
+                continue
+            if n_obs[c] < min_obs:
+                codes[c] = POSE_FEW_OBS
+                continue
+            codes[c] = POSE_KEPT
+            Rc, tc = R[c], t[c]
+            cost[c, 0] = cur[0]
+            for _ in range(iters):
+                delta, pd = solve_normal(cur)
+                if not pd:
+                    break
+                Rt, tt = apply_delta(Rc, tc, delta)
+                nxt, valid = evaluate_camera(K[c], Rt, tt, Xc, ou, ov, w)
+                if not (valid and nxt[0] < cur[0]):
+                    break
+                Rc, tc, cur = Rt, tt, nxt
+                codes[c] = POSE_MOVED
+                steps[c] += 1
+            cost[c, 1] = cur[0]
+            R_out[c], t_out[c] = Rc, tc
+    report = dict(cost=cost, n_obs=n_obs, codes=codes, normal=normal, steps=steps)
+    return (R_out, t_out, report, S) if return_sets else (R_out, t_out, report)
+
+
+def refine_cameras(ctx, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None, min_obs=64, iters=8,
+                   score_weights=False, diagnostics=False, stream=None):
+    """k_pose_normal / k_pose_step through the context of the rig (_lib.Context): Context.refine_cameras.  -> (R, t), or
+    (R, t, report) with diagnostics=True; the context's own rig is not changed."""
+    return ctx.refine_cameras(xyzs, kpts, det_of=det_of, n_persons=n_persons, views=views, keypoint_score_threshold=keypoint_score_threshold,
+                              free=free, min_obs=min_obs, iters=iters, score_weights=score_weights, diagnostics=diagnostics, stream=stream)
+
+
+# ------------------------------------------------------------------------------------------------ the alternation
+class _LibrarySteps:
+    """The four steps of one round of refine_rig on the GPU, from the library's public pieces (host arrays in and out)."""
+
+    def __init__(self, method, params, P):
+        self.method, self.params, self.P = method, params, P
+
+    def triangulate(self, K, R, t, kpts, n_persons):
+        from .batch import BatchTriangulator
+        bt = BatchTriangulator(K, R, t, self.params, pout_max=self.P, out_dtype=np.float64, method=self.method)
+        try:
+            res = bt.run_host(kpts, n_persons)
+        finally:
+            bt.close()
+        if res["status"] != _lib.ERR_OVERFLOW:            # (a frame with more clusters than `persons` keeps `persons` of them: a nudged
+            _lib.check(res["status"], "refine_rig: triangulation")   # camera splits a person in two until it is repaired)
+        self.overflow_frames = int(((res["flags"] & _lib.FLAG_OVERFLOW) != 0).sum())   # ... and the round's history says how many
+        return res["xyzs"]
+
+    def open(self, K, R, t):
+        self.ctx = _lib.Context(K, R, t)
+
+    def close(self):
+        self.ctx.close()
+
+    def cost(self, xyzs, kpts, n_persons, thr):
+        return self.ctx.reproject_cost(xyzs, kpts, n_persons=n_persons, keypoint_score_threshold=thr)
+
+    def pixels(self, xyzs):
+        return self.ctx.reproject(xyzs, dtype=np.float64)
+
+    def joints(self, xyzs, kpts, **kw):
+        return self.ctx.refine_joints(xyzs, kpts, **kw)
+
+    def cameras(self, xyzs, kpts, **kw):
+        return self.ctx.refine_cameras(xyzs, kpts, diagnostics=True, **kw)
+
+
+class _ReferenceSteps:
+    """The same steps by the NumPy rules (no GPU); the triangulation is the caller's."""
+
+    def __init__(self, triangulate):
+        self.triangulate = triangulate
+
+    def open(self, K, R, t):
+        self.rig = (K, R, t)
+
+    def close(self):
+        pass
+
+    def cost(self, xyzs, kpts, n_persons, thr):
+        from .reproject import reprojection_cost_reference
+        return reprojection_cost_reference(*self.rig, xyzs, kpts, n_persons=n_persons, keypoint_score_threshold=thr)
+
+    def pixels(self, xyzs):
+        from .reproject import reproject_reference
+        return reproject_reference(*self.rig, xyzs)
+
+    def joints(self, xyzs, kpts, **kw):
+        from .refine import refine_joints_reference
+        return refine_joints_reference(*self.rig, xyzs, kpts, **kw)[0]
+
+    def cameras(self, xyzs, kpts, **kw):
+        return refine_cameras_reference(*self.rig, xyzs, kpts, **kw)
+
+
+def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.DLT, params=None, persons=None, gate_px=12.0,
+               min_joints=8, joint_iters=4, camera_iters=8, min_obs=64, score_weights=False, triangulate=None, reference=False):
+    """Block-coordinate bundle adjustment of the extrinsics: `rounds` times triangulate on the current rig, match the detections to the
+    3D persons (reprojection_cost + match_detections, gate_px), refine the joints (refine_joints, joint_iters), refine the free cameras
+    (refine_cameras, camera_iters, min_obs), and build a new context from the result.  Host arrays: kpts [F, C, Pmax, kn, 3] on the
+    UNDISTORTED frame, n_persons [F, C] or None.
+
+    free (REQUIRED): the cameras that may move, as a bit mask, C booleans or camera indices.  It must leave at least one camera out --
+    the gauge: joints and cameras together are determined only up to a rigid motion and a scale.  Hold every camera that is trusted:
+    with only one held, the bad camera's RMS still falls in the first round, but the rig then creeps slowly round after round.
+    params: the triangulation's thresholds (default: the function-signature defaults with keypoint_num = kn and the centre joint
+    min(18, kn - 1)); persons: the 3D persons per frame (default Pmax).  CALIBRATE ON A SINGLE-PERSON RECORDING (Pmax = 1: every
+    camera's detection is the same person and the DLT takes every view).  With several persons per frame the triangulation first
+    has to associate detections across cameras with the very rig that is wrong: a camera half a degree off misses a joint 5 m away
+    by 4 cm, its ray pairs fall outside distance_threshold or form a second cluster, and on the two-person recipe the alternation
+    did not repair it (EXPERIMENTS.md).  triangulate(K, R, t, kpts, n_persons) -> xyzs [F, P, kn, 4]
+    replaces the BatchTriangulator; reference=True runs every other step by its NumPy rule (no GPU; needs `triangulate`).
+
+    -> (R [C, 3, 3], t [C, 3], history): history[r] = dict(overflow_frames: the frames in which the library's triangulation found
+    more clusters than `persons` and dropped some (0 with the caller's `triangulate`), view_rms [C]: each camera's RMS pixel residual over its matched views
+    BEFORE round r's pose step, cost [C, 2], n_obs [C], codes [C]: that step's report), and a last entry with the view_rms of the
+    returned rig alone."""
+    from .reproject import match_detections, view_residuals
+    K, R, t, _, C = _rig(K, R, t, None)
+    if free is None:
+        raise ValueError("refine_rig: free is required (the cameras that may move)")
+    mask = free_mask(free, C)
+    if mask == (1 << C) - 1:
+        raise ValueError("refine_rig: free must leave at least one camera out (the gauge: a rigid motion and a scale of the whole scene)")
+    if int(rounds) != rounds or int(rounds) < 1:
+        raise ValueError("refine_rig: rounds must be an integer >= 1")
+    kpts = _lib.host_floats(kpts)
+    if kpts.ndim != 5 or kpts.shape[1] != C or kpts.shape[-1] != 3:
+        raise ValueError(f"kpts must be [F, C={C}, Pmax, kn, 3] (got shape {kpts.shape})")
+    F, _, Pmax, kn, _ = kpts.shape
+    P = Pmax if persons is None else int(persons)
+    if n_persons is not None:
+        n_persons = np.ascontiguousarray(n_persons, dtype=np.int32).reshape(F, C)
+    if params is None:
+        params = dict(keypoint_num=kn, center_point_index=min(18, kn - 1))
+    thr = float(params.get("keypoint_score_threshold", 0.5)) if isinstance(params, dict) else float(params.keypoint_score_threshold)
+    if reference and triangulate is None:
+        raise ValueError("refine_rig: reference=True needs `triangulate` (the library's triangulation runs on the GPU)")
+    steps = _ReferenceSteps(triangulate) if reference else _LibrarySteps(method, params, P)
+    if triangulate is not None:
+        steps.triangulate = triangulate
+    R, t = np.array(R, copy=True), np.array(t, copy=True)
+    history = []
+
+    def measure(xyzs):
+        cs, cn = steps.cost(xyzs, kpts, n_persons, thr)
+        det_of, _ = match_detections(np.asarray(cs), np.asarray(cn), gate_px, min_joints)
+        resid = view_residuals(steps.pixels(xyzs), kpts, det_of, thr)[0]                   # [F, C, P, kn], NaN where nothing counts
+        r2 = np.moveaxis(np.asarray(resid) ** 2, 1, 0).reshape(C, -1)
+        with np.errstate(all="ignore"):
+            rms = np.sqrt(np.nansum(r2, axis=1) / np.maximum((~np.isnan(r2)).sum(axis=1), 1))
+        return det_of, np.where((~np.isnan(r2)).any(axis=1), rms, np.nan)
+
+    for r in range(int(rounds) + 1):
+        steps.overflow_frames = 0
+        xyzs = np.ascontiguousarray(steps.triangulate(K, R, t, kpts, n_persons), dtype=np.float64)
+        steps.open(K, R, t)
+        try:
+            det_of, view_rms = measure(xyzs)
+            if r == int(rounds):
+                history.append(dict(overflow_frames=steps.overflow_frames, view_rms=view_rms))
+                break
+            kw = dict(det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr, score_weights=score_weights)
+            xyzs = steps.joints(xyzs, kpts, iters=joint_iters, **kw)
+            R, t, rep = steps.cameras(xyzs, kpts, free=mask, min_obs=min_obs, iters=camera_iters, **kw)
+            R, t = np.array(R, dtype=np.float64), np.array(t, dtype=np.float64)
+            history.append(dict(overflow_frames=steps.overflow_frames, view_rms=view_rms, cost=np.array(rep["cost"]), n_obs=np.array(rep["n_obs"]), codes=np.array(rep["codes"])))
+        finally:
+            steps.close()
+    return R, t, history
+
+
+__all__ = ["refine_cameras", "refine_cameras_reference", "refine_rig", "POSE_FIXED", "POSE_FEW_OBS", "POSE_KEPT", "POSE_MOVED"]
