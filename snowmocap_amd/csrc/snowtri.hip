@@ -2009,6 +2009,12 @@ int snowtri_track_gather(snowtri_ctx *ctx, int64_t F, int32_t Pout_max, int32_t 
 // ------------------------------------------------------------------------------- record passes: gap filling, despiking
 namespace {
 
+// A refusal by the entry point `who`: "<who>: <what>" is what snowtri_last_error() then says.  -> the status.
+struct Refuse {
+    const char *who;
+    int operator()(const char *what, int status = SNOWTRI_ERR_BAD_ARG) const { return arg_fail(status, (std::string(who) + ": " + what).c_str()); }
+};
+
 // The host side of a pass xyzs[T][m][4] -> out[T][m][4] (+ codes[T][m], may be null) over a track of joint records, after the
 // entry point `who` has checked its context and its own parameters: every other refusal (nothing is written or enqueued on one),
 // an empty track (OK before any pointer is looked at), the staging of host arrays through ctx->in / ctx->out, and between the
@@ -2016,7 +2022,7 @@ namespace {
 template <typename Launch>
 int record_pass(const char *who, snowtri_ctx *ctx, int64_t T, int64_t m, const void *xyzs, int xyz_dtype, void *out, uint8_t *codes, int memspace,
                 void *stream, Launch launch) {
-    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    const Refuse refuse{who};
     if (xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) return refuse("unknown xyz_dtype");
     if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
     if (T < 0 || m < 0) return refuse("T < 0 or m < 0");
@@ -2102,7 +2108,7 @@ namespace {
 // What snowtri_reproject and snowtri_reproject_cost check alike, before anything is enqueued or written.  -> 0, or the status.
 int reproject_args(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, int xyz_dtype, uint32_t flags, int other_dtype,
                    int memspace) {
-    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    const Refuse refuse{who};
     if (!ctx) return refuse("null context");
     if (ctx->C <= 0) return refuse("the context has no cameras");
     if ((xyz_dtype != SNOWTRI_F32 && xyz_dtype != SNOWTRI_F64) || (other_dtype != SNOWTRI_F32 && other_dtype != SNOWTRI_F64))
@@ -2116,6 +2122,19 @@ int reproject_args(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int3
     return 0;
 }
 
+// fn(a, b) with two zero values whose TYPES are the pair that two SNOWTRI_F32 / SNOWTRI_F64 codes name: a generic lambda takes
+// them with decltype and launches the kernel instantiated for that pair.
+template <typename Fn>
+void with_float_pair(int dtype_a, int dtype_b, Fn fn) {
+    if (dtype_a == SNOWTRI_F32) {
+        if (dtype_b == SNOWTRI_F32) fn(float(), float());
+        else fn(float(), double());
+    } else {
+        if (dtype_b == SNOWTRI_F32) fn(double(), float());
+        else fn(double(), double());
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2124,7 +2143,7 @@ int snowtri_reproject(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const 
                       int pix_dtype, int memspace, void *stream) {
     const char *who = "snowtri_reproject";
     if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, flags, pix_dtype, memspace)) return rc;
-    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    const Refuse refuse{who};
     // one lane per observation, 256 per workgroup on a one-dimensional grid; 64-bit element offsets
     if (F == 0) return SNOWTRI_OK;
     const int64_t max_obs = (int64_t)0x7fffffff * 256, per_person_frame = (int64_t)P * kn;   // (two int32: no overflow)
@@ -2146,17 +2165,12 @@ int snowtri_reproject(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const 
     if (int rc = sg.begin()) return rc;
     const dim3 grid((unsigned)((n_obs + 255) / 256));
     const int raw = (flags & SNOWTRI_REPROJECT_RAW) ? 1 : 0;
-#define LAUNCH_REPROJECT(TX, TP)                                                                                                  \
-    hipLaunchKernelGGL((k_reproject<TX, TP>), grid, dim3(256), 0, st, n_obs, (int)ctx->C, (int)P, (int)kn, raw, (const double *)ctx->dProj, \
-                       (const TX *)dx, (TP *)dp)
-    if (xyz_dtype == SNOWTRI_F32) {
-        if (pix_dtype == SNOWTRI_F32) LAUNCH_REPROJECT(float, float);
-        else LAUNCH_REPROJECT(float, double);
-    } else {
-        if (pix_dtype == SNOWTRI_F32) LAUNCH_REPROJECT(double, float);
-        else LAUNCH_REPROJECT(double, double);
-    }
-#undef LAUNCH_REPROJECT
+    with_float_pair(xyz_dtype, pix_dtype, [&](auto tx, auto tp) {
+        using TX = decltype(tx);
+        using TP = decltype(tp);
+        hipLaunchKernelGGL((k_reproject<TX, TP>), grid, dim3(256), 0, st, n_obs, (int)ctx->C, (int)P, (int)kn, raw, (const double *)ctx->dProj,
+                           (const TX *)dx, (TP *)dp);
+    });
     HIP_TRY(hipGetLastError());
     return sg.end();
 }
@@ -2166,7 +2180,7 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
                            int32_t *cost_n, int memspace, void *stream) {
     const char *who = "snowtri_reproject_cost";
     if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, flags, kpts_dtype, memspace)) return rc;
-    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
+    const Refuse refuse{who};
     if (Pmax < 1) return refuse("Pmax < 1");
     if (kn > kCostMaxJoints) return refuse("kn must not exceed 256 joints (four per lane of the wave that owns a person)");
     if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
@@ -2197,17 +2211,12 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
     if (int rc = sg.begin()) return rc;
     const dim3 grid((unsigned)((n_items + kCostWaves - 1) / kCostWaves));
     const int raw = (flags & SNOWTRI_REPROJECT_RAW) ? 1 : 0;
-#define LAUNCH_COST(TX, TK)                                                                                                           \
-    hipLaunchKernelGGL((k_reproject_cost<TX, TK>), grid, dim3(64 * kCostWaves), 0, st, n_items, (int)ctx->C, (int)P, (int)Pmax, (int)kn, raw, \
-                       keypoint_score_threshold, (const double *)ctx->dProj, (const TX *)dx, (const TK *)dk, dnp, ds, dn)
-    if (xyz_dtype == SNOWTRI_F32) {
-        if (kpts_dtype == SNOWTRI_F32) LAUNCH_COST(float, float);
-        else LAUNCH_COST(float, double);
-    } else {
-        if (kpts_dtype == SNOWTRI_F32) LAUNCH_COST(double, float);
-        else LAUNCH_COST(double, double);
-    }
-#undef LAUNCH_COST
+    with_float_pair(xyz_dtype, kpts_dtype, [&](auto tx, auto tk) {
+        using TX = decltype(tx);
+        using TK = decltype(tk);
+        hipLaunchKernelGGL((k_reproject_cost<TX, TK>), grid, dim3(64 * kCostWaves), 0, st, n_items, (int)ctx->C, (int)P, (int)Pmax, (int)kn, raw,
+                           keypoint_score_threshold, (const double *)ctx->dProj, (const TX *)dx, (const TK *)dk, dnp, ds, dn);
+    });
     HIP_TRY(hipGetLastError());
     return sg.end();
 }
@@ -2217,22 +2226,54 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
 // ------------------------------------------------------------------------------- refinement
 namespace {
 
-template <int CT>
-void launch_refine(int xyz_dtype, int kpts_dtype, dim3 grid, hipStream_t st, int64_t n_rec, int C, int P, int Pmax, int kn, double kthr, int iters,
-                   uint32_t flags, const double *proj, const void *dx, const void *dk, const int32_t *dnp, const int32_t *ddet,
-                   const uint32_t *dviews, void *d_out, double *d_cost, uint8_t *d_codes) {
-#define LAUNCH_REFINE(TX, TK)                                                                                                              \
-    hipLaunchKernelGGL((k_refine<CT, TX, TK>), grid, dim3(kRefineBlock), 0, st, n_rec, C, P, Pmax, kn, kthr, iters, flags, proj, (const TX *)dx, \
-                       (const TK *)dk, dnp, ddet, dviews, (TX *)d_out, d_cost, d_codes)
-    if (xyz_dtype == SNOWTRI_F32) {
-        if (kpts_dtype == SNOWTRI_F32) LAUNCH_REFINE(float, float);
-        else LAUNCH_REFINE(float, double);
-    } else {
-        if (kpts_dtype == SNOWTRI_F32) LAUNCH_REFINE(double, float);
-        else LAUNCH_REFINE(double, double);
+// The inputs that snowtri_refine_joints and snowtri_refine_cameras take alike -- the joint records, the detections of every camera
+// and what matches one to the other (n_persons, det_of, views) -- with the checks, sizes and staging the two share.
+struct ObservedInputs {
+    int64_t n_rec = 0;   // F * P * kn; 0 is the empty batch, of which no input pointer is looked at (the five below stay null)
+    size_t x_bytes = 0, k_bytes = 0, np_bytes = 0, det_bytes = 0, views_bytes = 0;
+    const void *dx = nullptr, *dk = nullptr;   // the caller's arrays; behind stage() and Staging::begin() what the kernels read
+    const int32_t *dnp = nullptr, *ddet = nullptr;
+    const uint32_t *dviews = nullptr;
+
+    // After reproject_args.  -> 0, or the status of a refusal; F == 0 is none, and what it means is the entry's to say.
+    int check(const Refuse &refuse, const snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+              const void *kpts, int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+              double keypoint_score_threshold, int32_t iters, uint32_t flags, uint32_t known_flags, int memspace) {
+        if (flags & ~known_flags) return refuse("unknown flag bit");
+        if (Pmax < 1) return refuse("Pmax < 1");
+        if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
+        if (iters < 1 || iters > kRefineMaxIters) return refuse("iters must lie in 1..16");
+        if (ctx->C > kRefineMaxCams) return refuse("more than 32 cameras (a set of cameras is a 32-bit mask)");
+        if (!det_of && P > Pmax) return refuse("det_of == NULL pairs person p with detection p: P must not exceed Pmax");
+        if (F == 0) return 0;
+        // one lane per record, 256 per workgroup on a one-dimensional grid; 64-bit element offsets
+        const int64_t max_rec = (int64_t)0x7fffffff * kRefineBlock, per_frame = (int64_t)P * kn;   // (two int32: no overflow)
+        if (F > max_rec / per_frame) return refuse("F * P * kn must not exceed (2^31 - 1) * 256 records");
+        const int64_t per_view = (int64_t)Pmax * kn, cp = (int64_t)ctx->C * std::max(P, Pmax);
+        if (F > (((int64_t)1 << 56) / per_view) / ctx->C || F > ((int64_t)1 << 56) / cp)
+            return refuse("F * C * Pmax * kn and F * C * P must not exceed 2^56 elements");
+        if (!xyzs || !kpts) return refuse("null array (xyzs or kpts)");
+        const size_t xs = dtype_size(xyz_dtype), ks = dtype_size(kpts_dtype);
+        if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) & (xs - 1)) || (((uintptr_t)kpts) & (ks - 1)) ||
+                                           (((uintptr_t)n_persons | (uintptr_t)det_of | (uintptr_t)views) & 3u)))
+            return refuse("xyzs, kpts, n_persons, det_of and views must be aligned to their element size");
+        n_rec = F * per_frame;
+        x_bytes = xs * 4 * (size_t)n_rec;
+        k_bytes = ks * 3 * (size_t)F * ctx->C * (size_t)per_view;
+        np_bytes = sizeof(int32_t) * (size_t)F * ctx->C;
+        det_bytes = np_bytes * P;
+        views_bytes = sizeof(uint32_t) * (size_t)n_rec;
+        dx = xyzs, dk = kpts, dnp = n_persons, ddet = det_of, dviews = views;
+        return 0;
     }
-#undef LAUNCH_REFINE
-}
+    void stage(Staging &sg) {   // (in this order: it is the layout of ctx->in)
+        sg.in(&dx, x_bytes);
+        sg.in(&dk, k_bytes);
+        sg.in(&dnp, np_bytes);
+        sg.in(&ddet, det_bytes);
+        sg.in(&dviews, views_bytes);
+    }
+};
 
 }  // namespace
 
@@ -2244,58 +2285,46 @@ int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, co
                           int memspace, void *stream) {
     const char *who = "snowtri_refine_joints";
     if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, 0u, kpts_dtype, memspace)) return rc;
-    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
-    if (flags & ~(uint32_t)SNOWTRI_REFINE_SCORE_WEIGHTS) return refuse("unknown flag bit");
-    if (Pmax < 1) return refuse("Pmax < 1");
-    if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
-    if (iters < 1 || iters > kRefineMaxIters) return refuse("iters must lie in 1..16");
-    if (ctx->C > kRefineMaxCams) return refuse("more than 32 cameras (a view set is a 32-bit mask)");
-    if (!det_of && P > Pmax) return refuse("det_of == NULL pairs person p with detection p: P must not exceed Pmax");
-    // one lane per record, 256 per workgroup on a one-dimensional grid; 64-bit element offsets
+    const Refuse refuse{who};
+    ObservedInputs in;
+    if (int rc = in.check(refuse, ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views, keypoint_score_threshold, iters,
+                          flags, SNOWTRI_REFINE_SCORE_WEIGHTS, memspace))
+        return rc;
     if (F == 0) return SNOWTRI_OK;
-    const int64_t max_rec = (int64_t)0x7fffffff * kRefineBlock, per_frame = (int64_t)P * kn;   // (two int32: no overflow)
-    if (F > max_rec / per_frame) return refuse("F * P * kn must not exceed (2^31 - 1) * 256 records");
-    const int64_t per_view = (int64_t)Pmax * kn, cp = (int64_t)ctx->C * std::max(P, Pmax);
-    if (F > (((int64_t)1 << 56) / per_view) / ctx->C || F > ((int64_t)1 << 56) / cp)
-        return refuse("F * C * Pmax * kn and F * C * P must not exceed 2^56 elements");
-    if (!xyzs || !kpts || !out_xyzs) return refuse("null array (xyzs, kpts or out_xyzs)");
-    const size_t xs = dtype_size(xyz_dtype), ks = dtype_size(kpts_dtype);
-    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs | (uintptr_t)out_xyzs) & (xs - 1)) || (((uintptr_t)kpts) & (ks - 1)) ||
-                                       (((uintptr_t)n_persons | (uintptr_t)det_of | (uintptr_t)views) & 3u) || (((uintptr_t)cost) & 7u)))
-        return refuse("xyzs, out_xyzs, kpts, n_persons, det_of, views and cost must be aligned to their element size");
-    const int64_t n_rec = F * per_frame;
-    const size_t x_bytes = xs * 4 * (size_t)n_rec, k_bytes = ks * 3 * (size_t)F * ctx->C * (size_t)per_view;
+    if (!out_xyzs) return refuse("null array (out_xyzs)");
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)out_xyzs) & (dtype_size(xyz_dtype) - 1)) || (((uintptr_t)cost) & 7u)))
+        return refuse("out_xyzs and cost must be aligned to their element size");
     // a lane reads its record and writes it at the same place: out_xyzs == xyzs is that; any other overlap lets one lane's store
     // reach another lane's load
-    if (out_xyzs != xyzs && (uintptr_t)xyzs < (uintptr_t)out_xyzs + x_bytes && (uintptr_t)out_xyzs < (uintptr_t)xyzs + x_bytes)
+    if (out_xyzs != xyzs && (uintptr_t)xyzs < (uintptr_t)out_xyzs + in.x_bytes && (uintptr_t)out_xyzs < (uintptr_t)xyzs + in.x_bytes)
         return refuse("out_xyzs must be xyzs itself or not overlap it");
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    const void *dx = xyzs, *dk = kpts;
-    const int32_t *dnp = n_persons, *ddet = det_of;
-    const uint32_t *dviews = views;
+    const int64_t n_rec = in.n_rec;
     void *d_out = out_xyzs;
     double *d_cost = cost;
     uint8_t *d_codes = codes;
     Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
-    sg.in(&dx, x_bytes);
-    sg.in(&dk, k_bytes);
-    sg.in(&dnp, sizeof(int32_t) * (size_t)F * ctx->C);
-    sg.in(&ddet, sizeof(int32_t) * (size_t)F * ctx->C * P);
-    sg.in(&dviews, sizeof(uint32_t) * (size_t)n_rec);
-    sg.out(&d_out, x_bytes);
+    in.stage(sg);
+    sg.out(&d_out, in.x_bytes);
     sg.out(&d_cost, sizeof(double) * 2 * (size_t)n_rec);
     sg.out(&d_codes, (size_t)n_rec);
     if (int rc = sg.begin()) return rc;
     // (a DEVICE call with out_xyzs == xyzs passes one pointer twice: the kernel declares neither of the two restrict)
     const dim3 grid((unsigned)((n_rec + kRefineBlock - 1) / kRefineBlock));
     const int C = ctx->C;
-#define REFINE_ARGS xyz_dtype, kpts_dtype, grid, st, n_rec, C, (int)P, (int)Pmax, (int)kn, keypoint_score_threshold, (int)iters, flags, \
-                    (const double *)ctx->dProj, dx, dk, dnp, ddet, dviews, d_out, d_cost, d_codes
-    if (C == 4) launch_refine<4>(REFINE_ARGS);
-    else if (C == 8) launch_refine<8>(REFINE_ARGS);
-    else launch_refine<0>(REFINE_ARGS);
-#undef REFINE_ARGS
+    auto launch = [&](auto ct) {   // ct: the camera count the kernel is compiled for (0: any) as a std::integral_constant
+        with_float_pair(xyz_dtype, kpts_dtype, [&](auto tx, auto tk) {
+            using TX = decltype(tx);
+            using TK = decltype(tk);
+            hipLaunchKernelGGL((k_refine<decltype(ct)::value, TX, TK>), grid, dim3(kRefineBlock), 0, st, n_rec, C, (int)P, (int)Pmax, (int)kn,
+                               keypoint_score_threshold, (int)iters, flags, (const double *)ctx->dProj, (const TX *)in.dx, (const TK *)in.dk,
+                               in.dnp, in.ddet, in.dviews, (TX *)d_out, d_cost, d_codes);
+        });
+    };
+    if (C == 4) launch(std::integral_constant<int, 4>());
+    else if (C == 8) launch(std::integral_constant<int, 8>());
+    else launch(std::integral_constant<int, 0>());
     HIP_TRY(hipGetLastError());
     return sg.end();
 }
@@ -2303,33 +2332,6 @@ int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, co
 }  // extern "C"
 
 // ------------------------------------------------------------------------------- camera pose refinement
-namespace {
-
-void launch_pose_normal(int xyz_dtype, int kpts_dtype, dim3 grid, hipStream_t st, int64_t n_rec, int C, int P, int Pmax, int kn, double kthr,
-                        uint32_t flags, const double *base, const double *trial, const int32_t *active, const void *dx, const void *dk,
-                        const int32_t *dnp, const int32_t *ddet, const uint32_t *dviews, double *partials) {
-#ifdef SNOWTRI_POSE_PER_RECORD   // (a development build: the shape that lost, EXPERIMENTS.md round 22)
-#define POSE_NORMAL k_pose_normal_rec
-    grid = dim3(grid.x);
-#else
-#define POSE_NORMAL k_pose_normal
-#endif
-#define LAUNCH_POSE(TX, TK)                                                                                                               \
-    hipLaunchKernelGGL((POSE_NORMAL<TX, TK>), grid, dim3(kPoseBlock), 0, st, n_rec, C, P, Pmax, kn, kthr, flags, base, trial, active, \
-                       (const TX *)dx, (const TK *)dk, dnp, ddet, dviews, partials)
-    if (xyz_dtype == SNOWTRI_F32) {
-        if (kpts_dtype == SNOWTRI_F32) LAUNCH_POSE(float, float);
-        else LAUNCH_POSE(float, double);
-    } else {
-        if (kpts_dtype == SNOWTRI_F32) LAUNCH_POSE(double, float);
-        else LAUNCH_POSE(double, double);
-    }
-#undef LAUNCH_POSE
-#undef POSE_NORMAL
-}
-
-}  // namespace
-
 extern "C" {
 
 int snowtri_pose_sweep_records(void) { return kPoseGridCap * kPoseBlock; }
@@ -2340,51 +2342,26 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
                            double *t_out, double *cost, int64_t *n_obs, uint8_t *codes, double *normal, int memspace, void *stream) {
     const char *who = "snowtri_refine_cameras";
     if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, 0u, kpts_dtype, memspace)) return rc;
-    auto refuse = [who](const char *what) { return arg_fail(SNOWTRI_ERR_BAD_ARG, (std::string(who) + ": " + what).c_str()); };
-    if (flags & ~(uint32_t)SNOWTRI_REFINE_SCORE_WEIGHTS) return refuse("unknown flag bit");
-    if (Pmax < 1) return refuse("Pmax < 1");
-    if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
-    if (iters < 1 || iters > kRefineMaxIters) return refuse("iters must lie in 1..16");
+    const Refuse refuse{who};
+    ObservedInputs in;   // (F == 0 is work here: no input pointer is looked at, only k_pose_step runs, every pose is copied)
+    if (int rc = in.check(refuse, ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views, keypoint_score_threshold, iters,
+                          flags, SNOWTRI_REFINE_SCORE_WEIGHTS, memspace))
+        return rc;
     if (min_obs < 3) return refuse("min_obs must be at least 3 (six parameters, two equations per observation)");
-    if (ctx->C > kRefineMaxCams) return refuse("more than 32 cameras (free_mask is a 32-bit mask)");
     if (ctx->C < 32 && (free_mask >> ctx->C)) return refuse("free_mask has a bit at or above the number of cameras");
-    if (!det_of && P > Pmax) return refuse("det_of == NULL pairs person p with detection p: P must not exceed Pmax");
     if (!R_out || !t_out) return refuse("null array (R_out or t_out)");
     if (memspace == SNOWTRI_DEVICE && (((uintptr_t)R_out | (uintptr_t)t_out | (uintptr_t)cost | (uintptr_t)n_obs | (uintptr_t)normal) & 7u))
         return refuse("R_out, t_out, cost, n_obs and normal must be aligned to their element size");
     const int C = ctx->C;
-    int64_t n_rec = 0;
-    size_t x_bytes = 0, k_bytes = 0;
-    if (F > 0) {
-        const int64_t max_rec = (int64_t)0x7fffffff * kRefineBlock, per_frame = (int64_t)P * kn;   // (two int32: no overflow)
-        if (F > max_rec / per_frame) return refuse("F * P * kn must not exceed (2^31 - 1) * 256 records");
-        const int64_t per_view = (int64_t)Pmax * kn, cp = (int64_t)C * std::max(P, Pmax);
-        if (F > (((int64_t)1 << 56) / per_view) / C || F > ((int64_t)1 << 56) / cp)
-            return refuse("F * C * Pmax * kn and F * C * P must not exceed 2^56 elements");
-        if (!xyzs || !kpts) return refuse("null array (xyzs or kpts)");
-        const size_t xs = dtype_size(xyz_dtype), ks = dtype_size(kpts_dtype);
-        if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)xyzs) & (xs - 1)) || (((uintptr_t)kpts) & (ks - 1)) ||
-                                           (((uintptr_t)n_persons | (uintptr_t)det_of | (uintptr_t)views) & 3u)))
-            return refuse("xyzs, kpts, n_persons, det_of and views must be aligned to their element size");
-        n_rec = F * per_frame;
-        x_bytes = xs * 4 * (size_t)n_rec;
-        k_bytes = ks * 3 * (size_t)F * C * (size_t)per_view;
-    }
+    const int64_t n_rec = in.n_rec;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     if (!ctx->pose_ws) HIP_TRY(hipMalloc(&ctx->pose_ws, sizeof(double) * pose_ws_doubles(C)));   // the first call on this context, and no later one
-    const void *dx = F ? xyzs : nullptr, *dk = F ? kpts : nullptr;   // (an empty batch looks at no input pointer)
-    const int32_t *dnp = F ? n_persons : nullptr, *ddet = F ? det_of : nullptr;
-    const uint32_t *dviews = F ? views : nullptr;
     double *dR = R_out, *dt = t_out, *d_cost = cost, *d_normal = normal;
     int64_t *d_nobs = n_obs;
     uint8_t *d_codes = codes;
     Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
-    sg.in(&dx, x_bytes);
-    sg.in(&dk, k_bytes);
-    sg.in(&dnp, sizeof(int32_t) * (size_t)F * C);
-    sg.in(&ddet, sizeof(int32_t) * (size_t)F * C * P);
-    sg.in(&dviews, sizeof(uint32_t) * (size_t)n_rec);
+    in.stage(sg);
     sg.out(&dR, sizeof(double) * 9 * (size_t)C);
     sg.out(&dt, sizeof(double) * 3 * (size_t)C);
     sg.out(&d_cost, sizeof(double) * 2 * (size_t)C);
@@ -2397,11 +2374,22 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
     const int G = n_rec ? grid_for(n_rec, kPoseBlock, kPoseGridCap) : 0;
     const int n_eval = n_rec ? (int)iters : 0;   // evaluations behind the one at the input pose: 2 (iters + 1) launches whatever the data does
     for (int e = 0; e <= n_eval; e++) {
+        const double *trial = e ? ws + pose_ws_trial(C) : base;
+        const int32_t *active = e ? reinterpret_cast<const int32_t *>(ws + pose_ws_active(C)) : nullptr;
         if (G)
-            launch_pose_normal(xyz_dtype, kpts_dtype, dim3((unsigned)G, (unsigned)C), st, n_rec, C, (int)P, (int)Pmax, (int)kn,
-                               keypoint_score_threshold, flags, base, e ? ws + pose_ws_trial(C) : base,
-                               e ? reinterpret_cast<const int32_t *>(ws + pose_ws_active(C)) : nullptr, dx, dk, dnp, ddet, dviews,
-                               ws + pose_ws_partials(C));
+            with_float_pair(xyz_dtype, kpts_dtype, [&](auto tx, auto tk) {
+                using TX = decltype(tx);
+                using TK = decltype(tk);
+#ifdef SNOWTRI_POSE_PER_RECORD   // (a development build: the shape that lost, EXPERIMENTS.md round 22)
+                const auto kernel = k_pose_normal_rec<TX, TK>;
+                const dim3 grid((unsigned)G);
+#else
+                const auto kernel = k_pose_normal<TX, TK>;
+                const dim3 grid((unsigned)G, (unsigned)C);
+#endif
+                hipLaunchKernelGGL(kernel, grid, dim3(kPoseBlock), 0, st, n_rec, C, (int)P, (int)Pmax, (int)kn, keypoint_score_threshold, flags, base,
+                                   trial, active, (const TX *)in.dx, (const TK *)in.dk, in.dnp, in.ddet, in.dviews, ws + pose_ws_partials(C));
+            });
         hipLaunchKernelGGL(k_pose_step, dim3(1), dim3(kPoseStepBlock), 0, st, C, G, e, e == n_eval ? 1 : 0, free_mask, (int)min_obs, base, ws, dR, dt,
                            d_cost, d_nobs, d_codes, d_normal);
     }

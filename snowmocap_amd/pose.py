@@ -31,8 +31,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import POSE_FEW_OBS, POSE_FIXED, POSE_KEPT, POSE_MOVED, free_mask  # noqa: F401
-from .records import missing_records
-from .refine import MAX_CAMERAS, _check_iters
+from .records import missing_records  # noqa: F401
+from .refine import _check_iters, observation_sets, project_camera  # noqa: F401  (rule 1 and the projection are stated there, once)
 from .reproject import _rig
 
 H_INDEX = [(a, b) for a in range(6) for b in range(a + 1)]      # normal[7 + k] = H[a][b]: the lower triangle row by row
@@ -76,18 +76,6 @@ def apply_delta(Rc, tc, delta):
         for j in range(3):
             Rn[i, j] = (E[i, 0] * Rc[0, j] + E[i, 1] * Rc[1, j]) + E[i, 2] * Rc[2, j]
     return Rn, np.array([tc[0] + delta[3], tc[1] + delta[4], tc[2] + delta[5]])
-
-
-def project_camera(Kc, Rc, tc, X):
-    """Rules 1 and 3 of "Reprojection" for one camera: X [n, 3] -> x, y, pc2, u, v, ok [n] (ok: pc2 > 0 and a finite pixel)."""
-    d0, d1, d2 = X[:, 0] - tc[0], X[:, 1] - tc[1], X[:, 2] - tc[2]
-    pc0 = (Rc[0, 0] * d0 + Rc[1, 0] * d1) + Rc[2, 0] * d2
-    pc1 = (Rc[0, 1] * d0 + Rc[1, 1] * d1) + Rc[2, 1] * d2
-    pc2 = (Rc[0, 2] * d0 + Rc[1, 2] * d1) + Rc[2, 2] * d2
-    x, y = pc0 / pc2, pc1 / pc2
-    u = (Kc[0, 0] * x + Kc[0, 1] * y) + Kc[0, 2]
-    v = Kc[1, 1] * y + Kc[1, 2]
-    return x, y, pc2, u, v, (pc2 > 0) & np.isfinite(u) & np.isfinite(v)
 
 
 def pose_jacobian(Kc, Rc, tc, X):
@@ -158,49 +146,6 @@ def solve_normal(normal):
                 s = s - L[k, a] * delta[k]
             delta[a] = s
     return delta, pd
-
-
-def observation_sets(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, score_weights=False):
-    """Rule 1 -> X [N, 3] (the records' points, (0, 0, 0) for a missing one), S [C, N] bool, obs [C, N, 3] = (u_obs, v_obs, w)."""
-    K, R, t, _, C = _rig(K, R, t, None)
-    if C > MAX_CAMERAS:
-        raise ValueError(f"more than {MAX_CAMERAS} cameras")
-    thr = float(keypoint_score_threshold)
-    if thr != thr:
-        raise ValueError("keypoint_score_threshold is NaN")
-    xin = _lib.host_floats(xyzs)
-    if xin.ndim != 4 or xin.shape[-1] != 4:
-        raise ValueError(f"xyzs must be [F, P, kn, 4] records (got shape {xin.shape})")
-    F, P, kn, _ = xin.shape
-    kp = np.asarray(kpts).astype(np.float64)
-    if kp.ndim != 5 or kp.shape[:2] != (F, C) or kp.shape[3:] != (kn, 3) or kp.shape[2] < 1:
-        raise ValueError(f"kpts must be [F={F}, C={C}, Pmax >= 1, kn={kn}, 3] (got shape {kp.shape})")
-    Pmax = kp.shape[2]
-    if det_of is None:
-        if P > Pmax:
-            raise ValueError("det_of=None pairs person p with detection p: P must not exceed Pmax")
-        q = np.broadcast_to(np.arange(P, dtype=np.int64), (F, C, P))
-    else:
-        q = np.asarray(det_of).astype(np.int64).reshape(F, C, P)
-    nq = np.full((F, C), Pmax, dtype=np.int64) if n_persons is None else np.asarray(n_persons).astype(np.int64).reshape(F, C)
-    N = F * P * kn
-    x4 = xin.astype(np.float64)
-    measured = ~missing_records(x4).reshape(N)
-    listed = (q >= 0) & (q < nq[..., None]) & (q < Pmax)
-    obs = np.take_along_axis(kp, np.where(listed, q, 0)[..., None, None], axis=2) if N else np.zeros((F, C, P, kn, 3))
-    obs = np.moveaxis(obs, 1, 0).reshape(C, N, 3).copy()
-    listed = np.moveaxis(np.broadcast_to(listed[..., None], (F, C, P, kn)), 1, 0).reshape(C, N)
-    allowed = np.full(N, 0xffffffff, dtype=np.uint32) if views is None else np.asarray(views).astype(np.uint32).reshape(N)
-    X = np.where(measured[:, None], x4.reshape(N, 4)[:, :3], 0.0)
-    S = np.zeros((C, N), dtype=bool)
-    with np.errstate(all="ignore"):
-        for c in range(C):
-            ok = project_camera(K[c], R[c], t[c], X)[5]
-            bit = ((allowed >> np.uint32(c)) & 1).astype(bool)
-            S[c] = measured & listed[c] & np.isfinite(obs[c, :, 0]) & np.isfinite(obs[c, :, 1]) & ~(obs[c, :, 2] < thr) & bit & ok
-    if not score_weights:
-        obs[..., 2] = 1.0
-    return X, S, obs
 
 
 def refine_cameras_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None,

@@ -53,14 +53,24 @@ def refine_args(refine):
     return _check_iters(iters), float(gate_px), bool(score_weights)
 
 
-def refine_joints_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4,
-                            score_weights=False, return_views=False):
-    """The rule in NumPy: xyzs [F, P, kn, 4] (float32 / float64), kpts [F, C, Pmax, kn, 3], det_of [F, C, P] or None, n_persons
-    [F, C] or None, views [F, P, kn] (bit c: camera c may be used) or None ->
-    (out: xyzs' shape and dtype, cost [F, P, kn, 2] float64, codes [F, P, kn] uint8); with return_views also the view set V of
-    every record as a mask [F, P, kn] uint32 (0 for a copied record)."""
+def project_camera(Kc, Rc, tc, X):
+    """Rules 1 and 3 of "Reprojection" for one camera: X [n, 3] -> x, y, pc2, u, v, ok [n] (ok: pc2 > 0 and a finite pixel)."""
+    d0, d1, d2 = X[:, 0] - tc[0], X[:, 1] - tc[1], X[:, 2] - tc[2]
+    pc0 = (Rc[0, 0] * d0 + Rc[1, 0] * d1) + Rc[2, 0] * d2
+    pc1 = (Rc[0, 1] * d0 + Rc[1, 1] * d1) + Rc[2, 1] * d2
+    pc2 = (Rc[0, 2] * d0 + Rc[1, 2] * d1) + Rc[2, 2] * d2
+    x, y = pc0 / pc2, pc1 / pc2
+    u = (Kc[0, 0] * x + Kc[0, 1] * y) + Kc[0, 2]
+    v = Kc[1, 1] * y + Kc[1, 2]
+    return x, y, pc2, u, v, (pc2 > 0) & np.isfinite(u) & np.isfinite(v)
+
+
+def observation_sets(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, score_weights=False):
+    """Rule 1 of "Refinement" without its at-least-two-views clause, which is rule 1 of "Camera pose refinement": which observation of
+    which camera is a view of which record.  xyzs [F, P, kn, 4], kpts [F, C, Pmax, kn, 3], det_of [F, C, P] or None, n_persons [F, C]
+    or None, views [F, P, kn] (bit c: camera c may be used) or None ->
+    X [N, 3] (the records' points, (0, 0, 0) for a missing one), S [C, N] bool, obs [C, N, 3] = (u_obs, v_obs, w)."""
     K, R, t, _, C = _rig(K, R, t, None)
-    iters = _check_iters(iters)
     if C > MAX_CAMERAS:
         raise ValueError(f"more than {MAX_CAMERAS} cameras")
     thr = float(keypoint_score_threshold)
@@ -86,22 +96,38 @@ def refine_joints_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, vi
     measured = ~missing_records(x4).reshape(N)
     listed = (q >= 0) & (q < nq[..., None]) & (q < Pmax)                                               # [F, C, P]
     obs = np.take_along_axis(kp, np.where(listed, q, 0)[..., None, None], axis=2) if N else np.zeros((F, C, P, kn, 3))
-    obs = np.moveaxis(obs, 1, 0).reshape(C, N, 3)                                                      # [C, N, (u, v, s)]
+    obs = np.moveaxis(obs, 1, 0).reshape(C, N, 3).copy()                                               # [C, N, (u, v, s)]
     listed = np.moveaxis(np.broadcast_to(listed[..., None], (F, C, P, kn)), 1, 0).reshape(C, N)
     allowed = np.full(N, 0xffffffff, dtype=np.uint32) if views is None else np.asarray(views).astype(np.uint32).reshape(N)
+    X = np.where(measured[:, None], x4.reshape(N, 4)[:, :3], 0.0)
+    S = np.zeros((C, N), dtype=bool)
+    with np.errstate(all="ignore"):
+        for c in range(C):
+            ok = project_camera(K[c], R[c], t[c], X)[5]
+            bit = ((allowed >> np.uint32(c)) & 1).astype(bool)
+            S[c] = measured & listed[c] & np.isfinite(obs[c, :, 0]) & np.isfinite(obs[c, :, 1]) & ~(obs[c, :, 2] < thr) & bit & ok
+    if not score_weights:
+        obs[..., 2] = 1.0
+    return X, S, obs
+
+
+def refine_joints_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4,
+                            score_weights=False, return_views=False):
+    """The rule in NumPy: xyzs [F, P, kn, 4] (float32 / float64), kpts [F, C, Pmax, kn, 3], det_of [F, C, P] or None, n_persons
+    [F, C] or None, views [F, P, kn] (bit c: camera c may be used) or None ->
+    (out: xyzs' shape and dtype, cost [F, P, kn, 2] float64, codes [F, P, kn] uint8); with return_views also the view set V of
+    every record as a mask [F, P, kn] uint32 (0 for a copied record)."""
+    K, R, t, _, C = _rig(K, R, t, None)
+    iters = _check_iters(iters)
+    X, V, obs = observation_sets(K, R, t, xyzs, kpts, det_of, n_persons, views, keypoint_score_threshold, score_weights)
+    xin = _lib.host_floats(xyzs)
+    F, P, kn, _ = xin.shape
+    N = F * P * kn
+    measured = ~missing_records(xin).reshape(N)
 
     def project(X):
         """X [n, 3] -> x, y, pc2, u, v, ok [C, n] (rules 1, 3 and the geometric half of rule 4 of "Reprojection")."""
-        out = []
-        for c in range(C):
-            d0, d1, d2 = X[:, 0] - t[c, 0], X[:, 1] - t[c, 1], X[:, 2] - t[c, 2]
-            pc0 = (R[c, 0, 0] * d0 + R[c, 1, 0] * d1) + R[c, 2, 0] * d2
-            pc1 = (R[c, 0, 1] * d0 + R[c, 1, 1] * d1) + R[c, 2, 1] * d2
-            pc2 = (R[c, 0, 2] * d0 + R[c, 1, 2] * d1) + R[c, 2, 2] * d2
-            x, y = pc0 / pc2, pc1 / pc2
-            u = K[c, 0, 0] * x + K[c, 0, 1] * y + K[c, 0, 2]
-            v = K[c, 1, 1] * y + K[c, 1, 2]
-            out.append((x, y, pc2, u, v, (pc2 > 0) & np.isfinite(u) & np.isfinite(v)))
+        out = [project_camera(K[c], R[c], t[c], X) for c in range(C)]
         return [np.stack(a) for a in zip(*out)] if out else [np.zeros((0, X.shape[0]))] * 6
 
     def evaluate(X, V, ou, ov, w):
@@ -143,14 +169,9 @@ def refine_joints_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, vi
         return np.stack([s0, s1, s2], axis=1), pd
 
     with np.errstate(all="ignore"):
-        X = np.where(measured[:, None], x4.reshape(N, 4)[:, :3], 0.0)
-        ok0 = project(X)[5]
-        bit = ((allowed[None, :] >> np.arange(C, dtype=np.uint32)[:, None]) & 1).astype(bool)
-        V = measured[None, :] & listed & np.isfinite(obs[..., 0]) & np.isfinite(obs[..., 1]) & ~(obs[..., 2] < thr) & bit & ok0
         few = V.sum(axis=0) < 2
         V &= ~few[None, :]
-        ou, ov = np.where(V, obs[..., 0], 0.0), np.where(V, obs[..., 1], 0.0)
-        w = np.where(V, obs[..., 2] if score_weights else 1.0, 0.0)
+        ou, ov, w = np.where(V, obs[..., 0], 0.0), np.where(V, obs[..., 1], 0.0), np.where(V, obs[..., 2], 0.0)
         E, H, g, _ = evaluate(X, V, ou, ov, w)
         E0 = E.copy()
         active = measured & ~few
