@@ -2409,6 +2409,72 @@ const char *type_name() {
     return sizeof(T) == 4 ? "float" : "double";
 }
 
+// "k_name<a,b,...>": a kernel as snowtri_last_kernel_names spells it, its template arguments without spaces.
+std::string kernel_name(const char *kernel, const std::vector<std::string> &args) {
+    std::string s = std::string(kernel) + "<";
+    for (size_t i = 0; i < args.size(); i++) s += (i ? "," : "") + args[i];
+    return s + ">";
+}
+
+// fn(std::integral_constant<int, CC>()) for the one camera count CC == C in [Lo, Hi]; false when there is none.  A generic lambda
+// takes the constant with decltype and launches the kernel instantiated for it, so [Lo, Hi] is what a route instantiates.
+// Kernel-development builds (-DSNOWTRI_DEV_MIN, scripts/ab_build.sh): 4 cameras only.
+template <int Lo, int Hi, typename Fn>
+bool with_cameras(int C, Fn &&fn) {
+    if constexpr (Lo > Hi) {
+        return false;
+    } else {
+#ifdef SNOWTRI_DEV_MIN
+        constexpr bool kept = Lo == 4;
+#else
+        constexpr bool kept = true;
+#endif
+        if constexpr (kept)
+            if (C == Lo) {
+                fn(std::integral_constant<int, Lo>());
+                return true;
+            }
+        return with_cameras<Lo + 1, Hi>(C, fn);
+    }
+}
+
+// ... and fn(std::integral_constant<int, TT>()) for the instantiated workgroup shape of k_candidate_sums that `threads` names
+// (sums_launch_shape rounds to one of them).
+template <typename Fn>
+void with_sums_threads(int threads, Fn &&fn) {
+    if (threads == 256) fn(std::integral_constant<int, 256>());
+    else if (threads == 512) fn(std::integral_constant<int, 512>());
+    else fn(std::integral_constant<int, 1024>());
+}
+
+// A kernel that asks for more dynamic LDS than the 48 KB every kernel may have: the limit is raised first (snowtri_ctx::raise_lds).
+int raise_lds_or_fail(snowtri_ctx *ctx, const void *kern, size_t lds) {
+    if (lds > 48 * 1024 && ctx->raise_lds(kern, (int)lds)) {
+        g_last_error = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
+        return SNOWTRI_ERR_HIP;
+    }
+    return SNOWTRI_OK;
+}
+
+// Every launch of the fused call.  `may_attach`: this dispatch is the call's ONE kernel, so with snowtri_set_timing(ctx, 2) the
+// ring's event pair rides on the dispatch itself: begin and end of THIS kernel as its completion signal records them (what
+// rocprofv3's kernel trace reads), without the two barrier packets of a bracketing pair in the interval.
+template <typename... KArgs, typename... Args>
+int launch_kernel(snowtri_ctx *ctx, hipStream_t st, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds, bool may_attach,
+                  const Args &...args) {
+    static_assert(sizeof...(KArgs) == sizeof...(Args), "one argument per kernel parameter");
+    if (int rc = raise_lds_or_fail(ctx, (const void *)kern, lds)) return rc;
+    if (may_attach && ctx->timing && ctx->timing_attach) {
+        const int64_t slot = ctx->ev_count % kTimingRing;
+        hipExtLaunchKernelGGL(kern, grid, block, lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0, args...);
+        ctx->ev_attached = true;
+    } else {
+        hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    }
+    HIP_TRY(hipGetLastError());
+    return SNOWTRI_OK;
+}
+
 // Frames per tile for the fast kernel: maximise (lane utilisation of the item loop: T*J items in
 // 256-wide passes) x (balance of the tiles over the CUs -- the kernel is fp64-VALU-bound, so a CU
 // with one more tile than its neighbours sets the launch time), under the LDS budget.  Prefer
@@ -2450,19 +2516,10 @@ int launch_fused_single(snowtri_ctx *ctx, hipStream_t st, int64_t F, int J, cons
     int rc = ctx->cur->work.ensure(per_block * (size_t)grid);
     if (rc) return rc;
     const size_t lds = fused_single_lds_bytes(T, prm.kn, NP);
-    auto kern = k_fused_single<C, METHOD, TIn, TOut>;
-    if (lds > 48 * 1024)
-        {
-            if (ctx->raise_lds((const void *)kern, (int)lds)) {
-                g_last_error = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
-                return SNOWTRI_ERR_HIP;
-            }
-        }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, F, J, T, ctx->rig(), d_kpts, d_np, prm, Pout,
-                       d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
-    HIP_TRY(hipGetLastError());
-    static const std::string name = std::string("k_fused_single<") + std::to_string(C) + "," + std::to_string(METHOD) + "," +
-                                    type_name<TIn>() + "," + type_name<TOut>() + ">";
+    rc = launch_kernel(ctx, st, k_fused_single<C, METHOD, TIn, TOut>, dim3(grid), dim3(kBlock), lds, false, F, J, T, ctx->rig(), d_kpts, d_np,
+                       prm, Pout, d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
+    if (rc) return rc;
+    static const std::string name = kernel_name("k_fused_single", {std::to_string(C), std::to_string(METHOD), type_name<TIn>(), type_name<TOut>()});
     ctx->last_kernels = name.c_str();
     return SNOWTRI_OK;
 }
@@ -2476,6 +2533,14 @@ int launch_fused_single(snowtri_ctx *ctx, hipStream_t st, int64_t F, int J, cons
 constexpr int kLeanJ = 133;
 constexpr int kFusedSingleMaxCams = 4;   // k_fused_single's pairwise item (everything in registers): up to six pairs
 constexpr int kLeanTilesPerWave = 4;
+
+// The two lean kernels name their output type only where it is not float.
+template <int C, typename TIn, typename TOut>
+std::string lean_kernel_name(const char *kernel) {
+    std::vector<std::string> args{std::to_string(C), type_name<TIn>(), std::to_string(kLeanJ)};
+    if (sizeof(TOut) == 8) args.push_back("double");
+    return kernel_name(kernel, args);
+}
 
 template <int C, typename TIn, typename TOut = float>
 int launch_fused_lean(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_kpts, const int32_t *d_np,
@@ -2500,7 +2565,6 @@ int launch_fused_lean(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_
     // small launch (at most kCoopMaxFrames frames per resident workgroup): workgroup tiles, passes dealt to the waves,
     // cooperative epilogue (k_fused_lean_coop)
     if (ctx->lean_coop != 0 && F <= (int64_t)ctx->num_cus * wg_small * kCoopMaxFrames) {
-        auto kc = k_fused_lean_coop<C, TIn, kLeanJ, TOut>;
         const int grid = (int)std::min<int64_t>(F, (int64_t)ctx->num_cus * wg_small);
         const int base = (int)(F / grid);
         const int64_t rem = F % grid;
@@ -2508,22 +2572,11 @@ int launch_fused_lean(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_
         const size_t lds = lean_coop_lds_bytes(C, kLeanJ, nf_max, kScoreBytes);
         int rc = ctx->cur->work.ensure(per_block * (size_t)grid);
         if (rc) return rc;
-        if (lds > 48 * 1024 && ctx->raise_lds((const void *)kc, (int)lds)) return SNOWTRI_ERR_HIP;
         if (ctx->debug) fprintf(stderr, "k_fused_lean_coop: F %lld grid %d frames per tile %d (+1 for %lld) lds %zu\n", (long long)F, grid, base, (long long)rem, lds);
-        if (ctx->timing && ctx->timing_attach) {
-            // the ring's event pair rides on the dispatch itself: begin and end of THIS kernel as its completion signal records
-            // them (what rocprofv3's kernel trace reads), without the two barrier packets of a bracketing pair in the interval
-            const int64_t slot = ctx->ev_count % kTimingRing;
-            hipExtLaunchKernelGGL(kc, dim3(grid), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
-                                  F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, un, d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
-            ctx->ev_attached = true;
-        } else {
-            hipLaunchKernelGGL(kc, dim3(grid), dim3(kBlock), lds, st, F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, un, d_xyzs, d_ps, d_cnt,
-                               d_fl, (char *)ctx->cur->work.p, per_block);
-        }
-        HIP_TRY(hipGetLastError());
-        static const std::string cname = std::string("k_fused_lean_coop<") + std::to_string(C) + "," + type_name<TIn>() + "," +
-                                         std::to_string(kLeanJ) + (kScoreBytes == 8 ? ",double>" : ">");
+        rc = launch_kernel(ctx, st, k_fused_lean_coop<C, TIn, kLeanJ, TOut>, dim3(grid), dim3(kBlock), lds, true, F, base, rem, nf_max, ctx->rig(),
+                           d_kpts, d_np, prm, un, d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
+        if (rc) return rc;
+        static const std::string cname = lean_kernel_name<C, TIn, TOut>("k_fused_lean_coop");
         ctx->last_kernels = cname.c_str();
         return SNOWTRI_OK;
     }
@@ -2553,35 +2606,20 @@ int launch_fused_lean(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_
         const size_t lds = lean_lds_bytes(C, kLeanJ, slow_words, kScoreBytes);
         int rc = ctx->cur->work.ensure(per_block * (size_t)grid);
         if (rc) return rc;
-        if (lds > 48 * 1024)
-            {
-            if (ctx->raise_lds((const void *)kern, (int)lds)) {
-                g_last_error = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
-                return SNOWTRI_ERR_HIP;
-            }
-        }
-        if (ctx->debug) {
+        // one segment = one kernel (Fs == F, so s0 == 0): its own begin / end, as k_fused_lean_coop above
+        rc = launch_kernel(ctx, st, kern, dim3(grid), dim3(kBlock), lds, Fs == F, Fs, ntiles, base, rem, slow_words, ctx->rig(),
+                           d_kpts + s0 * (int64_t)(C * kLeanJ * 3), d_np ? d_np + s0 * C : nullptr, prm, un,
+                           d_xyzs + s0 * (int64_t)(kLeanJ * 4), d_ps ? d_ps + s0 : nullptr, d_cnt + s0,
+                           d_fl ? d_fl + s0 : nullptr, (char *)ctx->cur->work.p, per_block);
+        if (rc) return rc;
+        if (ctx->debug) {   // (behind the launch: the limit of a launch above 48 KB is raised by then)
             int occ = 0;
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kBlock, lds);
             fprintf(stderr, "k_fused_lean: F %lld grid %d tiles %lld (%d frames +1 for %lld) lds %zu occupancy/CU %d\n",
                     (long long)Fs, grid, (long long)ntiles, base, (long long)rem, lds, occ);
         }
-        if (ctx->timing && ctx->timing_attach && Fs == F) {   // one segment = one kernel: its own begin / end (see k_fused_lean_coop above)
-            const int64_t slot = ctx->ev_count % kTimingRing;
-            hipExtLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
-                                  Fs, ntiles, base, rem, slow_words, ctx->rig(), d_kpts, d_np, prm, un, d_xyzs, d_ps, d_cnt, d_fl,
-                                  (char *)ctx->cur->work.p, per_block);
-            ctx->ev_attached = true;
-        } else {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, Fs, ntiles, base, rem, slow_words, ctx->rig(),
-                               d_kpts + s0 * (int64_t)(C * kLeanJ * 3), d_np ? d_np + s0 * C : nullptr, prm, un,
-                               d_xyzs + s0 * (int64_t)(kLeanJ * 4), d_ps ? d_ps + s0 : nullptr, d_cnt + s0,
-                               d_fl ? d_fl + s0 : nullptr, (char *)ctx->cur->work.p, per_block);
-        }
-        HIP_TRY(hipGetLastError());
     }
-    static const std::string name = std::string("k_fused_lean<") + std::to_string(C) + "," + type_name<TIn>() + "," +
-                                    std::to_string(kLeanJ) + (kScoreBytes == 8 ? ",double>" : ">");
+    static const std::string name = lean_kernel_name<C, TIn, TOut>("k_fused_lean");
     ctx->last_kernels = name.c_str();
     return SNOWTRI_OK;
 }
@@ -2599,26 +2637,14 @@ int launch_frame_general(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, 
     grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kMaxScratchBytes / per_block)));
     int rc = ctx->cur->work.ensure(per_block * (size_t)grid);
     if (rc) return rc;
-    const size_t lds = condense_lds_bytes((int)Kc);
-    auto kern = k_frame_general<TIn, TOut>;
-    if (lds > 48 * 1024)
-        {
-            if (ctx->raise_lds((const void *)kern, (int)lds)) {
-                g_last_error = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
-                return SNOWTRI_ERR_HIP;
-            }
-        }
-    hipLaunchKernelGGL(kern, dim3((int)grid), dim3(kBlock), lds, st, F, Pmax, J, (int)Kc, ctx->rig(), d_kpts, d_np,
-                       prm, Pout, d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
-    HIP_TRY(hipGetLastError());
-    static const std::string name = std::string("k_frame_general<") + type_name<TIn>() + "," + type_name<TOut>() + ">";
+    rc = launch_kernel(ctx, st, k_frame_general<TIn, TOut>, dim3((int)grid), dim3(kBlock), condense_lds_bytes((int)Kc), false, F, Pmax, J, (int)Kc,
+                       ctx->rig(), d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl, (char *)ctx->cur->work.p, per_block);
+    if (rc) return rc;
+    static const std::string name = kernel_name("k_frame_general", {type_name<TIn>(), type_name<TOut>()});
     ctx->last_kernels = name.c_str();
     return SNOWTRI_OK;
 }
 
-// The streaming kernels for the descriptors a k_frame_recompute launch over Fs frames left behind (snowtri_cluster.hpp):
-// `cnt[0]` complete-graph clusters in desc[0, cap), `cnt[1]` clusters of any other shape in desc[cap, 2 cap) with their
-// member words in `words`.
 // method = SNOWTRI_DLT, one detection per camera, keypoint_num == J == 133, one slot: k_dlt_coop (snowtri_dlt_lean.hpp).  Workgroup
 // tiles of equal size (+-1 frame): as many as the resident workgroups for a small batch, tiles of kCoopMaxFrames frames beyond.
 template <int C, typename TIn, typename TOut>
@@ -2630,41 +2656,12 @@ int launch_dlt_coop(snowtri_ctx *ctx, hipStream_t st, int64_t F, const TIn *d_kp
     const int64_t rem = F % tiles;
     const int nf_max = base + (rem ? 1 : 0);
     const size_t lds = dlt_coop_lds_bytes(C, kLeanJ, nf_max, (int)sizeof(TOut));
-    auto kern = k_dlt_coop<C, TIn, kLeanJ, TOut>;
-    if (lds > 48 * 1024 && ctx->raise_lds((const void *)kern, (int)lds)) return SNOWTRI_ERR_HIP;
-    if (ctx->timing && ctx->timing_attach) {   // one kernel: the ring's event pair rides on its dispatch (see launch_fused_lean)
-        const int64_t slot = ctx->ev_count % kTimingRing;
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
-                              F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);
-        ctx->ev_attached = true;
-    } else {
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, F, base, rem, nf_max, ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);
-    }
-    HIP_TRY(hipGetLastError());
-    static const std::string name = std::string("k_dlt_coop<") + std::to_string(C) + "," + type_name<TIn>() + ",133," + type_name<TOut>() + ">";
+    // one kernel: the ring's event pair rides on its dispatch
+    int rc = launch_kernel(ctx, st, k_dlt_coop<C, TIn, kLeanJ, TOut>, dim3((unsigned)tiles), dim3(kBlock), lds, true, F, base, rem, nf_max,
+                           ctx->rig(), d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);
+    if (rc) return rc;
+    static const std::string name = kernel_name("k_dlt_coop", {std::to_string(C), type_name<TIn>(), std::to_string(kLeanJ), type_name<TOut>()});
     ctx->last_kernels = name.c_str();
-    return SNOWTRI_OK;
-}
-
-template <int C, typename TIn, typename TOut>
-int launch_cluster_fuse(snowtri_ctx *ctx, hipStream_t st, int64_t Fs, int Pmax, int J, const TIn *d_kpts, const Params &prm,
-                        int Pout, TOut *d_xyzs, uint32_t *d_fl, const ClusterDesc *desc, const uint32_t *words,
-                        const unsigned long long *cnt, uint32_t cap) {
-    const int kn = prm.kn;
-    const int64_t passes_max = (Fs * Pout * (int64_t)kn + 63) / 64;
-    // exactly the waves that are resident at once (kClusterWaves per SIMD at this kernel's registers), each striding over
-    // the passes: with the member lists in a kernel of their own every pass costs the same, and short-lived workgroups only
-    // added their start-up (8 x 4: 334 -> 312 us).  (k_cluster_members on a second stream beside this kernel: measured, no gain.)
-    const int64_t W = std::min<int64_t>(passes_max, (int64_t)ctx->num_cus * 4 * kClusterWaves);
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((W + kBlock / 64 - 1) / (kBlock / 64), (int64_t)ctx->num_cus * 64));
-    const unsigned long long kmagic = (((unsigned long long)1 << 40) + (unsigned long long)kn - 1) / (unsigned long long)kn;
-    hipLaunchKernelGGL((k_cluster_fuse<C, TIn, TOut>), dim3(grid), dim3(kBlock), cluster_lds_bytes(C), st, desc, cnt, cap, ctx->rig(), d_kpts, prm,
-                       Pmax, J, kn, kmagic, Pout, d_xyzs, d_fl);
-    HIP_TRY(hipGetLastError());
-    const int gridm = (int)std::max<int64_t>(1, std::min<int64_t>((passes_max + 3) / 4, (int64_t)ctx->num_cus * 16));
-    hipLaunchKernelGGL((k_cluster_members<TIn, TOut>), dim3(gridm), dim3(kBlock), cluster_members_lds_bytes(C, ctx->npairs), st, desc, words, cnt,
-                       cap, ctx->rig(), d_kpts, prm, Pmax, J, kn, kmagic, Pout, d_xyzs, d_fl);
-    HIP_TRY(hipGetLastError());
     return SNOWTRI_OK;
 }
 
@@ -2689,36 +2686,20 @@ SumsLaunch sums_launch_shape(const snowtri_ctx *ctx, int Pmax, int J) {
 
 // Multi-person path without HBM candidate spill: k_frame_recompute (snowtri_general.hpp), or -- float32 outputs,
 // pairwise method, <= 16 cameras -- the streaming association of snowtri_assoc.hpp with k_frame_recompute for the frames
-// it leaves behind.
-template <int METHOD, typename TIn, typename TOut>
-int launch_frame_recompute(snowtri_ctx *ctx, hipStream_t st_call, int64_t F, int Pmax, int J, const TIn *d_kpts,
-                           const int32_t *d_np, const Params &prm, int Pout, TOut *d_xyzs, TOut *d_ps,
-                           int32_t *d_cnt, uint32_t *d_fl) {
+// it leaves behind.  What a call of launch_frame_recompute does is decided here, from its shape and the context's settings
+// alone (no HIP call, no scratch); the stages below read it.
+struct RecomputeRoute {
+    bool can_hand, sumless, sums_kn, post_scores, stream, handover;
+    bool split;          // the segments alternate between the caller's stream set and an internal one
+    SumsLaunch SL;       // (stream)
+    int64_t seg;         // frames per segment
+    long long names_key; // what the route's kernel names depend on (snowtri_ctx::names_key)
+};
+RecomputeRoute recompute_route(const snowtri_ctx *ctx, int METHOD, size_t in_size, size_t out_size, int64_t F, int Pmax, int J, const Params &prm,
+                               int Pout) {
     const int64_t Kc = snowtri_num_candidate_slots(ctx->C, Pmax);
     const int C = ctx->C, R = C * Pmax;
-    const size_t per_block = recompute_scratch_bytes(Kc, R, prm.kn);
-    // three workgroups per CU share the 160 KB of LDS (snowtri_general.hpp: the arena behind the tables is reused
-    // phase by phase)
-    const size_t lds = recompute_launch_lds(C, ctx->npairs);
-    auto kern = k_frame_recompute<METHOD, TIn, TOut>;
-    snowtri_ctx::OccCache &oc = ctx->recompute_occ[METHOD * 4 + (sizeof(TIn) == 8 ? 2 : 0) + (sizeof(TOut) == 8 ? 1 : 0)];
-    if (oc.per_cu < 0 || oc.lds != lds) {
-        // exactly the workgroups that are resident at once (registers and the ~50 KB of LDS decide: 3 per CU);
-        // they pull frames from an atomic counter until none are left
-        if (lds > 48 * 1024)
-            {
-            if (ctx->raise_lds((const void *)kern, (int)lds)) {
-                g_last_error = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
-                return SNOWTRI_ERR_HIP;
-            }
-        }
-        int q = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kern, kBlock, lds));
-        oc.lds = lds;
-        oc.per_cu = q;
-        if (ctx->debug) fprintf(stderr, "k_frame_recompute: R %d Kc %lld lds %zu occupancy/CU %d\n", R, (long long)Kc, lds, q);
-    }
-    int per_cu = oc.per_cu;
+    RecomputeRoute r{};
     // Hand-over of the output persons to the streaming fusion kernels (snowtri_cluster.hpp): pairwise method, 4-bit person
     // fields, non-negative scores (kthr >= 0).  A person's mean score (:150) is derived from the candidate means when
     // keypoint_num == J and the outputs are float32; otherwise k_person_scores takes it from the fused joints afterwards.  The
@@ -2731,60 +2712,359 @@ int launch_frame_recompute(snowtri_ctx *ctx, hipStream_t st_call, int64_t F, int
     // descriptors.  A person's mean score there is the mean of the DLT joint scores (mean confidences >= keypoint_score_threshold
     // >= 0), which the association cannot know: the route is taken when the filter of :151-152 cannot drop anybody
     // (condense_score_tol <= 0, the reference's default); otherwise the frames stay on k_frame_recompute<1>.
-    const bool can_hand = C >= 2 && Pmax <= kClusterMaxPersons && prm.kn >= 1 && J <= 256 && prm.kthr >= 0.0 && Pout >= 1 &&
-                          (size_t)Pout * 24 + 80 <= (size_t)kRayChunkBytes && !(prm.score_tol != prm.score_tol) &&
-                          (METHOD == 0 || prm.score_tol <= 0.0);
+    r.can_hand = C >= 2 && Pmax <= kClusterMaxPersons && prm.kn >= 1 && J <= 256 && prm.kthr >= 0.0 && Pout >= 1 &&
+                 (size_t)Pout * 24 + 80 <= (size_t)kRayChunkBytes && !(prm.score_tol != prm.score_tol) &&
+                 (METHOD == 0 || prm.score_tol <= 0.0);
     // ONE detection per camera with average_score_threshold <= 0 <= keypoint_score_threshold and no mean-score filter: every
     // listed candidate is kept whatever its mean (:80-81; scores that pass the keypoint gate are >= 0), so the candidate pass
     // has nothing to decide.  It is skipped (`sumless`): k_associate reads a constant positive sum for every slot, the
     // persons' mean scores come from the fused joints (k_person_scores), and a singular pair is flagged where its joint is
     // fused (cluster_joint_sequential / cluster_member_passes).  This is the route of single-person rigs of five and more
     // cameras on the shapes the lean kernels do not take (fused_dispatch).
-    const bool sumless = METHOD == 0 && Pmax == 1 && prm.avg_thr <= 0.0 && prm.kthr >= 0.0 && prm.score_tol <= 0.0 && ctx->sumless_mode != 0;
-    const bool sums_kn = !sumless && prm.kn != J && !(prm.score_tol <= 0.0);   // second candidate-sum launch over the first keypoint_num joints
-    const bool post_scores = sumless || sizeof(TOut) == 8 || prm.kn != J || METHOD == 1;   // the persons' mean scores by k_person_scores
-    SumsLaunch SL{};
+    r.sumless = METHOD == 0 && Pmax == 1 && prm.avg_thr <= 0.0 && prm.kthr >= 0.0 && prm.score_tol <= 0.0 && ctx->sumless_mode != 0;
+    r.sums_kn = !r.sumless && prm.kn != J && !(prm.score_tol <= 0.0);   // second candidate-sum launch over the first keypoint_num joints
+    r.post_scores = r.sumless || out_size == 8 || prm.kn != J || METHOD == 1;   // the persons' mean scores by k_person_scores
     // (distance_threshold >= 0: k_candidate_sums reads its distance gate off a sign bit, p1_tile_sums)
-    bool stream = can_hand && ctx->handover_mode == 1 && C <= 16 && Kc < ((int64_t)1 << 24) && Pout <= 1024 && (sumless || prm.dthr >= 0.0);
-    if (stream) {
-        SL = sums_launch_shape(ctx, Pmax, J);
-        stream = SL.Jc >= 1;
+    r.stream = r.can_hand && ctx->handover_mode == 1 && C <= 16 && Kc < ((int64_t)1 << 24) && Pout <= 1024 && (r.sumless || prm.dthr >= 0.0);
+    if (r.stream) {
+        r.SL = sums_launch_shape(ctx, Pmax, J);
+        r.stream = r.SL.Jc >= 1;
     }
-    const bool handover = METHOD == 0 && !stream && can_hand && sizeof(TOut) == 4 && prm.kn == J && ctx->handover_mode != 0 && C <= kClusterMaxCams;
+    r.handover = METHOD == 0 && !r.stream && r.can_hand && out_size == 4 && prm.kn == J && ctx->handover_mode != 0 && C <= kClusterMaxCams;
     // the two descriptor lists hold Pout persons for every frame of a segment (<= 2 M entries each, 64 MB together), the
     // member list Kc words per frame (<= 64 M words, 256 MB); row indices are 32-bit; the candidate sums of the
     // streaming association 8 Kc bytes per frame (<= 1 GB).  Sized for the LARGE rigs: a frame of 16 x 8 holds a CU for
     // ~225 us of its candidate pass, a launch ends with up to one such frame per CU in its tail, and 12 500 frames in
     // four segments of 3 125 (12 frames per CU) paid that tail four times -- now two segments of 6 250.
     int64_t seg_frames = F;
-    if (stream || handover)
+    if (r.stream || r.handover)
         seg_frames = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(((int64_t)2 << 20) / Pout, ((int64_t)64 << 20) / Kc),
                                                           ((int64_t)1 << 31) / R));
-    if (stream) seg_frames = std::max<int64_t>(1, std::min<int64_t>(seg_frames, ((int64_t)128 << 20) / Kc));
+    if (r.stream) seg_frames = std::max<int64_t>(1, std::min<int64_t>(seg_frames, ((int64_t)128 << 20) / Kc));
     const int64_t seg_cap = ctx->handover_seg_frames > 0 ? ctx->handover_seg_frames : seg_frames;
-    int64_t seg = (stream || handover) ? std::min(seg_frames, seg_cap) : F;
+    r.seg = (r.stream || r.handover) ? std::min(seg_frames, seg_cap) : F;
     // ONE call in (at least) two segments on two stream sets: every kernel of the streaming route holds the whole chip
     // while it runs, and a third of the route's time is latency-bound (k_associate: VALU busy ~20 %, the member lists);
     // with the segments alternating between the caller's stream and an internal one, those kernels of one segment run
     // beside the VALU-bound ones of the other (8 x 4: +8 % against one stream; what round 3 measured with two CALLS in
     // flight on two contexts, now inside the call).  Outputs do not depend on the cut (tests/test_gpu_handover.py).  Not
     // in overlap mode (whole calls already alternate over the sets) and not for batches too small to fill the chip twice.
-    StreamSet *const set_call = ctx->cur;
     // (rigs whose candidate pass holds a whole CU per workgroup -- 16 x 8: 1024 threads, 160 KB -- gain little, only the tails
     // of the kernels fill one another: 17.20 -> 17.01 ms per 12 500 frames, six interleaved runs.  Staggering the segments --
     // the second candidate pass waiting for the first so that it runs beside the first's latency-bound kernels -- LOSES:
     // 8 x 4 1.10 -> 1.24 ms; two half-size candidate passes side by side fill each other's tails, one alone does not.)
-    bool split = stream && ctx->split_segments >= 2 && ctx->overlap <= 1 && set_call == &ctx->sets[0];
-    if (split) {
-        int64_t nseg = std::max<int64_t>((F + seg - 1) / seg, ctx->split_segments);
+    r.split = r.stream && ctx->split_segments >= 2 && ctx->overlap <= 1 && ctx->cur == &ctx->sets[0];
+    if (r.split) {
+        int64_t nseg = std::max<int64_t>((F + r.seg - 1) / r.seg, ctx->split_segments);
         nseg += nseg & 1;
         const int64_t even = (F + nseg - 1) / nseg;
         if (even >= (ctx->split_forced ? 1 : (int64_t)ctx->num_cus * 4))   // (the knob set explicitly: tests split small batches too)
-            seg = even;
+            r.seg = even;
         else
-            split = false;
+            r.split = false;
     }
-    if (split) {
+    r.names_key = ((long long)C << 8) | (METHOD << 7) | ((int)in_size << 3) | ((int)out_size >> 2 << 2) | (r.stream ? 2 : 0) |
+                  (r.handover ? 1 : 0) | ((long long)r.SL.threads << 16) | ((long long)(r.sumless ? 1 : 0) << 32) | ((long long)Pmax << 34);
+    return r;
+}
+
+// The kernels of a route, in launch order (rebuilt only when the route changes).
+template <int METHOD, typename TIn, typename TOut>
+void recompute_route_names(snowtri_ctx *ctx, const RecomputeRoute &r) {
+    if (r.names_key != ctx->names_key) {
+        const int C = ctx->C;
+        const std::string tin = type_name<TIn>(), tout = type_name<TOut>();
+        const std::string rec = kernel_name("k_frame_recompute", {std::to_string(METHOD), tin, tout});
+        const std::string fuse = (C <= kClusterMaxCams ? kernel_name("k_cluster_fuse", {std::to_string(C), tin}) : kernel_name("k_cluster_fuse_wide", {tin})) +
+                                 " + " + kernel_name("k_cluster_members", {tin});
+        const std::string sums = kernel_name("k_candidate_sums", {tin, std::to_string(r.SL.threads)}) + " + " + kernel_name("k_candidate_sums_exact", {tin});
+        const std::string assoc = kernel_name("k_associate", {tin}), scores = kernel_name("k_person_scores", {tout});
+        if (r.stream && METHOD == 1)
+            ctx->names_buf = sums + " + " + assoc + " + " + kernel_name("k_cluster_dlt", {std::to_string(C <= kClusterMaxCams ? C : 0), tin, tout}) +
+                             " + " + scores + " + " + rec + " (frames left behind)";
+        else if (r.stream && r.sumless)
+            ctx->names_buf = kernel_name("k_singular_scan", {tin}) + " + " + assoc + " + " + fuse + " + " + scores + " + " + rec + " (frames left behind)";
+        else if (r.stream)
+            ctx->names_buf = sums + " + " + assoc + " + " + fuse + " + " + rec + " (frames left behind)";
+        else if (r.handover)
+            ctx->names_buf = rec + " + " + fuse;
+        else
+            ctx->names_buf = rec;
+        ctx->names_key = r.names_key;
+    }
+    ctx->last_kernels = ctx->names_buf.c_str();
+}
+
+// Resident workgroups per CU of k_frame_recompute<METHOD, TIn, TOut> at `lds` bytes (queried once per LDS size).
+template <int METHOD, typename TIn, typename TOut>
+int recompute_per_cu(snowtri_ctx *ctx, size_t lds, int R, int64_t Kc, int *per_cu) {
+    auto kern = k_frame_recompute<METHOD, TIn, TOut>;
+    snowtri_ctx::OccCache &oc = ctx->recompute_occ[METHOD * 4 + (sizeof(TIn) == 8 ? 2 : 0) + (sizeof(TOut) == 8 ? 1 : 0)];
+    if (oc.per_cu < 0 || oc.lds != lds) {
+        // exactly the workgroups that are resident at once (registers and the ~50 KB of LDS decide: 3 per CU);
+        // they pull frames from an atomic counter until none are left
+        if (int rc = raise_lds_or_fail(ctx, (const void *)kern, lds)) return rc;
+        int q = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kern, kBlock, lds));
+        oc.lds = lds;
+        oc.per_cu = q;
+        if (ctx->debug) fprintf(stderr, "k_frame_recompute: R %d Kc %lld lds %zu occupancy/CU %d\n", R, (long long)Kc, lds, q);
+    }
+    *per_cu = oc.per_cu;
+    return SNOWTRI_OK;
+}
+
+// A launch_frame_recompute call: its shape, what k_frame_recompute needs at that shape, and the caller's arrays.
+template <typename TIn, typename TOut>
+struct RecomputeCall {
+    int Pmax, J, Pout;
+    int64_t Kc;
+    const Params &prm;
+    size_t lds, per_block;      // k_frame_recompute's LDS and slab
+    int per_cu;                 // ... and resident workgroups per CU
+    unsigned long long kmagic;  // item / keypoint_num
+    const TIn *kpts;
+    const int32_t *np;
+    TOut *xyzs, *ps;
+    int32_t *cnt;
+    uint32_t *fl;
+};
+
+// One segment of it: stream, stream set, frames, the segment's part of the arrays, its lists and counters, and what one stage
+// leaves for the next.
+template <typename TIn, typename TOut>
+struct RecomputeSegment {
+    const RecomputeCall<TIn, TOut> &call;
+    hipStream_t st;
+    StreamSet *set;
+    int64_t Fs, grid;           // frames; workgroups of a k_frame_recompute launch over all of them
+    const TIn *kpts;
+    const int32_t *np;
+    TOut *xyzs, *ps;
+    int32_t *cnt;
+    uint32_t *fl;
+    ClusterDesc *desc;          // the descriptor lists: complete graphs in desc[0, cap), the others in desc[cap, 2 cap) with their
+    uint32_t *words;            // member words in `words` (word_cap of them)
+    uint32_t cap, word_cap;
+    unsigned long long *next_frame, *hand_counters, *slow_count, *exact_count, *slow_count2, *sums_ticket;
+    // candidate stage -> association
+    double *csum, *csum_kn;
+    uint32_t *slow_list, *exact_list;
+    // association -> k_frame_recompute: the frames left behind
+    const uint32_t *final_slow_list;
+    const unsigned long long *final_slow_count;
+};
+
+// Segment [s0, s0 + Fs) of g.call on stream set S: the slabs and descriptor lists it needs, its counters cleared on `st`.
+template <typename TIn, typename TOut>
+int open_segment(snowtri_ctx *ctx, const RecomputeRoute &r, StreamSet &S, hipStream_t st, int64_t s0, int64_t Fs, RecomputeSegment<TIn, TOut> &g) {
+    const RecomputeCall<TIn, TOut> &call = g.call;
+    const int C = ctx->C, R = C * call.Pmax;
+    ctx->cur = &S;
+    ctx->last_set = &S;
+    g.st = st;
+    g.set = &S;
+    g.Fs = Fs;
+    g.next_frame = S.d_counters + 2, g.hand_counters = S.d_counters + kHandCountersAt, g.slow_count = S.d_counters + 6;
+    g.exact_count = S.d_counters + 7, g.slow_count2 = S.d_counters + 8, g.sums_ticket = S.d_counters + 9;
+    g.grid = std::min<int64_t>(Fs, (int64_t)ctx->num_cus * std::max(1, call.per_cu));
+    g.grid = std::max<int64_t>(1, std::min<int64_t>(g.grid, (int64_t)(kMaxScratchBytes / call.per_block)));
+    int rc = S.work.ensure(call.per_block * (size_t)g.grid);
+    if (rc) return rc;
+    g.cap = 0, g.word_cap = 0;
+    g.desc = nullptr;
+    g.words = nullptr;
+    if (r.stream || r.handover) {
+        ctx->last_handover = true;
+        g.cap = (uint32_t)(Fs * call.Pout);
+        g.word_cap = (uint32_t)(Fs * call.Kc);
+        rc = S.desc.ensure((size_t)2 * g.cap * sizeof(ClusterDesc) + (size_t)g.word_cap * 4);
+        if (rc) return rc;
+        g.desc = (ClusterDesc *)S.desc.p;
+        g.words = (uint32_t *)(g.desc + (size_t)2 * g.cap);
+    }
+    HIP_TRY(hipMemsetAsync(g.next_frame, 0, (kCounterWords - 2) * sizeof(unsigned long long), st));   // next_frame, slow / exact / slow (second pass) frames, the frame tickets of k_candidate_sums, the hand-over list counters
+    g.kpts = call.kpts + s0 * (int64_t)R * call.J * 3;
+    g.np = call.np ? call.np + s0 * C : nullptr;
+    g.xyzs = call.xyzs + s0 * (int64_t)call.Pout * call.prm.kn * 4;
+    g.ps = call.ps ? call.ps + s0 * call.Pout : nullptr;
+    g.cnt = call.cnt + s0;
+    g.fl = call.fl ? call.fl + s0 : nullptr;
+    return SNOWTRI_OK;
+}
+
+// ---- the stages of a segment.  Streaming route: candidates -> association -> fusion (-> person scores) -> k_frame_recompute on
+// the frames left behind.
+
+// The candidate pass: k_candidate_sums (and again over the first keypoint_num joints) + k_candidate_sums_exact; without one
+// (`sumless`) the constant sums and k_singular_scan.
+template <typename TIn, typename TOut>
+int stage_candidates(snowtri_ctx *ctx, const RecomputeRoute &r, RecomputeSegment<TIn, TOut> &g) {
+    const RecomputeCall<TIn, TOut> &c = g.call;
+    const int64_t Fs = g.Fs, Kc = c.Kc;
+    const SumsLaunch &SL = r.SL;
+    const size_t sum_bytes = ((size_t)Fs * Kc * 8 + 255) & ~(size_t)255;
+    int rc = g.set->sums.ensure((r.sums_kn ? 2 : 1) * sum_bytes + (size_t)Fs * 12 + 256);   // + the frames left behind (two passes) + the frames to re-do exactly
+    if (rc) return rc;
+    g.csum = (double *)g.set->sums.p;
+    g.csum_kn = r.sums_kn ? (double *)((char *)g.set->sums.p + sum_bytes) : nullptr;
+    g.slow_list = (uint32_t *)((char *)g.set->sums.p + (r.sums_kn ? 2 : 1) * sum_bytes);
+    g.exact_list = g.slow_list + Fs;
+    const int grid1 = (int)std::min<int64_t>(Fs, (int64_t)ctx->num_cus * SL.per_cu);
+    if (ctx->debug) {
+        const AssocShape ash = associate_shape(ctx->C, ctx->npairs, c.Pout, Kc);
+        fprintf(stderr, "k_candidate_sums: threads %d lds %d per_cu %d grid %d Jc %d | k_associate rounds in registers %d lds %zu\n",
+                SL.threads, SL.lds, SL.per_cu, grid1, SL.Jc, ash.rc, ash.lds);
+    }
+    if (r.sumless) {
+        // every byte 0x3f: the double 4.7e-4 in every slot -- positive, finite, kept by :80-81 for any threshold <= 0
+        HIP_TRY(hipMemsetAsync(g.csum, 0x3f, (size_t)Fs * Kc * 8, g.st));
+        if (!g.fl) return SNOWTRI_OK;
+        HIP_TRY(hipMemsetAsync(g.fl, 0, (size_t)Fs * sizeof(uint32_t), g.st));   // (the candidate pass clears the flags otherwise)
+        // ... and finds every singular pair of every listed candidate and joint; here a scan asks that one question
+        // (the flag must not depend on the route: k_singular_scan, snowtri_assoc.hpp)
+        return launch_kernel(ctx, g.st, k_singular_scan<TIn>, dim3(grid_for(Fs * (int64_t)c.J, kBlock, ctx->num_cus * 16)), dim3(kBlock), 0, false, Fs,
+                             c.J, ctx->rig(), g.kpts, g.np, g.fl);
+    }
+    with_sums_threads(SL.threads, [&](auto tt) {
+        constexpr int TT = decltype(tt)::value;
+        auto k1 = k_candidate_sums<TIn, TT>;
+        rc = launch_kernel(ctx, g.st, k1, dim3(grid1), dim3(TT), (size_t)SL.lds, false, Fs, c.Pmax, c.J, c.J, (int)Kc, ctx->rig(), g.kpts, g.np, c.prm,
+                           g.csum, g.fl, g.exact_list, g.exact_count, g.sums_ticket, SL.lds);
+        if (!rc && r.sums_kn)   // the sums over the first keypoint_num joints, on a ticket counter of their own
+            rc = launch_kernel(ctx, g.st, k1, dim3(grid1), dim3(TT), (size_t)SL.lds, false, Fs, c.Pmax, c.prm.kn, c.J, (int)Kc, ctx->rig(), g.kpts,
+                               g.np, c.prm, g.csum_kn, (uint32_t *)nullptr, (uint32_t *)nullptr, g.exact_count, g.sums_ticket + 1, SL.lds);
+    });
+    if (rc) return rc;
+    // the frames it listed (exact_count of them, known on the device only; normally none)
+    return launch_kernel(ctx, g.st, k_candidate_sums_exact<TIn>, dim3((int)std::min<int64_t>(Fs, ctx->num_cus)), dim3(kBlock), 0, false, c.Pmax, c.J,
+                         (int)Kc, ctx->rig(), g.kpts, g.np, c.prm, g.csum, g.fl, (const uint32_t *)g.exact_list,
+                         (const unsigned long long *)g.exact_count);
+}
+
+// k_associate: the persons of every frame into the descriptor lists; the frames it cannot take are listed for k_frame_recompute.
+template <typename TIn, typename TOut>
+int stage_associate(snowtri_ctx *ctx, const RecomputeRoute &r, RecomputeSegment<TIn, TOut> &g) {
+    const RecomputeCall<TIn, TOut> &c = g.call;
+    const int C = ctx->C;
+    const int64_t Fs = g.Fs, Kc = c.Kc;
+    // first launch: centres in registers where the rig's true pairs fit 4 / 16 rounds of 64 (snowtri_assoc.hpp)
+    const AssocShape ash = associate_shape(C, ctx->npairs, c.Pout, Kc);
+    auto k2 = k_associate<TIn, TOut, 0>;   // the second launch (every slot in LDS)
+    auto k2a = ash.rc == 4 ? k_associate<TIn, TOut, 4> : (ash.rc == 16 ? k_associate<TIn, TOut, 16> : k2);
+    const size_t lds2 = ash.lds;
+    // small rigs: 16 waves per CU, each striding over the frames; large rigs (a frame takes > 100 us and only a few
+    // fit a CU's LDS): one frame per workgroup, the dispatcher evens out the tail
+    const int grid2 = (int)std::min<int64_t>(Fs, lds2 > 10 * 1024 ? Fs : (int64_t)ctx->num_cus * ctx->assoc_wg_per_cu);
+    int rc = launch_kernel(ctx, g.st, k2a, dim3(grid2), dim3(64), lds2, false, Fs, c.Pmax, c.J, (int)Kc, ctx->rig(), g.kpts, g.np, c.prm, c.Pout,
+                           g.csum, g.xyzs, g.ps, g.cnt, g.fl, g.desc, g.words, g.hand_counters, g.cap, g.word_cap, g.slow_list, g.slow_count,
+                           (int)lds2, 1, (const uint32_t *)nullptr, (const unsigned long long *)nullptr, r.post_scores ? 0 : 1,
+                           (const double *)g.csum_kn);
+    if (rc) return rc;
+    // the frames whose kept candidates did not fit that LDS (slow_count of them, known on the device only; none on
+    // the reference's workloads): again with room for every slot, one wave per CU; what this launch lists is
+    // left to k_frame_recompute
+    g.final_slow_list = g.slow_list;
+    g.final_slow_count = g.slow_count;
+    const size_t lds2_full = associate_lds_bytes_full(C, ctx->npairs, c.Pout, Kc);
+    if (lds2_full <= lds2) return SNOWTRI_OK;
+    uint32_t *slow_list2 = g.exact_list + Fs;
+    const int per_cu2 = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds2_full));
+    rc = launch_kernel(ctx, g.st, k2, dim3((int)std::min<int64_t>(Fs, (int64_t)ctx->num_cus * per_cu2)), dim3(64), lds2_full, false, Fs, c.Pmax, c.J,
+                       (int)Kc, ctx->rig(), g.kpts, g.np, c.prm, c.Pout, g.csum, g.xyzs, g.ps, g.cnt, g.fl, g.desc, g.words, g.hand_counters, g.cap,
+                       g.word_cap, slow_list2, g.slow_count2, (int)lds2_full, 1, (const uint32_t *)g.slow_list,
+                       (const unsigned long long *)g.slow_count, r.post_scores ? 0 : 1, (const double *)g.csum_kn);
+    if (rc) return rc;
+    g.final_slow_list = slow_list2;
+    g.final_slow_count = g.slow_count2;
+    return SNOWTRI_OK;
+}
+
+// The streaming kernels for the descriptors the association (or a k_frame_recompute launch over Fs frames) left behind
+// (snowtri_cluster.hpp): `cnt[0]` complete-graph clusters in desc[0, cap), `cnt[1]` clusters of any other shape in desc[cap, 2 cap)
+// with their member words in `words`.  Pairwise method: k_cluster_fuse (up to 8 cameras: register-resident rays) or
+// k_cluster_fuse_wide for the complete graphs, then k_cluster_members; DLT: k_cluster_dlt for both lists.
+template <int METHOD, typename TIn, typename TOut>
+int stage_fusion(snowtri_ctx *ctx, const RecomputeRoute &r, RecomputeSegment<TIn, TOut> &g) {
+    const RecomputeCall<TIn, TOut> &c = g.call;
+    const int C = ctx->C, kn = c.prm.kn;
+    const int64_t Fs = g.Fs;
+    const int64_t passes_max = (Fs * c.Pout * (int64_t)kn + 63) / 64;
+    int rc = SNOWTRI_OK;
+    if constexpr (METHOD == 1) {
+        // both descriptor lists in one launch: an N-view DLT per (output person, joint)
+        const int gridd = (int)std::max<int64_t>(1, std::min<int64_t>((passes_max + 3) / 4, (int64_t)ctx->num_cus * kClusterDltWaves));
+        auto dlt = [&](auto cc) {
+            rc = launch_kernel(ctx, g.st, k_cluster_dlt<decltype(cc)::value, TIn, TOut>, dim3(gridd), dim3(kBlock), cluster_dlt_lds_bytes(C), false,
+                               g.desc, g.words, g.hand_counters, g.cap, ctx->rig(), g.kpts, c.prm, c.Pmax, c.J, kn, c.kmagic, c.Pout, g.xyzs);
+        };
+        if (!with_cameras<2, kClusterMaxCams>(C, dlt)) dlt(std::integral_constant<int, 0>());   // more than 8 cameras
+        return rc;
+    } else {
+        const bool narrow = with_cameras<2, kClusterMaxCams>(C, [&](auto cc) {
+            // exactly the waves that are resident at once (kClusterWaves per SIMD at this kernel's registers), each striding over
+            // the passes: with the member lists in a kernel of their own every pass costs the same, and short-lived workgroups only
+            // added their start-up (8 x 4: 334 -> 312 us).  (k_cluster_members on a second stream beside this kernel: measured, no gain.)
+            const int64_t W = std::min<int64_t>(passes_max, (int64_t)ctx->num_cus * 4 * kClusterWaves);
+            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((W + kBlock / 64 - 1) / (kBlock / 64), (int64_t)ctx->num_cus * 64));
+            rc = launch_kernel(ctx, g.st, k_cluster_fuse<decltype(cc)::value, TIn, TOut>, dim3(grid), dim3(kBlock), cluster_lds_bytes(C), false, g.desc,
+                               g.hand_counters, g.cap, ctx->rig(), g.kpts, c.prm, c.Pmax, c.J, kn, c.kmagic, c.Pout, g.xyzs, g.fl);
+        });
+        // (the hand-over from inside k_frame_recompute has no wide kernel: only a build without this camera count gets here)
+        if (!narrow && !r.stream) return SNOWTRI_ERR_BAD_ARG;
+        if (!narrow) {   // more than 8 cameras: complete graphs with their rays in LDS
+            const int64_t wpasses = (Fs * c.Pout * (int64_t)kn + 15) / 16;   // 16 items per wave pass
+            const int ppw_wide = 8;   // (many short-lived workgroups here: 6 -> 886, 24 -> 906, 400 -> 1042 us per 4 000 frames of 16 x 8)
+            const int gridw = (int)std::max<int64_t>(1, std::min<int64_t>((wpasses + 4 * ppw_wide - 1) / (4 * ppw_wide), (int64_t)ctx->num_cus * 64));
+            rc = launch_kernel(ctx, g.st, k_cluster_fuse_wide<TIn, TOut>, dim3(gridw), dim3(kBlock), cluster_wide_lds_bytes(C), false, g.desc,
+                               g.hand_counters, g.cap, ctx->rig(), g.kpts, c.prm, c.Pmax, c.J, kn, c.kmagic, c.Pout, g.xyzs, g.fl);
+        }
+        if (rc) return rc;
+        // ... then the member lists
+        const int gridm = (int)std::max<int64_t>(1, std::min<int64_t>((passes_max + 3) / 4, (int64_t)ctx->num_cus * 16));
+        return launch_kernel(ctx, g.st, k_cluster_members<TIn, TOut>, dim3(gridm), dim3(kBlock), cluster_members_lds_bytes(C, ctx->npairs), false, g.desc,
+                             g.words, g.hand_counters, g.cap, ctx->rig(), g.kpts, c.prm, c.Pmax, c.J, kn, c.kmagic, c.Pout, g.xyzs, g.fl);
+    }
+}
+
+// The persons' mean scores from the fused joints (keypoint_num < J, float64 outputs).
+template <typename TIn, typename TOut>
+int stage_person_scores(snowtri_ctx *ctx, RecomputeSegment<TIn, TOut> &g) {
+    const RecomputeCall<TIn, TOut> &c = g.call;
+    const int gridp = (int)std::max<int64_t>(1, std::min<int64_t>((g.Fs * c.Pout + 3) / 4, (int64_t)ctx->num_cus * 32));
+    return launch_kernel(ctx, g.st, k_person_scores<TOut>, dim3(gridp), dim3(kBlock), 0, false, g.Fs, c.Pout, c.prm.kn, (const TOut *)g.xyzs, g.ps,
+                         (const int32_t *)g.cnt);
+}
+
+// k_frame_recompute: over the whole segment (writing the descriptor lists where the route hands over), or -- `left_behind` -- over
+// the frames k_associate listed (slow_count of them, known on the device only): phase 3 inside the kernel.
+template <int METHOD, typename TIn, typename TOut>
+int stage_recompute(snowtri_ctx *ctx, RecomputeSegment<TIn, TOut> &g, bool left_behind) {
+    const RecomputeCall<TIn, TOut> &c = g.call;
+    const int64_t grid = left_behind ? std::max<int64_t>(1, std::min<int64_t>(g.grid, ctx->num_cus)) : g.grid;
+    return launch_kernel(ctx, g.st, k_frame_recompute<METHOD, TIn, TOut>, dim3((int)grid), dim3(kBlock), c.lds, false, g.Fs, c.Pmax, c.J, (int)c.Kc,
+                         ctx->rig(), g.kpts, g.np, c.prm, c.Pout, g.xyzs, g.ps, g.cnt, g.fl, (char *)g.set->work.p, c.per_block, g.next_frame,
+                         (int)c.lds, left_behind ? (ClusterDesc *)nullptr : g.desc, left_behind ? (uint32_t *)nullptr : g.words, g.hand_counters,
+                         left_behind ? 0u : g.cap, left_behind ? 0u : g.word_cap, left_behind ? g.final_slow_list : (const uint32_t *)nullptr,
+                         left_behind ? g.final_slow_count : (const unsigned long long *)nullptr);
+}
+
+template <int METHOD, typename TIn, typename TOut>
+int launch_frame_recompute(snowtri_ctx *ctx, hipStream_t st_call, int64_t F, int Pmax, int J, const TIn *d_kpts,
+                           const int32_t *d_np, const Params &prm, int Pout, TOut *d_xyzs, TOut *d_ps,
+                           int32_t *d_cnt, uint32_t *d_fl) {
+    const int64_t Kc = snowtri_num_candidate_slots(ctx->C, Pmax);
+    const int C = ctx->C;
+    const unsigned long long kn1 = (unsigned long long)std::max(1, prm.kn);
+    // three workgroups per CU share the 160 KB of LDS (snowtri_general.hpp: the arena behind the tables is reused
+    // phase by phase)
+    RecomputeCall<TIn, TOut> call{Pmax, J, Pout, Kc, prm, recompute_launch_lds(C, ctx->npairs), recompute_scratch_bytes(Kc, C * Pmax, prm.kn), 0,
+                                  (((unsigned long long)1 << 40) + kn1 - 1) / kn1, d_kpts, d_np, d_xyzs, d_ps, d_cnt, d_fl};
+    int rc = recompute_per_cu<METHOD, TIn, TOut>(ctx, call.lds, C * Pmax, Kc, &call.per_cu);
+    if (rc) return rc;
+    const RecomputeRoute r = recompute_route(ctx, METHOD, sizeof(TIn), sizeof(TOut), F, Pmax, J, prm, Pout);
+    StreamSet *const set_call = ctx->cur;
+    if (r.split) {
         if (ctx->ensure_set(1, true, st_call)) {
             g_last_error = "creating the internal stream of the multi-person split failed";
             return SNOWTRI_ERR_HIP;
@@ -2805,246 +3085,34 @@ int launch_frame_recompute(snowtri_ctx *ctx, hipStream_t st_call, int64_t F, int
             if (armed && hipEventRecord(ctx->sets[1].done, ctx->sets[1].stream) == hipSuccess)
                 (void)hipStreamWaitEvent(caller, ctx->sets[1].done, 0);
         }
-    } split_join{ctx, st_call, set_call, split};
-    const uint32_t *final_slow_list = nullptr;                 // what the streaming association leaves to k_frame_recompute
-    const unsigned long long *final_slow_count = nullptr;
-    {   // the kernels of this route, in launch order (rebuilt only when the route changes)
-        const long long key = ((long long)C << 8) | (METHOD << 7) | ((int)sizeof(TIn) << 3) | ((int)sizeof(TOut) >> 2 << 2) |
-                              (stream ? 2 : 0) | (handover ? 1 : 0) | ((long long)SL.threads << 16) | ((long long)(sumless ? 1 : 0) << 32) |
-                              ((long long)Pmax << 34);
-        if (key != ctx->names_key) {
-            const std::string tin = type_name<TIn>(), tout = type_name<TOut>();
-            const std::string rec = "k_frame_recompute<" + std::to_string(METHOD) + "," + tin + "," + tout + ">";
-            const std::string fuse = C <= kClusterMaxCams ? "k_cluster_fuse<" + std::to_string(C) + "," + tin + "> + k_cluster_members<" + tin + ">"
-                                                           : "k_cluster_fuse_wide<" + tin + "> + k_cluster_members<" + tin + ">";
-            if (stream && METHOD == 1)
-                ctx->names_buf = "k_candidate_sums<" + tin + "," + std::to_string(SL.threads) + "> + k_candidate_sums_exact<" + tin +
-                                 "> + k_associate<" + tin + "> + k_cluster_dlt<" + std::to_string(C <= kClusterMaxCams ? C : 0) + "," + tin + "," + tout + "> + k_person_scores<" + tout + "> + " + rec + " (frames left behind)";
-            else if (stream && sumless)
-                ctx->names_buf = "k_singular_scan<" + tin + "> + k_associate<" + tin + "> + " + fuse + " + k_person_scores<" + tout + "> + " + rec + " (frames left behind)";
-            else if (stream)
-                ctx->names_buf = "k_candidate_sums<" + tin + "," + std::to_string(SL.threads) + "> + k_candidate_sums_exact<" + tin +
-                                 "> + k_associate<" + tin + "> + " + fuse + " + " + rec + " (frames left behind)";
-            else if (handover)
-                ctx->names_buf = rec + " + " + fuse;
-            else
-                ctx->names_buf = rec;
-            ctx->names_key = key;
-        }
-        ctx->last_kernels = ctx->names_buf.c_str();
-    }
-    const unsigned long long kn1 = (unsigned long long)std::max(1, prm.kn), kmagic = (((unsigned long long)1 << 40) + kn1 - 1) / kn1;   // item / keypoint_num
+    } split_join{ctx, st_call, set_call, r.split};
+    recompute_route_names<METHOD, TIn, TOut>(ctx, r);
+    RecomputeSegment<TIn, TOut> g{call};
     int seg_index = 0;
-    for (int64_t s0 = 0; s0 < F; s0 += seg, seg_index++) {
-        const int64_t Fs = std::min<int64_t>(seg, F - s0);
-        StreamSet &S = split && (seg_index & 1) ? ctx->sets[1] : *set_call;
-        const hipStream_t st = split && (seg_index & 1) ? S.stream : st_call;
-        ctx->cur = &S;
-        ctx->last_set = &S;
-        unsigned long long *next_frame = S.d_counters + 2, *hand_counters = S.d_counters + kHandCountersAt, *slow_count = S.d_counters + 6,
-                           *exact_count = S.d_counters + 7, *slow_count2 = S.d_counters + 8, *sums_ticket = S.d_counters + 9;
-        int64_t grid = std::min<int64_t>(Fs, (int64_t)ctx->num_cus * std::max(1, per_cu));
-        grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kMaxScratchBytes / per_block)));
-        int rc = ctx->cur->work.ensure(per_block * (size_t)grid);
-        if (rc) return rc;
-        uint32_t cap = 0, word_cap = 0;
-        ClusterDesc *desc = nullptr;
-        uint32_t *words = nullptr;
-        if (stream || handover) {
-            ctx->last_handover = true;
-            cap = (uint32_t)(Fs * Pout);
-            word_cap = (uint32_t)(Fs * Kc);
-            rc = ctx->cur->desc.ensure((size_t)2 * cap * sizeof(ClusterDesc) + (size_t)word_cap * 4);
-            if (rc) return rc;
-            desc = (ClusterDesc *)ctx->cur->desc.p;
-            words = (uint32_t *)(desc + (size_t)2 * cap);
+    for (int64_t s0 = 0; s0 < F; s0 += r.seg, seg_index++) {
+        const bool internal = r.split && (seg_index & 1);
+        StreamSet &S = internal ? ctx->sets[1] : *set_call;
+        if ((rc = open_segment(ctx, r, S, internal ? S.stream : st_call, s0, std::min<int64_t>(r.seg, F - s0), g))) return rc;
+        if (r.stream) {
+            if ((rc = stage_candidates(ctx, r, g))) return rc;
+            if ((rc = stage_associate(ctx, r, g))) return rc;
+        } else if ((rc = stage_recompute<METHOD>(ctx, g, false))) {
+            return rc;
         }
-        HIP_TRY(hipMemsetAsync(next_frame, 0, (kCounterWords - 2) * sizeof(unsigned long long), st));   // next_frame, slow / exact / slow (second pass) frames, the frame tickets of k_candidate_sums, the hand-over list counters
-        const TIn *kp_seg = d_kpts + s0 * (int64_t)R * J * 3;
-        const int32_t *np_seg = d_np ? d_np + s0 * C : nullptr;
-        TOut *xyz_seg = d_xyzs + s0 * (int64_t)Pout * prm.kn * 4;
-        TOut *ps_seg = d_ps ? d_ps + s0 * Pout : nullptr;
-        uint32_t *fl_seg = d_fl ? d_fl + s0 : nullptr;
-        {
-            if (stream) {
-                // ---- k_candidate_sums -> k_associate -> k_cluster_fuse (DLT: k_cluster_dlt), then k_frame_recompute on the frames left behind
-                const size_t sum_bytes = ((size_t)Fs * Kc * 8 + 255) & ~(size_t)255;
-                rc = ctx->cur->sums.ensure((sums_kn ? 2 : 1) * sum_bytes + (size_t)Fs * 12 + 256);   // + the frames left behind (two passes) + the frames to re-do exactly
-                if (rc) return rc;
-                double *csum = (double *)ctx->cur->sums.p;
-                double *csum_kn = sums_kn ? (double *)((char *)ctx->cur->sums.p + sum_bytes) : nullptr;
-                uint32_t *slow_list = (uint32_t *)((char *)ctx->cur->sums.p + (sums_kn ? 2 : 1) * sum_bytes);
-                // first launch: centres in registers where the rig's true pairs fit 4 / 16 rounds of 64 (snowtri_assoc.hpp)
-                const AssocShape ash = associate_shape(C, ctx->npairs, Pout, Kc);
-                auto k2 = k_associate<TIn, TOut, 0>;   // the second launch (every slot in LDS)
-                auto k2a = ash.rc == 4 ? k_associate<TIn, TOut, 4> : (ash.rc == 16 ? k_associate<TIn, TOut, 16> : k2);
-                const size_t lds2 = ash.lds;
-                if (lds2 > 48 * 1024 && ctx->raise_lds((const void *)k2a, (int)lds2)) return SNOWTRI_ERR_HIP;
-                const int grid1 = (int)std::min<int64_t>(Fs, (int64_t)ctx->num_cus * SL.per_cu);
-                if (ctx->debug)
-                    fprintf(stderr, "k_candidate_sums: threads %d lds %d per_cu %d grid %d Jc %d | k_associate rounds in registers %d lds %zu\n",
-                            SL.threads, SL.lds, SL.per_cu, grid1, SL.Jc, ash.rc, lds2);
-                uint32_t *exact_list = slow_list + Fs;
-#define SNOWTRI_SUMS(TT)                                                                                                             \
-    {                                                                                                                                \
-        auto k1 = k_candidate_sums<TIn, TT>;                                                                                         \
-        if (SL.lds > 48 * 1024 && ctx->raise_lds((const void *)k1, SL.lds)) return SNOWTRI_ERR_HIP;                                 \
-        hipLaunchKernelGGL(k1, dim3(grid1), dim3(TT), SL.lds, st, Fs, Pmax, J, J, (int)Kc, ctx->rig(), kp_seg, np_seg, prm, csum, fl_seg, \
-                           exact_list, exact_count, sums_ticket, SL.lds);                                                            \
-        if (sums_kn) {   /* the sums over the first keypoint_num joints, on a ticket counter of their own */                        \
-            hipLaunchKernelGGL(k1, dim3(grid1), dim3(TT), SL.lds, st, Fs, Pmax, prm.kn, J, (int)Kc, ctx->rig(), kp_seg, np_seg, prm,  \
-                               csum_kn, (uint32_t *)nullptr, (uint32_t *)nullptr, exact_count, sums_ticket + 1, SL.lds);            \
-        }                                                                                                                            \
-    }
-                if (sumless) {
-                    // every byte 0x3f: the double 4.7e-4 in every slot -- positive, finite, kept by :80-81 for any threshold <= 0
-                    HIP_TRY(hipMemsetAsync(csum, 0x3f, (size_t)Fs * Kc * 8, st));
-                    if (fl_seg) {
-                        HIP_TRY(hipMemsetAsync(fl_seg, 0, (size_t)Fs * sizeof(uint32_t), st));   // (the candidate pass clears the flags otherwise)
-                        // ... and finds every singular pair of every listed candidate and joint; here a scan asks that one question
-                        // (the flag must not depend on the route: k_singular_scan, snowtri_assoc.hpp)
-                        hipLaunchKernelGGL((k_singular_scan<TIn>), dim3(grid_for(Fs * (int64_t)J, kBlock, ctx->num_cus * 16)), dim3(kBlock), 0, st, Fs, J,
-                                           ctx->rig(), kp_seg, np_seg, fl_seg);
-                        HIP_TRY(hipGetLastError());
-                    }
-                } else {
-                    if (SL.threads == 256) SNOWTRI_SUMS(256) else if (SL.threads == 512) SNOWTRI_SUMS(512) else SNOWTRI_SUMS(1024)
-                    HIP_TRY(hipGetLastError());
-                    // the frames it listed (exact_count of them, known on the device only; normally none)
-                    hipLaunchKernelGGL((k_candidate_sums_exact<TIn>), dim3((int)std::min<int64_t>(Fs, ctx->num_cus)), dim3(kBlock), 0, st, Pmax, J,
-                                       (int)Kc, ctx->rig(), kp_seg, np_seg, prm, csum, fl_seg, (const uint32_t *)exact_list,
-                                       (const unsigned long long *)exact_count);
-                    HIP_TRY(hipGetLastError());
-                }
-#undef SNOWTRI_SUMS
-                // small rigs: 16 waves per CU, each striding over the frames; large rigs (a frame takes > 100 us and only a few
-                // fit a CU's LDS): one frame per workgroup, the dispatcher evens out the tail
-                const int grid2 = (int)std::min<int64_t>(Fs, lds2 > 10 * 1024 ? Fs : (int64_t)ctx->num_cus * ctx->assoc_wg_per_cu);
-                hipLaunchKernelGGL(k2a, dim3(grid2), dim3(64), lds2, st, Fs, Pmax, J, (int)Kc, ctx->rig(), kp_seg, np_seg, prm, Pout, csum,
-                                   xyz_seg, ps_seg, d_cnt + s0, fl_seg, desc, words, hand_counters, cap, word_cap, slow_list,
-                                   slow_count, (int)lds2, 1, (const uint32_t *)nullptr, (const unsigned long long *)nullptr, post_scores ? 0 : 1,
-                                   (const double *)csum_kn);
-                HIP_TRY(hipGetLastError());
-                // the frames whose kept candidates did not fit that LDS (slow_count of them, known on the device only; none on
-                // the reference's workloads): again with room for every slot, one wave per CU; what this launch lists is
-                // left to k_frame_recompute
-                final_slow_list = slow_list;
-                final_slow_count = slow_count;
-                const size_t lds2_full = associate_lds_bytes_full(C, ctx->npairs, Pout, Kc);
-                if (lds2_full > lds2) {
-                    if (lds2_full > 48 * 1024 && ctx->raise_lds((const void *)k2, (int)lds2_full)) return SNOWTRI_ERR_HIP;
-                    uint32_t *slow_list2 = exact_list + Fs;
-                    const int per_cu2 = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds2_full));
-                    hipLaunchKernelGGL(k2, dim3((int)std::min<int64_t>(Fs, (int64_t)ctx->num_cus * per_cu2)), dim3(64), lds2_full, st, Fs, Pmax, J,
-                                       (int)Kc, ctx->rig(), kp_seg, np_seg, prm, Pout, csum, xyz_seg, ps_seg, d_cnt + s0, fl_seg,
-                                       desc, words, hand_counters, cap, word_cap, slow_list2, slow_count2, (int)lds2_full, 1,
-                                       (const uint32_t *)slow_list, (const unsigned long long *)slow_count, post_scores ? 0 : 1,
-                                       (const double *)csum_kn);
-                    HIP_TRY(hipGetLastError());
-                    final_slow_list = slow_list2;
-                    final_slow_count = slow_count2;
-                }
-            }
-        }
-        if (!stream) {
-            hipLaunchKernelGGL(kern, dim3((int)grid), dim3(kBlock), lds, st, Fs, Pmax, J, (int)Kc, ctx->rig(), kp_seg, np_seg, prm, Pout,
-                               xyz_seg, ps_seg, d_cnt + s0, fl_seg, (char *)ctx->cur->work.p, per_block, next_frame, (int)lds, desc, words,
-                               hand_counters, cap, word_cap, (const uint32_t *)nullptr, (const unsigned long long *)nullptr);
-            HIP_TRY(hipGetLastError());
-        }
-        if constexpr (METHOD == 1) {
-            if (stream) {
-                // both descriptor lists in one launch: an N-view DLT per (output person, joint)
-                const int64_t passes_max = (Fs * Pout * (int64_t)prm.kn + 63) / 64;
-                const int gridd = (int)std::max<int64_t>(1, std::min<int64_t>((passes_max + 3) / 4, (int64_t)ctx->num_cus * kClusterDltWaves));
-                switch (C) {
-#define SNOWTRI_CASE(CC)                                                                                                                \
-    case CC:                                                                                                                            \
-        hipLaunchKernelGGL((k_cluster_dlt<CC, TIn, TOut>), dim3(gridd), dim3(kBlock), cluster_dlt_lds_bytes(C), st, desc, words, hand_counters, cap, \
-                           ctx->rig(), kp_seg, prm, Pmax, J, prm.kn, kmagic, Pout, xyz_seg);                                            \
-        break;
-#ifndef SNOWTRI_DEV_MIN
-                    SNOWTRI_CASE(2)
-                    SNOWTRI_CASE(3)
-                    SNOWTRI_CASE(5)
-                    SNOWTRI_CASE(6)
-                    SNOWTRI_CASE(7)
-#endif
-                    SNOWTRI_CASE(4)
-                    SNOWTRI_CASE(8)
-                    default:   // more than 8 cameras
-                        hipLaunchKernelGGL((k_cluster_dlt<0, TIn, TOut>), dim3(gridd), dim3(kBlock), cluster_dlt_lds_bytes(C), st, desc, words, hand_counters, cap,
-                                           ctx->rig(), kp_seg, prm, Pmax, J, prm.kn, kmagic, Pout, xyz_seg);
-#undef SNOWTRI_CASE
-                }
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        {
-            if constexpr (METHOD == 0) if (stream || handover) {
-                switch (C) {
-#define SNOWTRI_CASE(CC)                                                                                                       \
-    case CC:                                                                                                                   \
-        rc = launch_cluster_fuse<CC, TIn, TOut>(ctx, st, Fs, Pmax, J, kp_seg, prm, Pout, xyz_seg, fl_seg, desc, words,       \
-                                                hand_counters, cap);                                                           \
-        break;
-#ifndef SNOWTRI_DEV_MIN
-                    SNOWTRI_CASE(2)
-                    SNOWTRI_CASE(3)
-                    SNOWTRI_CASE(5)
-                    SNOWTRI_CASE(6)
-                    SNOWTRI_CASE(7)
-#endif
-                    SNOWTRI_CASE(4)
-                    SNOWTRI_CASE(8)
-#undef SNOWTRI_CASE
-                    default: {   // more than 8 cameras: complete graphs with their rays in LDS, then the member lists
-                        const int64_t passes_max = (Fs * Pout * (int64_t)prm.kn + 63) / 64;
-                        const int gridm = (int)std::max<int64_t>(1, std::min<int64_t>((passes_max + 3) / 4, (int64_t)ctx->num_cus * 16));
-                        if (stream) {
-                            auto kw = k_cluster_fuse_wide<TIn, TOut>;
-                            const size_t ldsw = cluster_wide_lds_bytes(C);
-                            if (ldsw > 48 * 1024 && ctx->raise_lds((const void *)kw, (int)ldsw)) return SNOWTRI_ERR_HIP;
-                            const int64_t wpasses = (Fs * Pout * (int64_t)prm.kn + 15) / 16;   // 16 items per wave pass
-                            const int ppw_wide = 8;   // (many short-lived workgroups here: 6 -> 886, 24 -> 906, 400 -> 1042 us per 4 000 frames of 16 x 8)
-                            const int gridw = (int)std::max<int64_t>(1, std::min<int64_t>((wpasses + 4 * ppw_wide - 1) / (4 * ppw_wide),
-                                                                                         (int64_t)ctx->num_cus * 64));
-                            hipLaunchKernelGGL(kw, dim3(gridw), dim3(kBlock), ldsw, st, desc, hand_counters, cap, ctx->rig(), kp_seg, prm, Pmax, J,
-                                               prm.kn, kmagic, Pout, xyz_seg, fl_seg);
-                            HIP_TRY(hipGetLastError());
-                        }
-                        hipLaunchKernelGGL((k_cluster_members<TIn, TOut>), dim3(gridm), dim3(kBlock), cluster_members_lds_bytes(C, ctx->npairs), st,
-                                           desc, words, hand_counters, cap, ctx->rig(), kp_seg, prm, Pmax, J, prm.kn, kmagic, Pout, xyz_seg, fl_seg);
-                        rc = hipGetLastError() == hipSuccess ? SNOWTRI_OK : SNOWTRI_ERR_HIP;
-                    }
-                }
-                if (rc) return rc;
-            }
-            if (stream && post_scores && ps_seg) {
-                // the persons' mean scores from the fused joints (keypoint_num < J, float64 outputs)
-                const int gridp = (int)std::max<int64_t>(1, std::min<int64_t>((Fs * Pout + 3) / 4, (int64_t)ctx->num_cus * 32));
-                hipLaunchKernelGGL((k_person_scores<TOut>), dim3(gridp), dim3(kBlock), 0, st, Fs, Pout, prm.kn, (const TOut *)xyz_seg, ps_seg,
-                                   (const int32_t *)(d_cnt + s0));
-                HIP_TRY(hipGetLastError());
-            }
-            if (stream) {
-                // the frames k_associate listed (slow_count of them, known on the device only): phase 3 inside the kernel
-                const int gridr = (int)std::max<int64_t>(1, std::min<int64_t>(grid, ctx->num_cus));
-                hipLaunchKernelGGL(kern, dim3(gridr), dim3(kBlock), lds, st, Fs, Pmax, J, (int)Kc, ctx->rig(), kp_seg, np_seg, prm, Pout,
-                                   xyz_seg, ps_seg, d_cnt + s0, fl_seg, (char *)ctx->cur->work.p, per_block, next_frame, (int)lds,
-                                   (ClusterDesc *)nullptr, (uint32_t *)nullptr, hand_counters, 0u, 0u,
-                                   final_slow_list, final_slow_count);
-                HIP_TRY(hipGetLastError());
-            }
-        }
+        if (r.stream || r.handover)
+            if ((rc = stage_fusion<METHOD>(ctx, r, g))) return rc;
+        if (r.stream && r.post_scores && g.ps)
+            if ((rc = stage_person_scores(ctx, g))) return rc;
+        if (r.stream)
+            if ((rc = stage_recompute<METHOD>(ctx, g, true))) return rc;
     }
     ctx->cur = set_call;
-    if (split) {   // the caller's stream continues behind the internal one
+    if (r.split) {   // the caller's stream continues behind the internal one
         split_join.armed = false;
         HIP_TRY(hipEventRecord(ctx->sets[1].done, ctx->sets[1].stream));
         HIP_TRY(hipStreamWaitEvent(st_call, ctx->sets[1].done, 0));
     }
-    ctx->last_stream = stream;
+    ctx->last_stream = r.stream;
     return SNOWTRI_OK;
 }
 
@@ -3072,24 +3140,12 @@ int launch_dlt_robust(snowtri_ctx *ctx, hipStream_t st, int64_t F, int J, const 
         g_last_error = "SNOWTRI_DLT_ROBUST: keypoint_num too large for the LDS stash of one frame (or more than 2^31 tiles)";
         return SNOWTRI_ERR_BAD_ARG;
     }
-    auto kern = k_dlt_robust<C, TIn, TOut>;
-    if (lds > 48 * 1024 && ctx->raise_lds((const void *)kern, (int)lds)) {
-        g_last_error = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
-        return SNOWTRI_ERR_HIP;
-    }
     const double tau2 = rb.threshold_px * rb.threshold_px;
-    if (ctx->timing && ctx->timing_attach) {   // one kernel: the ring's event pair rides on its dispatch (see launch_fused_lean)
-        const int64_t slot = ctx->ev_count % kTimingRing;
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, ctx->ev_ring[2 * slot], ctx->ev_ring[2 * slot + 1], 0,
-                              F, J, (int)T, ctx->rig(), d_kpts, d_np, prm, tau2, (int)rb.max_drops, Pout, d_xyzs, d_ps, d_cnt, d_fl, rb.views,
-                              (TOut *)rb.resid);
-        ctx->ev_attached = true;
-    } else {
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), lds, st, F, J, (int)T, ctx->rig(), d_kpts, d_np, prm, tau2,
-                           (int)rb.max_drops, Pout, d_xyzs, d_ps, d_cnt, d_fl, rb.views, (TOut *)rb.resid);
-    }
-    HIP_TRY(hipGetLastError());
-    static const std::string name = std::string("k_dlt_robust<") + std::to_string(C) + "," + type_name<TIn>() + "," + type_name<TOut>() + ">";
+    // one kernel: the ring's event pair rides on its dispatch
+    int rc = launch_kernel(ctx, st, k_dlt_robust<C, TIn, TOut>, dim3((unsigned)tiles), dim3(kBlock), lds, true, F, J, (int)T, ctx->rig(), d_kpts, d_np,
+                           prm, tau2, (int)rb.max_drops, Pout, d_xyzs, d_ps, d_cnt, d_fl, rb.views, (TOut *)rb.resid);
+    if (rc) return rc;
+    static const std::string name = kernel_name("k_dlt_robust", {std::to_string(C), type_name<TIn>(), type_name<TOut>()});
     ctx->last_kernels = name.c_str();
     return SNOWTRI_OK;
 }
@@ -3111,8 +3167,9 @@ int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J,
     // Newton-refined branch; up to four cameras they stay on k_fused_single<C,0,TIn,double>)
     // (lean_item -- float32 outputs up to five cameras -- measures lengths in units of distance_threshold: a threshold outside
     // lean_units_ok, i.e. not in [2^-64, 2^64] m or NaN, takes the route below as if there were no lean kernel; the rolled item keeps metres)
-    const bool lean_item_shape = std::is_same<TOut, float>::value && C <= 5;
-    const bool lean = method != SNOWTRI_DLT && fast && (std::is_same<TOut, float>::value || C >= 5) && J == kLeanJ && prm.kn == kLeanJ &&
+    constexpr bool out_f32 = std::is_same<TOut, float>::value;
+    const bool lean_item_shape = out_f32 && C <= 5;
+    const bool lean = method != SNOWTRI_DLT && fast && (out_f32 || C >= 5) && J == kLeanJ && prm.kn == kLeanJ &&
                       Pout == 1 && ctx->lean_mode != 0 && (!lean_item_shape || lean_units_ok(prm.dthr));
     // Five cameras and more on any other shape (float64 outputs, keypoint_num < J, other skeletons, several slots): the
     // unrolled pairwise_item of k_fused_single does not fit the register file there (10-28 pairs: 41-1 075 spilled VGPRs, round-4
@@ -3130,26 +3187,12 @@ int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J,
         HIP_TRY(hipEventRecord(ctx->ev[0], st));
         HIP_TRY(hipEventRecord(ctx->ev_ring[2 * ring_slot], st));
     }
-    int rc;
+    int rc = SNOWTRI_ERR_BAD_ARG;   // (what a camera count outside a route's instantiations gets)
     if (method == SNOWTRI_DLT_ROBUST) {
         // one detection per camera, two to eight cameras (checked by the entry point)
-        switch (C) {
-#define SNOWTRI_CASE(CC)                                                                                                          \
-    case CC:                                                                                                                      \
-        rc = launch_dlt_robust<CC, TIn, TOut>(ctx, st, F, J, d_kpts, d_np, prm, rb, Pout, d_xyzs, d_ps, d_cnt, d_fl);             \
-        break;
-#ifndef SNOWTRI_DEV_MIN
-            SNOWTRI_CASE(2)
-            SNOWTRI_CASE(3)
-            SNOWTRI_CASE(5)
-            SNOWTRI_CASE(6)
-            SNOWTRI_CASE(7)
-            SNOWTRI_CASE(8)
-#endif
-            SNOWTRI_CASE(4)
-#undef SNOWTRI_CASE
-            default: rc = SNOWTRI_ERR_BAD_ARG;
-        }
+        with_cameras<2, kRobustMaxCams>(C, [&](auto cc) {
+            rc = launch_dlt_robust<decltype(cc)::value, TIn, TOut>(ctx, st, F, J, d_kpts, d_np, prm, rb, Pout, d_xyzs, d_ps, d_cnt, d_fl);
+        });
     } else if (method == SNOWTRI_DLT && (Pmax > 1 || C > 8)) {
         // several detections per camera: the reference's association (phases 1-2), then DLT per cluster
         if (prm.kn > kRecomputeMaxKn || !recompute_shape_ok(C, Pmax, J, ctx->npairs, (int)sizeof(TIn))) {
@@ -3161,72 +3204,19 @@ int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J,
         rc = launch_frame_recompute<1, TIn, TOut>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl);
     } else if (method == SNOWTRI_DLT) {
         // one detection per camera: no association needed.  The Wholebody skeleton with every joint asked for and one slot: k_dlt_coop
-        const bool dlt_lean = dlt_coop;
-        switch (C) {
-#define SNOWTRI_CASE(CC)                                                                                      \
-    case CC:                                                                                                  \
-        rc = dlt_lean ? launch_dlt_coop<CC, TIn, TOut>(ctx, st, F, d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl)  \
-                      : launch_fused_single<CC, 1, TIn, TOut>(ctx, st, F, J, d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl); \
-        break;
-#ifndef SNOWTRI_DEV_MIN
-            SNOWTRI_CASE(2)
-            SNOWTRI_CASE(3)
-            SNOWTRI_CASE(5)
-            SNOWTRI_CASE(6)
-            SNOWTRI_CASE(7)
-            SNOWTRI_CASE(8)
-#endif
-            SNOWTRI_CASE(4)
-#undef SNOWTRI_CASE
-            default: rc = SNOWTRI_ERR_BAD_ARG;
-        }
+        with_cameras<2, 8>(C, [&](auto cc) {
+            constexpr int CC = decltype(cc)::value;
+            rc = dlt_coop ? launch_dlt_coop<CC, TIn, TOut>(ctx, st, F, d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl)
+                          : launch_fused_single<CC, 1, TIn, TOut>(ctx, st, F, J, d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl);
+        });
     } else if (lean) {
-        if constexpr (std::is_same<TOut, float>::value) {
-            switch (C) {
-#define SNOWTRI_CASE(CC)                                                                                          \
-    case CC:                                                                                                      \
-        rc = launch_fused_lean<CC, TIn>(ctx, st, F, d_kpts, d_np, prm, (float *)xyzs, (float *)ps, d_cnt, d_fl); \
-        break;
-#ifndef SNOWTRI_DEV_MIN
-                SNOWTRI_CASE(3)
-                SNOWTRI_CASE(5)
-                SNOWTRI_CASE(6)
-                SNOWTRI_CASE(7)
-                SNOWTRI_CASE(8)
-#endif
-                SNOWTRI_CASE(4)
-#undef SNOWTRI_CASE
-                default: rc = SNOWTRI_ERR_BAD_ARG;
-            }
-        } else {
-            switch (C) {
-#define SNOWTRI_CASE(CC)                                                                                          \
-    case CC:                                                                                                      \
-        rc = launch_fused_lean<CC, TIn, double>(ctx, st, F, d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);       \
-        break;
-#ifndef SNOWTRI_DEV_MIN
-                SNOWTRI_CASE(5)
-                SNOWTRI_CASE(6)
-                SNOWTRI_CASE(7)
-                SNOWTRI_CASE(8)
-#endif
-#undef SNOWTRI_CASE
-                default: rc = SNOWTRI_ERR_BAD_ARG;
-            }
-        }
+        with_cameras<out_f32 ? 3 : 5, 8>(C, [&](auto cc) {
+            rc = launch_fused_lean<decltype(cc)::value, TIn, TOut>(ctx, st, F, d_kpts, d_np, prm, d_xyzs, d_ps, d_cnt, d_fl);
+        });
     } else if (single_small) {
-        switch (C) {
-#define SNOWTRI_CASE(CC)                                                                                   \
-    case CC:                                                                                               \
-        rc = launch_fused_single<CC, 0, TIn, TOut>(ctx, st, F, J, d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl); \
-        break;
-#ifndef SNOWTRI_DEV_MIN
-            SNOWTRI_CASE(3)
-#endif
-            SNOWTRI_CASE(4)
-#undef SNOWTRI_CASE
-            default: rc = SNOWTRI_ERR_BAD_ARG;
-        }
+        with_cameras<3, kFusedSingleMaxCams>(C, [&](auto cc) {
+            rc = launch_fused_single<decltype(cc)::value, 0, TIn, TOut>(ctx, st, F, J, d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl);
+        });
     } else if (prm.kn <= kRecomputeMaxKn && recompute_shape_ok(C, Pmax, J, ctx->npairs, (int)sizeof(TIn)) &&
                ctx->general_mode != 1) {
         rc = launch_frame_recompute<0, TIn, TOut>(ctx, st, F, Pmax, J, d_kpts, d_np, prm, Pout, d_xyzs, d_ps, d_cnt, d_fl);
@@ -3249,57 +3239,6 @@ int fused_dispatch(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J,
     return SNOWTRI_OK;
 }
 
-}  // namespace
-
-extern "C" int snowtri_triangulate_condense(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J,
-                                            const void *kpts, int in_dtype, const int32_t *n_persons,
-                                            const snowtri_params *params, int method, int32_t Pout_max,
-                                            void *out_xyzs, void *out_pscore, int out_dtype,
-                                            int32_t *out_count, uint32_t *out_flags, int memspace,
-                                            void *stream) {
-    return snowtri_triangulate_condense_ex(ctx, F, Pmax, J, kpts, in_dtype, n_persons, params, method, Pout_max, out_xyzs, out_pscore,
-                                           out_dtype, out_count, out_flags, memspace, stream, 0u);
-}
-
-namespace {
-int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
-               const snowtri_params *params, int method, int32_t Pout_max, void *out_xyzs, void *out_pscore, int out_dtype,
-               int32_t *out_count, uint32_t *out_flags, int memspace, void *stream, uint32_t call_flags, const RobustCall *explicit_rb);
-}
-
-extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J,
-                                               const void *kpts, int in_dtype, const int32_t *n_persons,
-                                               const snowtri_params *params, int method, int32_t Pout_max,
-                                               void *out_xyzs, void *out_pscore, int out_dtype,
-                                               int32_t *out_count, uint32_t *out_flags, int memspace,
-                                               void *stream, uint32_t call_flags) {
-    return fused_call(ctx, F, Pmax, J, kpts, in_dtype, n_persons, params, method, Pout_max, out_xyzs, out_pscore, out_dtype, out_count,
-                      out_flags, memspace, stream, call_flags, nullptr);
-}
-
-extern "C" int snowtri_triangulate_robust(snowtri_ctx *ctx, int64_t F, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
-                                          const snowtri_params *params, double reproj_threshold_px, int32_t max_drops, int32_t Pout_max,
-                                          void *out_xyzs, void *out_pscore, int out_dtype, int32_t *out_count, uint32_t *out_flags,
-                                          uint32_t *out_views, void *out_resid, int memspace, void *stream) {
-    if (!ctx) return SNOWTRI_ERR_BAD_ARG;
-    if (!(reproj_threshold_px >= 0.0)) {
-        g_last_error = "reproj_threshold_px must be >= 0 (+inf allowed), not negative or NaN";
-        return SNOWTRI_ERR_BAD_ARG;
-    }
-    if (max_drops < 0 || max_drops > kRobustMaxDrops) {
-        g_last_error = "max_drops must be in [0, 6]";
-        return SNOWTRI_ERR_BAD_ARG;
-    }
-    RobustCall rb;
-    rb.threshold_px = reproj_threshold_px;
-    rb.max_drops = max_drops;
-    rb.views = out_views;
-    rb.resid = out_resid;
-    return fused_call(ctx, F, 1, J, kpts, in_dtype, n_persons, params, SNOWTRI_DLT_ROBUST, Pout_max, out_xyzs, out_pscore, out_dtype,
-                      out_count, out_flags, memspace, stream, 0u, &rb);
-}
-
-namespace {
 // The fused call.  explicit_rb: snowtri_triangulate_robust (its own settings and diagnostics; always on the caller's stream);
 // nullptr: snowtri_triangulate_condense[_ex], where method = SNOWTRI_DLT_ROBUST takes the context's settings and no diagnostics.
 int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
@@ -3472,4 +3411,48 @@ int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void 
     }
     return SNOWTRI_OK;
 }
+
 }  // namespace
+
+extern "C" int snowtri_triangulate_condense(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J,
+                                            const void *kpts, int in_dtype, const int32_t *n_persons,
+                                            const snowtri_params *params, int method, int32_t Pout_max,
+                                            void *out_xyzs, void *out_pscore, int out_dtype,
+                                            int32_t *out_count, uint32_t *out_flags, int memspace,
+                                            void *stream) {
+    return snowtri_triangulate_condense_ex(ctx, F, Pmax, J, kpts, in_dtype, n_persons, params, method, Pout_max, out_xyzs, out_pscore,
+                                           out_dtype, out_count, out_flags, memspace, stream, 0u);
+}
+
+extern "C" int snowtri_triangulate_condense_ex(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J,
+                                               const void *kpts, int in_dtype, const int32_t *n_persons,
+                                               const snowtri_params *params, int method, int32_t Pout_max,
+                                               void *out_xyzs, void *out_pscore, int out_dtype,
+                                               int32_t *out_count, uint32_t *out_flags, int memspace,
+                                               void *stream, uint32_t call_flags) {
+    return fused_call(ctx, F, Pmax, J, kpts, in_dtype, n_persons, params, method, Pout_max, out_xyzs, out_pscore, out_dtype, out_count,
+                      out_flags, memspace, stream, call_flags, nullptr);
+}
+
+extern "C" int snowtri_triangulate_robust(snowtri_ctx *ctx, int64_t F, int32_t J, const void *kpts, int in_dtype, const int32_t *n_persons,
+                                          const snowtri_params *params, double reproj_threshold_px, int32_t max_drops, int32_t Pout_max,
+                                          void *out_xyzs, void *out_pscore, int out_dtype, int32_t *out_count, uint32_t *out_flags,
+                                          uint32_t *out_views, void *out_resid, int memspace, void *stream) {
+    if (!ctx) return SNOWTRI_ERR_BAD_ARG;
+    if (!(reproj_threshold_px >= 0.0)) {
+        g_last_error = "reproj_threshold_px must be >= 0 (+inf allowed), not negative or NaN";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    if (max_drops < 0 || max_drops > kRobustMaxDrops) {
+        g_last_error = "max_drops must be in [0, 6]";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    RobustCall rb;
+    rb.threshold_px = reproj_threshold_px;
+    rb.max_drops = max_drops;
+    rb.views = out_views;
+    rb.resid = out_resid;
+    return fused_call(ctx, F, 1, J, kpts, in_dtype, n_persons, params, SNOWTRI_DLT_ROBUST, Pout_max, out_xyzs, out_pscore, out_dtype,
+                      out_count, out_flags, memspace, stream, 0u, &rb);
+}
+
