@@ -101,62 +101,6 @@ struct Scratch {
     }
 };
 
-// The host arrays of one call staged through two Scratch buffers: `ins` holds what the kernels only read, `outs` what they
-// write.  The entry point declares each array by the address of its own device-pointer variable, which holds the caller's
-// pointer until begin() puts the staged address there (a null pointer declares nothing and stays null); begin() goes before
-// the first launch, end() behind the last.  Both buffers are sized before either base pointer is taken -- Scratch::ensure
-// frees and reallocates -- and every array starts on a 16-byte boundary (the uint4 kernels).  With host == false (a
-// SNOWTRI_DEVICE call) nothing happens at all: the caller's pointers pass through and the buffers, which may hold a host
-// caller's data, are not touched.
-struct Staging {
-    enum Kind { kIn, kOut, kInOut };
-    struct Entry {
-        void *var, *host, *dev;   // the entry point's variable, the caller's array, its staged copy
-        size_t bytes, off;
-        Kind kind;
-    };
-    static constexpr int kMaxArrays = 12;
-    Scratch &ins, &outs;
-    const bool host;
-    const hipStream_t st;
-    Entry e[kMaxArrays];
-    int n = 0;
-    size_t in_bytes = 0, out_bytes = 0;
-
-    Staging(Scratch &ins_, Scratch &outs_, bool host_, hipStream_t st_) : ins(ins_), outs(outs_), host(host_), st(st_) {}
-    template <typename T> void in(const T **var, size_t bytes) { add(var, (void *)*var, bytes, kIn); }
-    template <typename T> void out(T **var, size_t bytes) { add(var, (void *)*var, bytes, kOut); }
-    template <typename T> void inout(T **var, size_t bytes) { add(var, (void *)*var, bytes, kInOut); }
-    void add(void *var, void *host_array, size_t bytes, Kind kind) {
-        if (!host || !host_array) return;
-        size_t &total = kind == kIn ? in_bytes : out_bytes;
-        if (n < kMaxArrays) e[n] = Entry{var, host_array, nullptr, bytes, total, kind};
-        ++n;
-        total += (bytes + 15) & ~(size_t)15;
-    }
-    int begin() {
-        if (n > kMaxArrays) {
-            g_last_error = "Staging: more arrays than kMaxArrays";
-            return SNOWTRI_ERR_BAD_ARG;
-        }
-        if (int rc = in_bytes ? ins.ensure(in_bytes) : 0) return rc;
-        if (int rc = out_bytes ? outs.ensure(out_bytes) : 0) return rc;
-        for (int i = 0; i < n; i++) {
-            e[i].dev = (char *)(e[i].kind == kIn ? ins.p : outs.p) + e[i].off;
-            if (e[i].kind != kOut) HIP_TRY(hipMemcpyAsync(e[i].dev, e[i].host, e[i].bytes, hipMemcpyHostToDevice, st));
-            std::memcpy(e[i].var, &e[i].dev, sizeof(void *));   // (the variable is a pointer to some T: all of one representation)
-        }
-        return SNOWTRI_OK;
-    }
-    int end() {   // the downloads of the declared outputs, then the call's one synchronisation
-        if (!host) return SNOWTRI_OK;
-        for (int i = 0; i < n; i++)
-            if (e[i].kind != kIn) HIP_TRY(hipMemcpyAsync(e[i].host, e[i].dev, e[i].bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SNOWTRI_OK;
-    }
-};
-
 // Page-locked host staging for the small per-frame calls: one H2D and one D2H per call, both truly asynchronous
 // (a pageable copy is staged and synchronised by the runtime, ~10-20 us each).
 struct PinnedScratch {
@@ -282,11 +226,14 @@ struct snowtri_ctx {
     Scratch track;                            // centres [F][Pout_max][4] fp64 of snowtri_track_persons (k_track_centres -> k_track_chain)
     hipEvent_t track_ev[3] = {nullptr, nullptr, nullptr};   // with timing on: before k_track_centres | between | behind k_track_chain
     bool track_ev_valid = false;
-    PinnedScratch pin_in, pin_out;            // host staging of the per-frame calls
+    PinnedScratch pin_in, pin_out;            // host staging of the per-frame and fused calls (Staging)
     PinnedScratch pin_done;                   // the completion word of the small host calls (HostDone, snowtri_kernels.hpp)
     unsigned long long done_seq = 0;
+    std::vector<uint32_t> flags_host;         // the flags of a SNOWTRI_HOST fused call that passed no out_flags (it only grows)
     Scratch cand;                             // candidates of the last SNOWTRI_HOST snowtri_triangulate call (device-resident hand-over)
     int64_t cand_token = 0, cand_F = 0, cand_Kc = 0, cand_J = 0;   // token 0: none
+    const double *cand_xyz = nullptr, *cand_ks = nullptr;          // ... where that call left them in `cand`
+    const uint8_t *cand_keep = nullptr;
     int overlap = 1;                  // snowtri_ctx_set_overlap: device calls rotate over this many sets (1 = the caller's stream)
     int64_t call_index = 0;
     hipEvent_t ev_fork = nullptr;     // the caller's stream at the time of a call / a split: the internal streams wait for it
@@ -428,6 +375,140 @@ struct snowtri_ctx {
     long long names_key = -1;
     Rig rig() const { return Rig{dM, dt, dpairs, dpairc, dP, C, npairs}; }
 };
+
+namespace {
+
+static inline void cpu_relax() {   // spin-wait hint of the host CPU
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    asm volatile("yield" ::: "memory");
+#else
+    std::this_thread::yield();
+#endif
+}
+
+// The host arrays of one call staged through two Scratch buffers: `ins` holds what the kernels only read, `outs` what they
+// write.  The entry point declares each array by the address of its own device-pointer variable, which holds the caller's
+// pointer until begin() puts the staged address there (a null pointer declares nothing and stays null); begin() goes before
+// the first launch, end() behind the last.  Every buffer is sized before any base pointer is taken -- ensure() frees and
+// reallocates -- and the layout is the declared order, every array on a 16-byte boundary (the uint4 kernels).  With
+// host == false (a SNOWTRI_DEVICE call) nothing happens at all: the caller's pointers pass through and the buffers, which may
+// hold a host caller's data, are not touched.
+//
+// The arrays travel by one of three routes.  kDirect: one hipMemcpyAsync per array each way, between the caller's arrays and
+// the scratch -- what every entry point gets that names no other.  The per-frame and fused calls pass their context and the
+// furthest route they allow, and begin() chooses by the declared totals.  kPinned, while inputs and outputs are each within
+// kPinnedMaxBytes: the arrays are memcpy'd into ctx->pin_in and uploaded in one copy, the output block comes back in one copy
+// into ctx->pin_out and is memcpy'd out (a pageable copy is staged and synchronised by the runtime, ~10-20 us each).  kMapped,
+// while inputs plus outputs are within kZeroCopyMaxBytes: no copy engine at all -- the staged inputs ARE ctx->pin_in as the
+// device sees it, mapped() gives the twin of a staged output in ctx->pin_out for the kernels to write as well as (or instead
+// of) the scratch, and `done` is the armed completion word a single launch may signal (HostDone, snowtri_kernels.hpp).
+struct Staging {
+    enum Kind { kIn, kOut, kInOut };
+    enum Route { kDirect, kPinned, kMapped };
+    struct Entry {
+        void *var, *host, *dev;   // the entry point's variable, the caller's array, its staged copy
+        size_t bytes, off;
+        Kind kind;
+    };
+    static constexpr int kMaxArrays = 12;
+    static constexpr size_t kSlack = 256;   // behind each block
+    Scratch &ins, &outs;
+    const bool host;
+    const hipStream_t st;
+    snowtri_ctx *const ctx;
+    Route route;   // until begin(): the furthest route allowed; then: the route taken
+    HostDone done{nullptr, nullptr, 0ull};
+    Entry e[kMaxArrays];
+    int n = 0;
+    size_t in_bytes = 0, out_bytes = 0;
+
+    Staging(Scratch &ins_, Scratch &outs_, bool host_, hipStream_t st_, snowtri_ctx *ctx_ = nullptr, Route allow = kDirect)
+        : ins(ins_), outs(outs_), host(host_), st(st_), ctx(ctx_), route(host_ && ctx_ ? allow : kDirect) {}
+    template <typename T> void in(const T **var, size_t bytes) { add(var, (void *)*var, bytes, kIn); }
+    template <typename T> void out(T **var, size_t bytes) { add(var, (void *)*var, bytes, kOut); }
+    template <typename T> void inout(T **var, size_t bytes) { add(var, (void *)*var, bytes, kInOut); }
+    void add(void *var, void *host_array, size_t bytes, Kind kind) {
+        if (!host || !host_array) return;
+        if (kind == kInOut) route = kDirect;   // (no entry point on the page-locked routes has one)
+        size_t &total = kind == kIn ? in_bytes : out_bytes;
+        if (n < kMaxArrays) e[n] = Entry{var, host_array, nullptr, bytes, total, kind};
+        ++n;
+        total += (bytes + 15) & ~(size_t)15;
+    }
+    int begin() {
+        if (n > kMaxArrays) {
+            g_last_error = "Staging: more arrays than kMaxArrays";
+            return SNOWTRI_ERR_BAD_ARG;
+        }
+        if (in_bytes > kPinnedMaxBytes || out_bytes > kPinnedMaxBytes) route = kDirect;   // larger host batches keep the direct copies
+        else if (route == kMapped && in_bytes + out_bytes > kZeroCopyMaxBytes) route = kPinned;
+        if (int rc = in_bytes ? ins.ensure(in_bytes + kSlack) : 0) return rc;
+        if (int rc = out_bytes ? outs.ensure(out_bytes + kSlack) : 0) return rc;
+        if (int rc = (route != kDirect && in_bytes) ? ctx->pin_in.ensure(in_bytes + kSlack) : 0) return rc;
+        if (int rc = (route != kDirect && out_bytes) ? ctx->pin_out.ensure(out_bytes + kSlack) : 0) return rc;
+        if (route == kMapped) {   // arm the completion word
+            if (int rc = ctx->pin_done.ensure(64)) return rc;
+            done = HostDone{(unsigned int *)(ctx->d_counters + kHostDoneCountAt), (unsigned long long *)ctx->pin_done.dev, ++ctx->done_seq};
+        }
+        for (int i = 0; i < n; i++) {
+            e[i].dev = (char *)(e[i].kind != kIn ? outs.p : route == kMapped ? ctx->pin_in.dev : ins.p) + e[i].off;
+            if (e[i].kind != kOut && e[i].bytes) {
+                if (route == kDirect) HIP_TRY(hipMemcpyAsync(e[i].dev, e[i].host, e[i].bytes, hipMemcpyHostToDevice, st));
+                else std::memcpy((char *)ctx->pin_in.p + e[i].off, e[i].host, e[i].bytes);
+            }
+            std::memcpy(e[i].var, &e[i].dev, sizeof(void *));   // (the variable is a pointer to some T: all of one representation)
+        }
+        if (route == kPinned && in_bytes) HIP_TRY(hipMemcpyAsync(ins.p, ctx->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));   // one staged upload
+        return SNOWTRI_OK;
+    }
+    // the twin of a staged output in mapped host memory as the device sees it; null unless the mapped route was taken
+    template <typename T> T *mapped(T *dev) const {
+        return route == kMapped ? (T *)((char *)ctx->pin_out.dev + ((char *)dev - (char *)outs.p)) : nullptr;
+    }
+    // zeros in the whole output block (not on the mapped route: its kernels write every byte of both copies)
+    int clear_outputs() {
+        if (out_bytes && route != kMapped) HIP_TRY(hipMemsetAsync(outs.p, 0, out_bytes, st));
+        return SNOWTRI_OK;
+    }
+    // The downloads of the declared outputs, then the call's one synchronisation.  signalled: the launch signals `done` (its
+    // outputs are in mapped host memory by then), so a mapped call spins on the word instead of sleeping on the runtime's interrupt.
+    int end(bool signalled = false) {
+        if (!host) return SNOWTRI_OK;
+        if (route == kPinned && out_bytes) HIP_TRY(hipMemcpyAsync(ctx->pin_out.p, outs.p, out_bytes, hipMemcpyDeviceToHost, st));   // one staged download
+        for (int i = 0; i < n && route == kDirect; i++)
+            if (e[i].kind != kIn && e[i].bytes) HIP_TRY(hipMemcpyAsync(e[i].host, e[i].dev, e[i].bytes, hipMemcpyDeviceToHost, st));
+        if (route == kMapped && signalled) {
+            if (int rc = wait_done()) return rc;
+        } else {
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        for (int i = 0; i < n && route != kDirect; i++)
+            if (e[i].kind != kIn && e[i].bytes) std::memcpy(e[i].host, (const char *)ctx->pin_out.p + e[i].off, e[i].bytes);
+        return SNOWTRI_OK;
+    }
+    // spin on the completion word; hipStreamSynchronize stays as the fall-back after 50 ms of spinning
+    int wait_done() {
+        const volatile unsigned long long *w = (const volatile unsigned long long *)ctx->pin_done.p;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spins = 0; *w != done.seq; spins++) {
+            cpu_relax();
+            if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) {
+                HIP_TRY(hipStreamSynchronize(st));   // (a failed launch never writes the word: the runtime reports it here)
+                if (*w != done.seq) {
+                    g_last_error = "a per-frame kernel finished without its completion word";
+                    return SNOWTRI_ERR_HIP;
+                }
+                break;
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        return SNOWTRI_OK;
+    }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -992,57 +1073,18 @@ int validate_params(const snowtri_params *p, int J, Params *out, bool need_conde
 
 size_t dtype_size(int dt) { return dt == SNOWTRI_F32 ? 4 : 8; }
 
-// The completion word of a small host call: arm it before the launch, spin on it afterwards (the kernels' outputs are already
-// in mapped host memory then).  hipStreamSynchronize stays as the fall-back after 50 ms of spinning.
-int host_done_arm(snowtri_ctx *ctx, HostDone *hd) {
-    int rc = ctx->pin_done.ensure(64);
-    if (rc) return rc;
-    hd->count = (unsigned int *)(ctx->d_counters + kHostDoneCountAt);
-    hd->flag = (unsigned long long *)ctx->pin_done.dev;
-    hd->seq = ++ctx->done_seq;
-    return SNOWTRI_OK;
-}
-static inline void cpu_relax() {   // spin-wait hint of the host CPU
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield" ::: "memory");
-#else
-    std::this_thread::yield();
-#endif
-}
-int host_done_wait(snowtri_ctx *ctx, hipStream_t st, const HostDone &hd) {
-    const volatile unsigned long long *w = (const volatile unsigned long long *)ctx->pin_done.p;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0; *w != hd.seq; spins++) {
-        cpu_relax();
-        if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) {
-            HIP_TRY(hipStreamSynchronize(st));   // (a failed launch never writes the word: the runtime reports it here)
-            if (*w != hd.seq) {
-                g_last_error = "a per-frame kernel finished without its completion word";
-                return SNOWTRI_ERR_HIP;
-            }
-            break;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return SNOWTRI_OK;
-}
-
+// m*: the mapped twins of the outputs and of the singular count, which the kernels fill as well (Staging::mapped; null: no mirror)
 template <typename TIn>
 void launch_triangulate(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, int J, int Kc,
                         const void *kpts, const int32_t *n_persons, const Params &prm, double *cxyz,
-                        double *cks, double *cps, uint8_t *ckeep, unsigned long long *n_singular, char *mirror = nullptr,
+                        double *cks, double *cps, uint8_t *ckeep, unsigned long long *n_singular, double *mx = nullptr,
+                        double *mk = nullptr, double *mp = nullptr, uint8_t *mkeep = nullptr, unsigned long long *mns = nullptr,
                         HostDone done = HostDone{nullptr, nullptr, 0ull}, bool *one_launch = nullptr) {
-    // mirror: host-mapped block [xyz | kscore | pscore | keep | (16-byte aligned) singular count] the kernels fill as well
     const int64_t total = F * (int64_t)Kc * J;
-    double *mx = (double *)mirror, *mk = mirror ? mx + 3 * total : nullptr, *mp = mirror ? mk + total : nullptr;
-    uint8_t *mkeep = mirror ? (uint8_t *)(mp + F * (int64_t)Kc) : nullptr;
-    const size_t ns_off = ((sizeof(double) * ((size_t)total * 4 + (size_t)F * Kc) + (size_t)F * Kc) + 15) & ~(size_t)15;
-    if (mirror && F * (int64_t)Kc <= 4096 && J <= 4096) {   // the per-frame call: one launch, a workgroup per candidate slot
+    if (mx && F * (int64_t)Kc <= 4096 && J <= 4096) {   // the per-frame call: one launch, a workgroup per candidate slot
         hipLaunchKernelGGL((k_triangulate_slots<TIn>), dim3((unsigned)(F * Kc)), dim3(kBlock), sizeof(double) * J, st, F, Pmax, J, Kc, ctx->rig(),
                            (const TIn *)kpts, n_persons, prm, cxyz, cks, cps, ckeep, n_singular, mx, mk, mp, mkeep,
-                           (unsigned long long *)(mirror + ns_off), (unsigned int *)(n_singular + 1), done);
+                           mns, (unsigned int *)(n_singular + 1), done);
         if (one_launch) *one_launch = true;
         return;
     }
@@ -1051,7 +1093,7 @@ void launch_triangulate(snowtri_ctx *ctx, hipStream_t st, int64_t F, int Pmax, i
                        n_singular, mx, mk);
     hipLaunchKernelGGL(k_cand_mean, dim3(grid_for(F * (int64_t)Kc, kBlock / 64, ctx->num_cus * 16)),
                        dim3(kBlock), 0, st, F, Pmax, J, Kc, ctx->rig(), n_persons, prm, (const double *)cks,
-                       cps, ckeep, mp, mkeep, n_singular, mirror ? (unsigned long long *)(mirror + ns_off) : nullptr);
+                       cps, ckeep, mp, mkeep, n_singular, mns);
 }
 
 constexpr int kCondenseMaxN = 9000;  // condense_lds_bytes(N) <= 160 KiB
@@ -1096,99 +1138,51 @@ int snowtri_triangulate(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, co
     if (rc) return rc;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    const size_t in_bytes = (size_t)F * ctx->C * Pmax * J * 3 * dtype_size(in_dtype);
-    const size_t np_bytes = n_persons ? sizeof(int32_t) * F * ctx->C : 0;
-    const size_t nx = (size_t)F * Kc * J;
+    const bool host = memspace == SNOWTRI_HOST;
+    const size_t slots = (size_t)F * Kc, nx = slots * J;
     const void *d_kpts = kpts;
     const int32_t *d_np = n_persons;
     double *d_xyz = cand_xyz, *d_ks = cand_kscore, *d_ps = cand_pscore;
     uint8_t *d_keep = cand_keep;
-    unsigned long long *d_nsing = ctx->d_counters;
-    const size_t in_np_off = (in_bytes + 15) & ~(size_t)15;
-    const size_t out_bytes = sizeof(double) * (nx * 4 + (size_t)F * Kc) + (size_t)F * Kc;
-    const size_t out_ns_off = (out_bytes + 15) & ~(size_t)15;          // the singular-pair counter rides behind the outputs
-    const bool host = memspace == SNOWTRI_HOST;
-    const bool pinned = host && in_np_off + np_bytes <= kPinnedMaxBytes && out_ns_off + 8 <= kPinnedMaxBytes;
-    // the per-frame call: kernels read the staged inputs and mirror their outputs in mapped page-locked memory, no copy engine
-    const bool zero_copy = pinned && in_np_off + np_bytes + out_ns_off + 8 <= kZeroCopyMaxBytes;
-    char *mirror = nullptr;
-    if (host) {
-        rc = ctx->in.ensure(in_np_off + np_bytes + 16);
-        if (rc) return rc;
-        rc = ctx->cand.ensure(out_ns_off + 64);   // (a scratch of its own: the candidates stay resident for snowtri_condense_resident)
-        if (rc) return rc;
-        ctx->cand_token = 0;
-        d_kpts = ctx->in.p;
-        if (n_persons) d_np = (int32_t *)((char *)ctx->in.p + in_np_off);
-        d_xyz = (double *)ctx->cand.p;
-        d_ks = d_xyz + nx * 3;
-        d_ps = d_ks + nx;
-        d_keep = (uint8_t *)(d_ps + (size_t)F * Kc);
-        d_nsing = (unsigned long long *)((char *)ctx->cand.p + out_ns_off);
-        if (pinned) {   // one staged upload
-            rc = ctx->pin_in.ensure(in_np_off + np_bytes);
-            if (rc) return rc;
-            rc = ctx->pin_out.ensure(out_ns_off + 8);
-            if (rc) return rc;
-            std::memcpy(ctx->pin_in.p, kpts, in_bytes);
-            if (n_persons) std::memcpy((char *)ctx->pin_in.p + in_np_off, n_persons, np_bytes);
-            if (zero_copy) {
-                d_kpts = ctx->pin_in.dev;
-                if (n_persons) d_np = (int32_t *)((char *)ctx->pin_in.dev + in_np_off);
-                mirror = (char *)ctx->pin_out.dev;
-                d_nsing = ctx->d_counters + kTriangulateSingularAt;   // (left at 0 by every call: k_cand_mean hands it over)
-            } else {
-                HIP_TRY(hipMemcpyAsync(ctx->in.p, ctx->pin_in.p, in_np_off + np_bytes, hipMemcpyHostToDevice, st));
-            }
-        } else {
-            HIP_TRY(hipMemcpyAsync(ctx->in.p, kpts, in_bytes, hipMemcpyHostToDevice, st));
-            if (n_persons) HIP_TRY(hipMemcpyAsync((void *)d_np, n_persons, np_bytes, hipMemcpyHostToDevice, st));
-        }
-        if (!zero_copy) HIP_TRY(hipMemsetAsync(d_xyz, 0, out_ns_off + 8, st));  // invalid slots read back as zeros; counter = 0
-    } else {
-        HIP_TRY(hipMemsetAsync(d_nsing, 0, sizeof(unsigned long long), st));
-    }
-    HostDone done{nullptr, nullptr, 0ull};
-    bool polled = false;
-    if (zero_copy) {
-        rc = host_done_arm(ctx, &done);
-        if (rc) return rc;
-    }
+    unsigned long long ns = 0, *d_nsing = host ? &ns : ctx->d_counters;   // (a host call's singular-pair counter rides behind its outputs)
+    // The outputs in a scratch of their own: the candidates stay resident for snowtri_condense_resident.  The per-frame call takes
+    // the mapped route: its kernels read the staged inputs and mirror their outputs in mapped page-locked memory, no copy engine.
+    Staging sg(ctx->in, ctx->cand, host, st, ctx, Staging::kMapped);
+    sg.in(&d_kpts, (size_t)F * ctx->C * Pmax * J * 3 * dtype_size(in_dtype));
+    sg.in(&d_np, sizeof(int32_t) * F * ctx->C);
+    sg.out(&d_xyz, sizeof(double) * nx * 3);
+    sg.out(&d_ks, sizeof(double) * nx);
+    sg.out(&d_ps, sizeof(double) * slots);
+    sg.out(&d_keep, slots);
+    sg.out(&d_nsing, sizeof(ns));
+    if (host) ctx->cand_token = 0;
+    rc = sg.begin();
+    if (rc) return rc;
+    unsigned long long *const m_nsing = sg.mapped(d_nsing);
+    if (m_nsing) d_nsing = ctx->d_counters + kTriangulateSingularAt;   // (left at 0 by every call: the kernels hand it over to the twin)
+    if (host) rc = sg.clear_outputs();   // invalid slots read back as zeros; counter = 0
+    else HIP_TRY(hipMemsetAsync(d_nsing, 0, sizeof(unsigned long long), st));
+    if (rc) return rc;
+    bool polled = false;   // the one-launch kernel signals the completion word
     if (in_dtype == SNOWTRI_F32)
-        launch_triangulate<float>(ctx, st, F, Pmax, J, (int)Kc, d_kpts, d_np, prm, d_xyz, d_ks, d_ps, d_keep, d_nsing, mirror, done, &polled);
+        launch_triangulate<float>(ctx, st, F, Pmax, J, (int)Kc, d_kpts, d_np, prm, d_xyz, d_ks, d_ps, d_keep, d_nsing, sg.mapped(d_xyz),
+                                  sg.mapped(d_ks), sg.mapped(d_ps), sg.mapped(d_keep), m_nsing, sg.done, &polled);
     else
-        launch_triangulate<double>(ctx, st, F, Pmax, J, (int)Kc, d_kpts, d_np, prm, d_xyz, d_ks, d_ps, d_keep, d_nsing, mirror, done, &polled);
+        launch_triangulate<double>(ctx, st, F, Pmax, J, (int)Kc, d_kpts, d_np, prm, d_xyz, d_ks, d_ps, d_keep, d_nsing, sg.mapped(d_xyz),
+                                   sg.mapped(d_ks), sg.mapped(d_ps), sg.mapped(d_keep), m_nsing, sg.done, &polled);
     HIP_TRY(hipGetLastError());
+    rc = sg.end(polled);
+    if (rc) return rc;
     if (host) {
-        unsigned long long ns = 0;
-        if (pinned) {   // one staged download (zero_copy: the kernels have written the staging buffer themselves)
-            if (!zero_copy) HIP_TRY(hipMemcpyAsync(ctx->pin_out.p, ctx->cand.p, out_ns_off + 8, hipMemcpyDeviceToHost, st));
-            if (polled) {   // the one-launch kernel signals a mapped word: no sleep on the runtime's interrupt
-                rc = host_done_wait(ctx, st, done);
-                if (rc) return rc;
-            } else {
-                HIP_TRY(hipStreamSynchronize(st));
-            }
-            const char *o = (const char *)ctx->pin_out.p;
-            std::memcpy(cand_xyz, o, sizeof(double) * nx * 3);
-            std::memcpy(cand_kscore, o + sizeof(double) * nx * 3, sizeof(double) * nx);
-            std::memcpy(cand_pscore, o + sizeof(double) * nx * 4, sizeof(double) * F * Kc);
-            std::memcpy(cand_keep, o + sizeof(double) * (nx * 4 + (size_t)F * Kc), (size_t)F * Kc);
-            std::memcpy(&ns, o + out_ns_off, sizeof(ns));
-        } else {
-            HIP_TRY(hipMemcpyAsync(cand_xyz, d_xyz, sizeof(double) * nx * 3, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(cand_kscore, d_ks, sizeof(double) * nx, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(cand_pscore, d_ps, sizeof(double) * F * Kc, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(cand_keep, d_keep, (size_t)F * Kc, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(&ns, d_nsing, sizeof(ns), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
         // the candidates stay on the device under a fresh token (snowtri_condense_resident)
         static std::atomic<int64_t> next_token{1};
         ctx->cand_token = next_token.fetch_add(1);
         ctx->cand_F = F;
         ctx->cand_Kc = Kc;
         ctx->cand_J = J;
+        ctx->cand_xyz = d_xyz;
+        ctx->cand_ks = d_ks;
+        ctx->cand_keep = d_keep;
         if (ns) return SNOWTRI_ERR_SINGULAR;
     }
     return SNOWTRI_OK;
@@ -1211,82 +1205,32 @@ int snowtri_condense(snowtri_ctx *ctx, int64_t F, int32_t N, int32_t J, const do
     if (rc) return rc;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    const int kn = prm.kn;
-    const size_t nx = (size_t)F * N * J;
-    const size_t no = (size_t)F * Pout_max * kn;
+    const size_t nx = (size_t)F * N * J, no = (size_t)F * Pout_max * prm.kn;
     const double *d_xyz = cand_xyz, *d_ks = cand_kscore;
     const uint8_t *d_keep = cand_keep;
     double *o_xyz = out_xyz, *o_ks = out_kscore, *o_ps = out_pscore;
     int32_t *o_cnt = out_count;
     uint32_t *o_fl = out_flags;
     const bool host = memspace == SNOWTRI_HOST;
-    const size_t in_total = sizeof(double) * nx * 4 + (size_t)F * N;
-    const size_t out_total = sizeof(double) * (no * 4 + (size_t)F * Pout_max) + 8 * (size_t)F;
-    const bool pinned = host && in_total <= kPinnedMaxBytes && out_total <= kPinnedMaxBytes;
-    if (host) {
-        rc = ctx->in.ensure(in_total + 64);
-        if (rc) return rc;
-        rc = ctx->out.ensure(out_total + 64);
-        if (rc) return rc;
-        double *p = (double *)ctx->in.p;
-        d_xyz = p;
-        d_ks = p + nx * 3;
-        if (cand_keep && N) d_keep = (uint8_t *)(p + nx * 4);
-        if (pinned) {   // one staged upload
-            rc = ctx->pin_in.ensure(in_total + 16);
-            if (rc) return rc;
-            rc = ctx->pin_out.ensure(out_total + 16);
-            if (rc) return rc;
-            char *h = (char *)ctx->pin_in.p;
-            if (nx) {
-                std::memcpy(h, cand_xyz, sizeof(double) * nx * 3);
-                std::memcpy(h + sizeof(double) * nx * 3, cand_kscore, sizeof(double) * nx);
-            }
-            if (cand_keep && N) std::memcpy(h + sizeof(double) * nx * 4, cand_keep, (size_t)F * N);
-            const size_t up = sizeof(double) * nx * 4 + ((cand_keep && N) ? (size_t)F * N : 0);
-            if (up) HIP_TRY(hipMemcpyAsync(p, h, up, hipMemcpyHostToDevice, st));
-        } else {
-            if (nx) {
-                HIP_TRY(hipMemcpyAsync(p, cand_xyz, sizeof(double) * nx * 3, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(p + nx * 3, cand_kscore, sizeof(double) * nx, hipMemcpyHostToDevice, st));
-            }
-            if (cand_keep && N) HIP_TRY(hipMemcpyAsync((void *)d_keep, cand_keep, (size_t)F * N, hipMemcpyHostToDevice, st));
-        }
-        o_xyz = (double *)ctx->out.p;
-        o_ks = o_xyz + no * 3;
-        o_ps = o_ks + no;
-        o_cnt = (int32_t *)(o_ps + (size_t)F * Pout_max);
-        o_fl = (uint32_t *)(o_cnt + F);
-    }
+    Staging sg(ctx->in, ctx->out, host, st, ctx, Staging::kPinned);
+    sg.in(&d_xyz, sizeof(double) * nx * 3);
+    sg.in(&d_ks, sizeof(double) * nx);
+    sg.in(&d_keep, (size_t)F * N);
+    sg.out(&o_xyz, sizeof(double) * no * 3);
+    sg.out(&o_ks, sizeof(double) * no);
+    sg.out(&o_ps, sizeof(double) * F * Pout_max);
+    sg.out(&o_cnt, sizeof(int32_t) * F);
+    sg.out(&o_fl, sizeof(uint32_t) * F);
+    rc = sg.begin();
+    if (rc) return rc;
     if (o_fl) HIP_TRY(hipMemsetAsync(o_fl, 0, sizeof(uint32_t) * F, st));
     rc = launch_condense(ctx, st, F, N, J, d_xyz, d_ks, d_keep, prm, Pout_max, SplitWriter{o_xyz, o_ks, o_ps},
                          o_cnt, o_fl);
     if (rc) return rc;
-    if (host) {
-        if (pinned) {   // one staged download
-            HIP_TRY(hipMemcpyAsync(ctx->pin_out.p, ctx->out.p, out_total, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            const char *o = (const char *)ctx->pin_out.p;
-            if (no) {
-                std::memcpy(out_xyz, o, sizeof(double) * no * 3);
-                std::memcpy(out_kscore, o + sizeof(double) * no * 3, sizeof(double) * no);
-            }
-            std::memcpy(out_pscore, o + sizeof(double) * no * 4, sizeof(double) * F * Pout_max);
-            std::memcpy(out_count, o + sizeof(double) * (no * 4 + (size_t)F * Pout_max), sizeof(int32_t) * F);
-            if (out_flags) std::memcpy(out_flags, o + sizeof(double) * (no * 4 + (size_t)F * Pout_max) + sizeof(int32_t) * F, sizeof(uint32_t) * F);
-        } else {
-            if (no) {
-                HIP_TRY(hipMemcpyAsync(out_xyz, o_xyz, sizeof(double) * no * 3, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(out_kscore, o_ks, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-            }
-            HIP_TRY(hipMemcpyAsync(out_pscore, o_ps, sizeof(double) * F * Pout_max, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_count, o_cnt, sizeof(int32_t) * F, hipMemcpyDeviceToHost, st));
-            if (out_flags) HIP_TRY(hipMemcpyAsync(out_flags, o_fl, sizeof(uint32_t) * F, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        for (int64_t f = 0; f < F; f++)
-            if (out_count[f] > Pout_max) return SNOWTRI_ERR_OVERFLOW;
-    }
+    rc = sg.end();
+    if (rc) return rc;
+    for (int64_t f = 0; host && f < F; f++)
+        if (out_count[f] > Pout_max) return SNOWTRI_ERR_OVERFLOW;
     return SNOWTRI_OK;
 }
 
@@ -1304,50 +1248,24 @@ int snowtri_condense_resident(snowtri_ctx *ctx, int64_t token, const snowtri_par
     if (rc) return rc;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = nullptr;
-    const int kn = prm.kn;
-    const size_t nx = (size_t)F * N * J, no = (size_t)F * Pout_max * kn;
-    const double *d_xyz = (const double *)ctx->cand.p, *d_ks = d_xyz + nx * 3;
-    const uint8_t *d_keep = (const uint8_t *)(d_ks + nx + (size_t)F * N);
-    const size_t out_total = sizeof(double) * (no * 4 + (size_t)F * Pout_max) + 4 * (size_t)F;   // xyz | kscore | pscore | count
-    const bool zero_copy = out_total <= kZeroCopyMaxBytes;   // the kernel writes the page-locked staging buffer itself
-    char *base;
-    if (zero_copy) {
-        rc = ctx->pin_out.ensure(out_total + 16);
-        if (rc) return rc;
-        base = (char *)ctx->pin_out.dev;
-    } else {
-        rc = ctx->out.ensure(out_total + 64);
-        if (rc) return rc;
-        base = (char *)ctx->out.p;
-    }
-    double *o_xyz = (double *)base, *o_ks = o_xyz + no * 3, *o_ps = o_ks + no;
-    int32_t *o_cnt = (int32_t *)(o_ps + (size_t)F * Pout_max);
+    const size_t no = (size_t)F * Pout_max * prm.kn;
+    double *o_xyz = out_xyz, *o_ks = out_kscore, *o_ps = out_pscore;
+    int32_t *o_cnt = out_count;
     // (the only flag of this entry is the overflow bit: derived from the counts below, no atomics on mapped memory)
-    HostDone done{nullptr, nullptr, 0ull};
-    if (zero_copy) {
-        rc = host_done_arm(ctx, &done);
-        if (rc) return rc;
-    }
-    rc = launch_condense(ctx, st, F, (int)N, J, d_xyz, d_ks, d_keep, prm, Pout_max, SplitWriter{o_xyz, o_ks, o_ps}, o_cnt, (uint32_t *)nullptr, done);
+    Staging sg(ctx->in, ctx->out, true, st, ctx, Staging::kMapped);
+    sg.out(&o_xyz, sizeof(double) * no * 3);
+    sg.out(&o_ks, sizeof(double) * no);
+    sg.out(&o_ps, sizeof(double) * F * Pout_max);
+    sg.out(&o_cnt, sizeof(int32_t) * F);
+    rc = sg.begin();
     if (rc) return rc;
-    if (zero_copy) {
-        rc = host_done_wait(ctx, st, done);
-        if (rc) return rc;
-    } else {
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    auto fetch = [&](void *dst, size_t off, size_t bytes) -> hipError_t {
-        if (!bytes) return hipSuccess;
-        if (zero_copy) {
-            std::memcpy(dst, (const char *)ctx->pin_out.p + off, bytes);
-            return hipSuccess;
-        }
-        return hipMemcpy(dst, base + off, bytes, hipMemcpyDeviceToHost);
-    };
-    HIP_TRY(fetch(out_xyz, 0, sizeof(double) * no * 3));
-    HIP_TRY(fetch(out_kscore, sizeof(double) * no * 3, sizeof(double) * no));
-    HIP_TRY(fetch(out_pscore, sizeof(double) * no * 4, sizeof(double) * F * Pout_max));
-    HIP_TRY(fetch(out_count, sizeof(double) * (no * 4 + (size_t)F * Pout_max), sizeof(int32_t) * F));
+    if (sg.mapped(o_cnt))   // the kernel writes the page-locked staging buffer itself, and nothing else
+        o_xyz = sg.mapped(o_xyz), o_ks = sg.mapped(o_ks), o_ps = sg.mapped(o_ps), o_cnt = sg.mapped(o_cnt);
+    rc = launch_condense(ctx, st, F, (int)N, J, ctx->cand_xyz, ctx->cand_ks, ctx->cand_keep, prm, Pout_max, SplitWriter{o_xyz, o_ks, o_ps}, o_cnt,
+                         (uint32_t *)nullptr, sg.done);
+    if (rc) return rc;
+    rc = sg.end(true);   // (k_condense signals the completion word it is given)
+    if (rc) return rc;
     int status = SNOWTRI_OK;
     for (int64_t f = 0; f < F; f++) {
         const bool over = out_count[f] > Pout_max;
@@ -3303,50 +3221,29 @@ int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void 
     }
     const int kn = prm.kn;
     const size_t isz = dtype_size(in_dtype), osz = dtype_size(out_dtype);
-    const size_t in_bytes = (size_t)F * ctx->C * Pmax * J * 3 * isz;
-    const size_t np_bytes = n_persons ? sizeof(int32_t) * F * ctx->C : 0;
-    const size_t o4 = (size_t)F * Pout_max * kn * 4 * osz, ops = (size_t)F * Pout_max * osz;
+    const bool host = memspace == SNOWTRI_HOST;
     const void *d_kpts = kpts;
     const int32_t *d_np = n_persons;
     void *d_xyzs = out_xyzs, *d_ps = out_pscore;
     int32_t *d_cnt = out_count;
     uint32_t *d_fl = out_flags;
-    const size_t np_off = (in_bytes + 15) & ~(size_t)15;
-    const size_t ps_off = (o4 + 15) & ~(size_t)15, cnt_off = ps_off + ((ops + 15) & ~(size_t)15);
-    // the diagnostics of snowtri_triangulate_robust behind the flags (host calls: staged like everything else)
-    uint32_t *const h_views = rb.views;
-    void *const h_resid = rb.resid;
-    const size_t views_bytes = h_views ? sizeof(uint32_t) * (size_t)F * kn : 0, resid_bytes = h_resid ? osz * (size_t)F * kn : 0;
-    const size_t views_off = (cnt_off + 8 * (size_t)F + 15) & ~(size_t)15, resid_off = views_off + ((views_bytes + 15) & ~(size_t)15);
-    const size_t out_total = (h_views || h_resid) ? resid_off + resid_bytes : cnt_off + 8 * (size_t)F;
-    const bool pinned = memspace == SNOWTRI_HOST && np_off + np_bytes <= kPinnedMaxBytes && out_total <= kPinnedMaxBytes;
-    if (memspace == SNOWTRI_HOST) {
-        rc = ctx->in.ensure(np_off + np_bytes + 64);
-        if (rc) return rc;
-        rc = ctx->out.ensure(out_total + 256);
-        if (rc) return rc;
-        d_kpts = ctx->in.p;
-        if (n_persons) d_np = (int32_t *)((char *)ctx->in.p + np_off);
-        if (pinned) {   // one staged upload (page-locked: truly asynchronous)
-            rc = ctx->pin_in.ensure(np_off + np_bytes);
-            if (rc) return rc;
-            rc = ctx->pin_out.ensure(out_total);
-            if (rc) return rc;
-            std::memcpy(ctx->pin_in.p, kpts, in_bytes);
-            if (n_persons) std::memcpy((char *)ctx->pin_in.p + np_off, n_persons, np_bytes);
-            HIP_TRY(hipMemcpyAsync(ctx->in.p, ctx->pin_in.p, np_off + np_bytes, hipMemcpyHostToDevice, st));
-        } else {
-            HIP_TRY(hipMemcpyAsync(ctx->in.p, kpts, in_bytes, hipMemcpyHostToDevice, st));
-            if (n_persons) HIP_TRY(hipMemcpyAsync((void *)d_np, n_persons, np_bytes, hipMemcpyHostToDevice, st));
-        }
-        char *o = (char *)ctx->out.p;
-        d_xyzs = o;
-        d_ps = o + ps_off;
-        d_cnt = (int32_t *)(o + cnt_off);
-        d_fl = (uint32_t *)(d_cnt + F);
-        if (h_views) rb.views = (uint32_t *)(o + views_off);
-        if (h_resid) rb.resid = o + resid_off;
-    } else if (!d_fl) {
+    if (host && !d_fl) {   // the return status and last_slow_frames come from the flags: a host call always takes them back
+        if (ctx->flags_host.size() < (size_t)F) ctx->flags_host.resize(F);
+        d_fl = ctx->flags_host.data();
+    }
+    const uint32_t *const fl = d_fl;   // (a host call's flags on the host)
+    Staging sg(ctx->in, ctx->out, host, st, ctx, Staging::kPinned);
+    sg.in(&d_kpts, (size_t)F * ctx->C * Pmax * J * 3 * isz);
+    sg.in(&d_np, sizeof(int32_t) * F * ctx->C);
+    sg.out(&d_xyzs, (size_t)F * Pout_max * kn * 4 * osz);
+    sg.out(&d_ps, (size_t)F * Pout_max * osz);
+    sg.out(&d_cnt, sizeof(int32_t) * F);
+    sg.out(&d_fl, sizeof(uint32_t) * F);
+    sg.out(&rb.views, sizeof(uint32_t) * F * kn);   // the diagnostics of snowtri_triangulate_robust: staged like everything else
+    sg.out(&rb.resid, osz * F * kn);
+    rc = sg.begin();
+    if (rc) return rc;
+    if (!d_fl) {   // a device call that takes no flags
         rc = ctx->cur->misc.ensure(sizeof(uint32_t) * F);
         if (rc) return rc;
         d_fl = (uint32_t *)ctx->cur->misc.p;
@@ -3370,35 +3267,9 @@ int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void 
     ctx->cur = &ctx->sets[0];
     if (rc) return rc;
     if (oset) oset->pending = true;   // (its `done` event is recorded once, by snowtri_ctx_join)
-    if (memspace == SNOWTRI_HOST) {
-        std::vector<uint32_t> fl_host;
-        uint32_t *fl = out_flags;
-        if (pinned) {   // one staged download
-            HIP_TRY(hipMemcpyAsync(ctx->pin_out.p, ctx->out.p, out_total, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            const char *o = (const char *)ctx->pin_out.p;
-            std::memcpy(out_xyzs, o, o4);
-            if (out_pscore) std::memcpy(out_pscore, o + ps_off, ops);
-            std::memcpy(out_count, o + cnt_off, sizeof(int32_t) * F);
-            if (out_flags)
-                std::memcpy(out_flags, o + cnt_off + sizeof(int32_t) * F, sizeof(uint32_t) * F);
-            else
-                fl = (uint32_t *)(o + cnt_off + sizeof(int32_t) * F);
-            if (h_views) std::memcpy(h_views, o + views_off, views_bytes);
-            if (h_resid) std::memcpy(h_resid, o + resid_off, resid_bytes);
-        } else {
-            HIP_TRY(hipMemcpyAsync(out_xyzs, d_xyzs, o4, hipMemcpyDeviceToHost, st));
-            if (out_pscore) HIP_TRY(hipMemcpyAsync(out_pscore, d_ps, ops, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_count, d_cnt, sizeof(int32_t) * F, hipMemcpyDeviceToHost, st));
-            if (!fl) {
-                fl_host.resize(F);
-                fl = fl_host.data();
-            }
-            HIP_TRY(hipMemcpyAsync(fl, d_fl, sizeof(uint32_t) * F, hipMemcpyDeviceToHost, st));
-            if (h_views) HIP_TRY(hipMemcpyAsync(h_views, rb.views, views_bytes, hipMemcpyDeviceToHost, st));
-            if (h_resid) HIP_TRY(hipMemcpyAsync(h_resid, rb.resid, resid_bytes, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
+    rc = sg.end();
+    if (rc) return rc;
+    if (host) {
         uint32_t any = 0;
         int64_t slow = 0;
         for (int64_t f = 0; f < F; f++) {

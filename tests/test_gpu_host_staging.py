@@ -2,7 +2,8 @@
 (snowmocap_amd/csrc/snowtri.hip: ctx->in, ctx->out).  A host call uploads its arrays, runs the kernels of the device call on the
 staged copies, and downloads the outputs, so every output has to come back bit for bit as the device call leaves it: with an
 optional array absent, across a regrowth of the scratch (it starts at 1 MiB and is freed and reallocated beyond that), and for
-an array that is both read and written.  No tolerance anywhere: both sides are the same kernels on the same values.
+an array that is both read and written; and, for the per-frame and fused calls, on each of the routes the staging helper chooses by
+the call's byte totals (section 5).  No tolerance anywhere: both sides are the same kernels on the same values.
 
 Every output buffer starts as 0xA5 bytes on both routes, so a byte neither route writes compares equal and a byte only one of them
 writes does not.  Only the production library is loaded.
@@ -388,3 +389,243 @@ def test_shard_fix_reads_and_writes_y_through_the_staging(ctx):
         fixed = shard_fix(ctx, Host, y_host, start, first)
         _same(fixed, shard_fix(ctx, Device, y_dev, start, first), f"snowtri_smooth_shard_fix first={first}")
         assert not np.array_equal(fixed[0], y_host), "the fix has changed y"
+
+
+# ------------------------------------------------------------------------------------------------ 5. the per-frame and fused calls
+# snowtri_triangulate, snowtri_condense, snowtri_condense_resident and the fused call choose how a host call's arrays travel from
+# its byte totals (snowtri.hip): one copy per array above kPinnedMaxBytes in either direction ("direct"), one page-locked block each
+# way up to that ("page-locked"), and -- snowtri_triangulate and snowtri_condense_resident only -- kernels that read and write mapped
+# page-locked memory while inputs plus outputs stay within kZeroCopyMaxBytes ("mapped").  Each case states the totals it computes
+# and the route it means to reach; the library's own totals differ by the padding between arrays, tens of bytes.  (The one-launch
+# kernel of the mapped snowtri_triangulate is not the device call's pair of kernels, but takes a slot's mean in their order: same bits.)
+PINNED_MAX = 4 << 20                           # kPinnedMaxBytes
+MAPPED_MAX = 256 << 10                         # kZeroCopyMaxBytes
+JF = 16                                        # joints = keypoint_num of the per-frame cases
+
+
+def _route(in_bytes, out_bytes, mapped):
+    if max(in_bytes, out_bytes) > PINNED_MAX:
+        return "direct"
+    return "mapped" if mapped and in_bytes + out_bytes <= MAPPED_MAX else "page-locked"
+
+
+def _twin_rig(C):
+    """The first C cameras of a ring of three whose camera 1 is camera 0 moved sideways: the same K and R, another centre, so that equal
+    pixels in the two are parallel rays bit for bit (a singular pair as snowtri_triangulate counts them)."""
+    from snowmocap_amd import synth
+    K, R, t = (a.copy() for a in synth.ring_rig(3))
+    K[1], R[1] = K[0], R[0]
+    t[1] = t[0] + R[0] @ np.array([0.4, 0.1, 0.0])
+    return K[:C], R[:C], t[:C]
+
+
+def _frames(seed, C, F, Pmax, J):
+    """float32 keypoints [F, C, Pmax, J, 3] and n_persons [F, C]; every fifth frame the last camera has a person fewer than Pmax."""
+    from snowmocap_amd import synth
+    rng = np.random.default_rng(seed)
+    kpts, n_persons = synth.make_keypoints(rng, *_twin_rig(C), synth.make_people(rng, F, Pmax, J=J), pixel_sigma=0.8)
+    n_persons[2::5, C - 1] = Pmax - 1
+    return kpts, n_persons
+
+
+def _with_parallel_rays(kpts):
+    """One joint of the second frame (the only one of a single frame) at the same pixel in cameras 0 and 1."""
+    bad = kpts.copy()
+    f, j = min(1, bad.shape[0] - 1), bad.shape[3] // 2
+    bad[f, 0, 0, j, :2] = bad[f, 1, 0, j, :2]
+    return bad
+
+
+def _params(**over):
+    from snowmocap_amd import synth
+    return _lib.make_params(**dict(synth.default_thresholds(), keypoint_num=JF, center_point_index=0, **over))
+
+
+APART = dict(condense_distance_tol=1e-9)       # no two candidates merge: three candidates of a frame are two persons (the last never seeds)
+
+
+class frame_ctx:
+    def __init__(self, C):
+        self.C = C
+
+    def __enter__(self):
+        assert _lib.lib().snowtri_device_count() > 0, "these tests need the HIP device"
+        assert _lib.build_info()["variants"] == [], "the production library only"
+        self.ctx = _lib.Context(*_twin_rig(self.C))
+        return self.ctx
+
+    def __exit__(self, *exc):
+        self.ctx.close()
+
+
+def triangulate(ctx, M, kpts, n_persons, prm, status=_lib.OK):
+    F, C, Pmax, J, _ = kpts.shape
+    Kc = int(ctx.L.snowtri_num_candidate_slots(C, Pmax))
+    # the host call defines the slots nobody fills as zeros; the device call leaves them alone, so it starts from zeros
+    fresh = M.out if M is Host else (lambda shape, dtype: M.put(np.zeros(shape, dtype)))
+    dk, dn = M.put(kpts), M.put(n_persons)
+    o = fresh((F, Kc, J, 3), np.float64), fresh((F, Kc, J), np.float64), fresh((F, Kc), np.float64), fresh((F, Kc), np.uint8)
+    rc = ctx.L.snowtri_triangulate(ctx.handle, F, Pmax, J, M.ptr(dk), _lib.dtype_code(kpts.dtype), M.ptr(dn), prm,
+                                   *(M.ptr(a) for a in o), M.code, None)
+    assert rc == status, f"snowtri_triangulate: status {rc}, not {status} [{_lib.lib().snowtri_last_error().decode()}]"
+    return tuple(M.get(a) for a in o)
+
+
+def _condensed(M, F, Pout, flags):
+    return (M.out((F, Pout, JF, 3), np.float64), M.out((F, Pout, JF), np.float64), M.out((F, Pout), np.float64), M.out((F,), np.int32),
+            M.out((F,), np.uint32) if flags else None)
+
+
+def condense(ctx, M, cand, prm, Pout, keep=True, flags=True, status=_lib.OK):
+    xyz, ks, _, kept = cand
+    F, N, J = ks.shape
+    dx, dk, dkeep = M.put(xyz), M.put(ks), M.put(kept if keep else None)
+    o = _condensed(M, F, Pout, flags)
+    rc = ctx.L.snowtri_condense(ctx.handle, F, N, J, M.ptr(dx), M.ptr(dk), M.ptr(dkeep), prm, Pout, *(M.ptr(a) for a in o), M.code, None)
+    assert rc == status, f"snowtri_condense: status {rc}, not {status}"
+    return tuple(None if a is None else M.get(a) for a in o)
+
+
+def condense_resident(ctx, F, prm, Pout, flags=True, status=_lib.OK):
+    o = _condensed(Host, F, Pout, flags)
+    token = int(ctx.L.snowtri_candidates_token(ctx.handle))
+    assert token != 0, "the host call has left its candidates on the device"
+    rc = ctx.L.snowtri_condense_resident(ctx.handle, token, prm, Pout, *(Host.ptr(a) for a in o))
+    assert rc == status, f"snowtri_condense_resident: status {rc}, not {status}"
+    return o
+
+
+def fused(ctx, M, kpts, n_persons, prm, Pout, out_dtype, pscore=True, flags=True, robust=False, diagnostics=False):
+    """-> status, snowtri_last_slow_frames, (xyzs, pscore, count, flags, views, resid)"""
+    F, C, Pmax, J, _ = kpts.shape
+    dk, dn = M.put(kpts), M.put(n_persons)
+    o = (M.out((F, Pout, JF, 4), out_dtype), M.out((F, Pout), out_dtype) if pscore else None, M.out((F,), np.int32),
+         M.out((F,), np.uint32) if flags else None,
+         M.out((F, JF), np.uint32) if diagnostics else None, M.out((F, JF), out_dtype) if diagnostics else None)
+    p = [M.ptr(a) for a in o]
+    codes = _lib.dtype_code(kpts.dtype), _lib.dtype_code(out_dtype)
+    if robust:
+        rc = ctx.L.snowtri_triangulate_robust(ctx.handle, F, J, M.ptr(dk), codes[0], M.ptr(dn), prm, 6.0, 1, Pout, p[0], p[1], codes[1], p[2], p[3],
+                                              p[4], p[5], M.code, None)
+    else:
+        assert not diagnostics
+        rc = ctx.L.snowtri_triangulate_condense(ctx.handle, F, Pmax, J, M.ptr(dk), codes[0], M.ptr(dn), prm, _lib.PAIRWISE, Pout, p[0], p[1], codes[1],
+                                                p[2], p[3], M.code, None)
+    return rc, ctx.last_slow_frames(), tuple(None if a is None else M.get(a) for a in o)
+
+
+def _status_of(flags):
+    any_ = int(np.bitwise_or.reduce(flags))
+    return _lib.ERR_SINGULAR if any_ & _lib.FLAG_SINGULAR else _lib.ERR_OVERFLOW if any_ & _lib.FLAG_OVERFLOW else _lib.OK
+
+
+def _triangulate_bytes(C, Pmax, J, F):
+    Kc = C * (C - 1) // 2 * Pmax * Pmax
+    return F * (C * Pmax * J * 3 * 4 + C * 4), F * Kc * (J * 4 * 8 + 8 + 1) + 8      # keypoints + n_persons | xyz, kscore, pscore, keep + the counter
+
+
+def _resident_bytes(F, Pout):
+    return F * (Pout * JF * 4 * 8 + Pout * 8 + 4)                                  # xyz, kscore | pscore | count
+
+
+TRIANGULATE_CASES = [
+    # C, Pmax, J, F: (input bytes, candidate bytes) -> route
+    (3, 1, JF, 32, "mapped"),                  # 18 816 + 50 024 = 67 KiB: the one-launch kernel
+    (3, 1, JF, 200, "page-locked"),            # 117 600 + 312 608 = 420 KiB
+    (3, 1, JF, 2800, "direct"),                # 1 646 400 | 4 376 408: the candidates are above 4 MiB
+    (2, 1, 4097, 1, "mapped"),                 # 98 336 + 131 121 = 224 KiB; J > 4096: k_triangulate + k_cand_mean, both mirrored
+    (2, 2, 1, 1025, "mapped"),                 # 57 400 + 168 108 = 220 KiB; F * Kc = 4100 > 4096: the same two launches
+]
+
+
+@pytest.mark.parametrize("C,Pmax,J,F,route", TRIANGULATE_CASES)
+def test_triangulate_host_equals_device_on_every_route(C, Pmax, J, F, route):
+    assert _route(*_triangulate_bytes(C, Pmax, J, F), mapped=True) == route
+    kpts, n_persons = _frames(30 + F, C, F, Pmax, J)
+    prm = _params()
+    with frame_ctx(C) as ctx:
+        want = triangulate(ctx, Device, kpts, n_persons, prm)
+        assert want[3].any() and (F == 1 or not want[3].all()), "kept candidates, and slots no pair of persons fills"
+        _same(triangulate(ctx, Host, kpts, n_persons, prm), want, f"snowtri_triangulate, {route}")
+        # a pair of parallel rays: counted on every route, and the counter is back at zero for the next call
+        bad = _with_parallel_rays(kpts)
+        want_bad = triangulate(ctx, Device, bad, n_persons, prm)
+        _same(triangulate(ctx, Host, bad, n_persons, prm, status=_lib.ERR_SINGULAR), want_bad, f"snowtri_triangulate with parallel rays, {route}")
+        _same(triangulate(ctx, Host, kpts, n_persons, prm), want, f"snowtri_triangulate after the singular call, {route}")
+
+
+@pytest.mark.parametrize("F,route", [(32, "mapped"), (200, "page-locked"), (2800, "direct")])
+def test_condense_resident_equals_condense_on_device_pointers(F, route):
+    Pout = 3
+    assert _route(0, _resident_bytes(F, Pout), mapped=True) == route     # 50 048 | 312 800 | 4 379 200 bytes of outputs
+    kpts, n_persons = _frames(30 + F, 3, F, 1, JF)
+    with frame_ctx(3) as ctx:
+        cand = triangulate(ctx, Device, kpts, n_persons, _params())
+        for prm, pout, status in ((_params(), Pout, _lib.OK), (_params(**APART), 1, _lib.ERR_OVERFLOW)):
+            want = condense(ctx, Device, cand, prm, pout)
+            assert want[3].max() >= 1 and (want[3].max() > pout) == (status == _lib.ERR_OVERFLOW)
+            assert np.array_equal(want[4], np.where(want[3] > pout, _lib.FLAG_OVERFLOW, 0))
+            for flags in (True, False):
+                triangulate(ctx, Host, kpts, n_persons, prm)
+                got = condense_resident(ctx, F, prm, pout, flags=flags, status=status)
+                _same(got, want[:4] + ((want[4],) if flags else (None,)), f"snowtri_condense_resident, {route}, Pout_max {pout}, flags {flags}")
+
+
+@pytest.mark.parametrize("F,route", [(64, "page-locked"), (2800, "direct")])
+def test_condense_host_equals_device_on_both_routes(F, route):
+    Pout = 3
+    assert _route(F * 3 * (JF * 4 * 8 + 1), _resident_bytes(F, Pout) + 4 * F, mapped=False) == route   # inputs: 98 496 | 4 309 200 bytes
+    kpts, n_persons = _frames(40 + F, 3, F, 1, JF)
+    with frame_ctx(3) as ctx:
+        cand = triangulate(ctx, Device, kpts, n_persons, _params())
+        for keep in (True, False):
+            for flags in (True, False):
+                _same(condense(ctx, Host, cand, _params(), Pout, keep, flags), condense(ctx, Device, cand, _params(), Pout, keep, flags),
+                      f"snowtri_condense, {route}, cand_keep {keep}, out_flags {flags}")
+        want = condense(ctx, Device, cand, _params(**APART), 1)
+        assert (want[4] == _lib.FLAG_OVERFLOW).any()
+        _same(condense(ctx, Host, cand, _params(**APART), 1, status=_lib.ERR_OVERFLOW), want, f"snowtri_condense, {route}, overflow")
+
+
+@pytest.mark.parametrize("out_dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("F,route", [(64, "page-locked"), (8000, "direct")])
+@pytest.mark.parametrize("robust", [False, True])
+def test_fused_calls_host_equal_device_on_both_routes(robust, F, route, out_dtype):
+    Pout = 2
+    osz = np.dtype(out_dtype).itemsize
+    out_bytes = F * (Pout * JF * 4 * osz + Pout * osz + 8 + (JF * (4 + osz) if robust else 0))
+    assert _route(_triangulate_bytes(3, 1, JF, F)[0], out_bytes, mapped=False) == route      # inputs: 37 632 | 4 704 000 bytes
+    kpts, n_persons = _frames(50 + F, 3, F, 1, JF)
+    with frame_ctx(3) as ctx:
+        options = [dict(), dict(pscore=False), dict(flags=False)] + ([dict(diagnostics=True), dict(diagnostics=True, flags=False)] if robust else [])
+        _, _, full = fused(ctx, Device, kpts, n_persons, _params(), Pout, out_dtype, robust=robust, diagnostics=robust)
+        assert full[2].max() >= 1
+        for opt in options:
+            rc, slow, got = fused(ctx, Host, kpts, n_persons, _params(), Pout, out_dtype, robust=robust, **opt)
+            want = tuple(w if g is not None else None for g, w in zip(got, full))
+            _same(got, want, f"fused call, robust {robust}, {route}, {opt}")
+            assert rc == _status_of(full[3]), f"{opt}: status {rc}"
+            assert slow == int(((full[3] & _lib.FLAG_FASTPATH) == 0).sum()), f"{opt}: snowtri_last_slow_frames"
+        if not robust:                         # (one detection per camera is one person at the most on the robust route)
+            _, _, over = fused(ctx, Device, kpts, n_persons, _params(**APART), 1, out_dtype)
+            assert (over[3] & _lib.FLAG_OVERFLOW).any() and not (over[3] & _lib.FLAG_SINGULAR).any()
+            for opt in (dict(), dict(flags=False)):
+                rc, slow, got = fused(ctx, Host, kpts, n_persons, _params(**APART), 1, out_dtype, **opt)
+                _same(got, tuple(w if g is not None else None for g, w in zip(got, over)), f"fused call, overflow, {route}, {opt}")
+                assert rc == _lib.ERR_OVERFLOW and slow == int(((over[3] & _lib.FLAG_FASTPATH) == 0).sum())
+
+
+def test_per_frame_staging_survives_a_regrowth_of_every_buffer():
+    """Large, small, large on one context: the device scratch and the page-locked buffers are all sized before a base pointer is taken."""
+    prm = _params()
+    with frame_ctx(3) as ctx:
+        cases = {F: _frames(60 + F, 3, F, 1, JF) for F in (2800, 32)}
+        want = {F: triangulate(ctx, Device, *a, prm) for F, a in cases.items()}
+        condensed = {F: condense(ctx, Device, want[F], prm, 3) for F in cases}
+        big, small = _frames(70, 3, 8000, 1, JF), _frames(71, 3, 64, 1, JF)
+        fused_want = {id(a): fused(ctx, Device, *a, prm, 2, np.float64)[2] for a in (big, small)}
+        for step, (F, a) in enumerate(((2800, big), (32, small), (2800, big))):
+            _same(triangulate(ctx, Host, *cases[F], prm), want[F], f"snowtri_triangulate, call {step + 1} of large / small / large")
+            _same(condense_resident(ctx, F, prm, 3), condensed[F], f"snowtri_condense_resident, call {step + 1}")
+            _same(condense(ctx, Host, want[F], prm, 3), condensed[F], f"snowtri_condense, call {step + 1}")
+            _same(fused(ctx, Host, *a, prm, 2, np.float64)[2], fused_want[id(a)], f"fused call, call {step + 1}")
