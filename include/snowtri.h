@@ -618,6 +618,47 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
                            double keypoint_score_threshold, uint32_t flags, double *cost_sum, int32_t *cost_n, int memspace,
                            void *stream);
 
+/* Assignment: the optimal ONE-TO-ONE matching of a camera's detections to the 3D persons, on the costs snowtri_reproject_cost wrote
+ * (no reference counterpart).  Picking each person's cheapest detection on its own lets two persons claim one detection -- one
+ * behind the other in a view, a ghost beside a real person -- and everything built on the match then pulls both towards the same 2D
+ * skeleton.  The rule, in fp64, per problem i < n (one frame and camera: n = F * C, the layout of snowtri_reproject_cost consumed
+ * unchanged) with P persons (rows), Pmax detections (columns) and gate2 = gate_px * gate_px:
+ *   1. mean[p][q] = cost_sum[i][p][q] / cost_n[i][p][q], one correctly rounded division.  The pair (p, q) is ADMISSIBLE iff
+ *      cost_n >= min_joints, the mean is not NaN and -inf < mean <= gate2; every other pair costs +inf.  (A detection behind
+ *      n_persons[f][c] has cost_n == 0 already: n_persons is no input.)
+ *   2. Staying unmatched costs gate2: the cost matrix is a[P][Pmax + P], columns q < Pmax hold the means, column Pmax + p is person
+ *      p's private dummy (gate2 in row p, +inf elsewhere).  A perfect matching of the rows always exists; the rule returns one of
+ *      minimum sum, and a person on its dummy is unmatched.  Two persons that both fit detection 0 get detections 0 and 1 if the
+ *      second fits either of them inside the gate, otherwise the worse-fitting one goes unmatched: the standard gated assignment.
+ *   3. WHICH optimum is fixed by the algorithm, the shortest-augmenting-path (Hungarian / Jonker-Volgenant) method in its textbook
+ *      form: rows inserted in order p = 0, 1, ..., duals u (rows) and v (columns), all 0 at the start.  Inserting row i: minv[j] =
+ *      +inf, no column used, j0 = a virtual column holding row i; then, until j0 is a column without a row: mark j0 used, i0 = its
+ *      row; for the unused columns j in increasing order cur = (a[i0][j] - u[i0]) - v[j], in that order; if cur < minv[j] then
+ *      minv[j] = cur and way[j] = j0; if minv[j] < delta (+inf at the start of the scan) then delta = minv[j], j1 = j -- both
+ *      comparisons strict, so ties go to the lowest column; then u of every used column's row += delta and its v -= delta, every
+ *      other minv -= delta, j0 = j1.  At the end the columns along way[] from j0 back to the virtual one each take the row of the
+ *      column before them.  Only additions, subtractions and comparisons of fp64 values: there is no product that could contract
+ *      into a fused multiply-add, +inf never meets -inf, and delta is always finite (row i's own dummy, at the finite gate2, is outside the tree).
+ *   4. det_of[i][p] = the detection of person p or -1; person_of[i][q] = the person that took detection q or -1 (the detections
+ *      nobody claimed); total[i] = the sum of mean over the matched pairs, added in increasing p with plain additions from 0.
+ * snowmocap_amd/reproject.py::assign_detections_reference is this rule in NumPy, and the kernel (snowmocap_amd/csrc/snowtri_assign.hpp,
+ * k_assign: a lane is a column, delta by a butterfly on the pair (minv, column), whose minimum is exact in any order) performs the
+ * same operations on the same values: EVERY OUTPUT AGREES WITH IT BIT FOR BIT, the integers and the bits of total.  A problem's
+ * output depends on its own P x Pmax costs, gate_px and min_joints only: not on n, its place in the launch, the problems packed into
+ * the same wave (64 / W of them, W = the smallest of 8, 16, 32, 64 >= P + Pmax) or how a batch is cut into calls.
+ *
+ * person_of and total may be NULL (not wanted).  Refusals (SNOWTRI_ERR_BAD_ARG, snowtri_last_error() names the argument; nothing is
+ * enqueued or written): a NULL context, an unknown memspace, n < 0, P or Pmax < 1, P + Pmax > 64 (a problem's columns are the lanes
+ * of one wave), min_joints < 1, a gate_px that is negative or NaN, a gate_px above 1e150 (rule 2 needs a finite cost of staying
+ * unmatched and the duals are sums of a few of them; the infinite gate that means "no gate" elsewhere is not offered here), a NULL
+ * cost_sum, cost_n or det_of, a device pointer that is not aligned to its element size, n * P * Pmax > 2^48, n > (2^31 - 1) * 4 * (64 / W) (the grid).  n == 0 is SNOWTRI_OK and looks at
+ * no pointer.  SNOWTRI_DEVICE: asynchronous on `stream`, no host read, no allocation, no internal stream.  SNOWTRI_HOST: staged and
+ * synchronous.  The context needs no cameras.  With snowtri_set_timing on, snowtri_last_kernel_ms gives k_assign's time in
+ * kernel_ms[0] (kernel_ms[1] is 0: there is no second phase). */
+int snowtri_assign_detections(snowtri_ctx *ctx, int64_t n, int32_t P, int32_t Pmax, const double *cost_sum, const int32_t *cost_n,
+                              double gate_px, int32_t min_joints, int32_t *det_of /* [n][P] */,
+                              int32_t *person_of /* [n][Pmax] or NULL */, double *total /* [n] or NULL */, int memspace, void *stream);
+
 /* Refinement: joint records of ANY route moved to a local minimum of their weighted reprojection error, in pixels (no reference
  * counterpart).  Every route ends in a closed-form estimate -- the score-weighted mean of two-ray midpoints (SNOWTRI_PAIRWISE), the
  * minimiser of an algebraic error (the DLT methods) -- and none of them minimises the distance between the joint's projections and

@@ -143,6 +143,8 @@ _SIGNATURES = {
     "snowtri_reproject": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_uint32, _c_p, ct.c_int, ct.c_int, _c_p]),
     "snowtri_reproject_cost": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p,
                                           ct.c_double, ct.c_uint32, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_assign_detections": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, _c_p, ct.c_double, ct.c_int32, _c_p, _c_p, _c_p,
+                                             ct.c_int, _c_p]),
     "snowtri_refine_joints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                          ct.c_double, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_pose_sweep_records": (ct.c_int, []),
@@ -458,6 +460,38 @@ class Context:
                                            float(keypoint_score_threshold), REPROJECT_RAW if raw else 0, ptr(cs), ptr(cn), *space.tail())
         self._reproject_status(rc, "snowtri_reproject_cost")
         return cs, cn
+
+    def assign_detections(self, cost_sum, cost_n, gate_px, min_joints=8, with_person_of=False, with_total=False, stream=None):
+        """The optimal one-to-one matching of detections to 3D persons per problem (include/snowtri.h, "Assignment"; k_assign):
+        cost_sum [..., P, Pmax] float64 and cost_n int32 of the same shape, as reproject_cost returns them (P + Pmax <= 64) ->
+        det_of [..., P] int32 (the detection of person p, -1: unmatched, which costs gate_px^2), then with_person_of: person_of
+        [..., Pmax] int32 (the person that took detection q, -1: nobody), with_total: total [...] float64 (the summed mean cost of the
+        matched pairs); one array, or a tuple in that order.  Host arrays, or contiguous CUDA tensors (both) used in place and
+        asynchronously on `stream`.  Every output equals reproject.assign_detections_reference bit for bit."""
+        space = Space("Context.assign_detections", cost_sum, cost_n, stream=stream)
+        if int(min_joints) != min_joints or int(min_joints) < 1:
+            raise ValueError("min_joints must be >= 1")
+        if not float(gate_px) >= 0.0:
+            raise ValueError("gate_px must be >= 0 and not NaN")
+        if not float(gate_px) <= 1e150:
+            raise ValueError("gate_px must not exceed 1e150 (staying unmatched costs gate_px^2, which must stay finite)")
+        if space.device is None:
+            cost_sum, cost_n = np.ascontiguousarray(cost_sum, dtype=np.float64), np.asarray(cost_n)
+        elif cost_sum.dtype != space.torch.float64 or not space._resident(cost_sum):
+            raise ValueError("cost_sum given to Context.assign_detections must be a contiguous float64 CUDA tensor")
+        if len(cost_sum.shape) < 2 or tuple(cost_sum.shape) != tuple(cost_n.shape):
+            raise ValueError("cost_sum and cost_n must both be [..., P, Pmax]")
+        cost_n = space.ints(cost_n, cost_sum.shape, "cost_n")
+        lead, P, Pmax = tuple(int(v) for v in cost_sum.shape[:-2]), int(cost_sum.shape[-2]), int(cost_sum.shape[-1])
+        n = int(np.prod(lead, dtype=np.int64))
+        det_of = space.empty(lead + (P,), "int32")
+        person_of = space.empty(lead + (Pmax,), "int32") if with_person_of else None
+        total = space.empty(lead, "float64") if with_total else None
+        rc = self.L.snowtri_assign_detections(self.handle, n, P, Pmax, ptr(cost_sum), ptr(cost_n), float(gate_px), int(min_joints), ptr(det_of),
+                                              ptr(person_of), ptr(total), *space.tail())
+        self._reproject_status(rc, "snowtri_assign_detections")
+        out = (det_of,) + ((person_of,) if with_person_of else ()) + ((total,) if with_total else ())
+        return out if len(out) > 1 else det_of
 
     def _refine_in(self, space, xyzs, kpts, n_persons, det_of, views, iters):
         """The inputs refine_joints and refine_cameras share, checked in `space` ->

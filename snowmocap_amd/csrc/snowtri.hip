@@ -33,6 +33,7 @@
 #include "snowtri_blender.hpp"
 #include "snowtri_undistort.hpp"
 #include "snowtri_reproject.hpp"
+#include "snowtri_assign.hpp"
 #include "snowtri_refine.hpp"
 #include "snowtri_pose.hpp"
 #include "snowtri_track.hpp"
@@ -2136,6 +2137,72 @@ int snowtri_reproject_cost(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
                            keypoint_score_threshold, (const double *)ctx->dProj, (const TX *)dx, (const TK *)dk, dnp, ds, dn);
     });
     HIP_TRY(hipGetLastError());
+    return sg.end();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------- assignment
+extern "C" {
+
+int snowtri_assign_detections(snowtri_ctx *ctx, int64_t n, int32_t P, int32_t Pmax, const double *cost_sum, const int32_t *cost_n, double gate_px,
+                              int32_t min_joints, int32_t *det_of, int32_t *person_of, double *total, int memspace, void *stream) {
+    const Refuse refuse{"snowtri_assign_detections"};
+    // (the context is looked at last: every other refusal names its argument with or without one)
+    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
+    if (n < 0) return refuse("n < 0");
+    if (P < 1 || Pmax < 1) return refuse("P < 1 or Pmax < 1");
+    if ((int64_t)P + Pmax > kAssignMaxColumns) return refuse("P + Pmax must not exceed 64 (the columns of a problem are the lanes of one wave)");
+    if (min_joints < 1) return refuse("min_joints < 1");
+    if (!(gate_px >= 0.0)) return refuse("gate_px must be >= 0 and not NaN");
+    // (staying unmatched costs gate_px^2: an infinite one leaves the rule without a finite column to fall back on, and the duals are
+    // sums of a few such costs: 1e300 leaves them room)
+    if (!(gate_px <= kAssignMaxGate)) return refuse("gate_px must not exceed 1e150 (staying unmatched costs gate_px^2, which must stay finite)");
+    // 64 / W problems per wave, four waves per workgroup on a one-dimensional grid; 64-bit element offsets
+    const int cols = P + Pmax, W = cols <= 8 ? 8 : cols <= 16 ? 16 : cols <= 32 ? 32 : 64;
+    const int64_t per_wg = (int64_t)kAssignWaves * (64 / W), pq = (int64_t)P * Pmax;
+    if (n > 0) {   // (n == 0 looks at no pointer)
+        if (n > ((int64_t)1 << 48) / pq) return refuse("n * P * Pmax must not exceed 2^48 costs");
+        if (n > (int64_t)0x7fffffff * per_wg) return refuse("n must not exceed (2^31 - 1) workgroups of 4 * (64 / W) problems");
+        if (!cost_sum || !cost_n || !det_of) return refuse("null array (cost_sum, cost_n or det_of)");
+        if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)cost_sum | (uintptr_t)total) & 7u) ||
+                                           (((uintptr_t)cost_n | (uintptr_t)det_of | (uintptr_t)person_of) & 3u)))
+            return refuse("cost_sum, cost_n, det_of, person_of and total must be aligned to their element size");
+    }
+    if (!ctx) return refuse("null context");
+    if (n == 0) return SNOWTRI_OK;
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const double *ds = cost_sum;
+    const int32_t *dn = cost_n;
+    int32_t *dd = det_of, *dp = person_of;
+    double *dt = total;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&ds, sizeof(double) * (size_t)(n * pq));
+    sg.in(&dn, sizeof(int32_t) * (size_t)(n * pq));
+    sg.out(&dd, sizeof(int32_t) * (size_t)n * P);
+    sg.out(&dp, sizeof(int32_t) * (size_t)n * Pmax);
+    sg.out(&dt, sizeof(double) * (size_t)n);
+    if (int rc = sg.begin()) return rc;
+    const dim3 grid((unsigned)((n + per_wg - 1) / per_wg));
+    const double gate2 = gate_px * gate_px;
+    auto launch = [&](auto w) {   // w: the sub-wave width the kernel is compiled for, as a std::integral_constant
+        hipLaunchKernelGGL((k_assign<decltype(w)::value>), grid, dim3(64 * kAssignWaves), 0, st, n, (int)P, (int)Pmax, gate2, (int)min_joints, ds, dn,
+                           dd, dp, dt);
+    };
+    if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0], st));   // snowtri_set_timing: the kernel between the pair snowtri_last_kernel_ms reads
+    if (W == 8) launch(std::integral_constant<int, 8>());
+    else if (W == 16) launch(std::integral_constant<int, 16>());
+    else if (W == 32) launch(std::integral_constant<int, 32>());
+    else launch(std::integral_constant<int, 64>());
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) {
+        HIP_TRY(hipEventRecord(ctx->ev[1], st));
+        HIP_TRY(hipEventRecord(ctx->ev[2], st));   // (no second phase: the pair (2, 3) is empty)
+        HIP_TRY(hipEventRecord(ctx->ev[3], st));
+        ctx->ev_valid = true;
+        ctx->ev_stream = st;
+    }
     return sg.end();
 }
 

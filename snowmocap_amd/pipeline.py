@@ -41,7 +41,7 @@ class TrackPipeline:
         self.bt.close()
 
     def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0, despike=None,
-            reproject=None, refine=None):
+            reproject=None, refine=None, one_to_one=False):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -95,16 +95,39 @@ class TrackPipeline:
         False) to find the detection of each camera that shows each person, refine_joints with that det_of and the pipeline's
         keypoint_score_threshold.  With D the triangulator's own undistorted copy of the keypoints is reused (no second k_undistort
         pass).  Adds refine_codes [F, P, kn] (uint8, refine.REFINE_*) and refine_cost [F, P, kn, 2] (px^2 before and after), both in
-        the triangulation's list order.  None (the default): off, nothing changes and no key is added."""
-        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, refine_args(refine))
+        the triangulation's list order.  None (the default): off, nothing changes and no key is added.
+        one_to_one=True: the matching step of reproject= and of refine= is reproject.assign_detections (k_assign: the optimal
+        assignment per frame and camera with the same gate, at most one person per detection) instead of match_detections.  A person
+        whose only detections inside the gate went to persons they fit better is then unmatched in that view (det_of -1) instead of
+        sharing one; with reproject=, shared -- still computed from det_of by the same expression -- is all False and person_of
+        [F, C, Pmax] is added (the person that took detection q, -1: a detection nobody claimed).  It needs reproject or refine
+        (ValueError otherwise), and gates of at most 1e150 px: staying unmatched costs gate_px^2, so the infinite gate that
+        match_detections reads as "no gate" is refused.  False (the default): nothing changes."""
+        if one_to_one and reproject is None and refine is None:
+            raise ValueError("one_to_one=True needs reproject= or refine=: it chooses how their matching step pairs persons and detections")
+        one_to_one, rfn = bool(one_to_one), refine_args(refine)
+        if one_to_one:                                     # before any work: the assignment needs a finite gate (<= 1e150)
+            from .reproject import assign_gate
+            for gate in ([reproject] if reproject is not None else []) + ([rfn[1]] if rfn else []):
+                assign_gate(gate)
+        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn, one_to_one)
         if reproject is not None:
-            self._add_reprojection(res, kpts, n_persons, float(reproject))
+            self._add_reprojection(res, kpts, n_persons, float(reproject), one_to_one)
         return res
 
-    def _add_reprojection(self, res, kpts, n_persons, gate_px):
+    def _match(self, cost_sum, cost_n, gate_px, one_to_one):
+        """The matching step of run(reproject=..., refine=...) -> (det_of, shared, person_of or None)."""
+        from .reproject import assign_detections, match_detections
+        if not one_to_one:
+            return match_detections(cost_sum, cost_n, gate_px) + (None,)
+        det_of, person_of = assign_detections(self.bt.ctx, cost_sum, cost_n, gate_px, with_person_of=True)
+        same = (det_of[..., :, None] == det_of[..., None, :]) & (det_of[..., :, None] >= 0)
+        return det_of, same.sum(dim=-1) > 1, person_of
+
+    def _add_reprojection(self, res, kpts, n_persons, gate_px, one_to_one=False):
         """run(reproject=gate_px): res["xyzs"] against the keypoints the caller passed (on the raw frame when the pipeline has D)."""
         import torch
-        from .reproject import match_detections, view_residuals
+        from .reproject import view_residuals
         dev = torch.device("cuda", self.device)
         if not torch.is_tensor(kpts):
             kpts = torch.from_numpy(np.ascontiguousarray(kpts)).to(dev)
@@ -119,14 +142,15 @@ class TrackPipeline:
         xyzs = res["xyzs"].contiguous()
         ctx, raw, thr = self.bt.ctx, self.bt.undistort, float(self.th["keypoint_score_threshold"])
         cost_sum, cost_n = ctx.reproject_cost(xyzs, kpts, n_persons=n_persons, keypoint_score_threshold=thr, raw=raw)
-        res["det_of"], res["shared"] = match_detections(cost_sum, cost_n, gate_px)
+        res["det_of"], res["shared"], person_of = self._match(cost_sum, cost_n, gate_px, one_to_one)
+        if person_of is not None:
+            res["person_of"] = person_of
         pix = ctx.reproject(xyzs, raw=raw, dtype=torch.float64)
         _, res["view_rms"], res["view_n"] = view_residuals(pix, kpts, res["det_of"], thr)
 
-    def _refine(self, xyzs, n_persons, rfn):
+    def _refine(self, xyzs, n_persons, rfn, one_to_one=False):
         """run(refine=...): the triangulated records against the undistorted keypoints of the call that made them
         -> (refined records, cost, codes)."""
-        from .reproject import match_detections
         iters, gate_px, score_weights = rfn
         ukpts = self.bt.last_undistorted_kpts
         if int(ukpts.shape[3]) != self.kn:                # the joints the triangulation kept are the first kn of a detection
@@ -134,11 +158,11 @@ class TrackPipeline:
         ctx, thr = self.bt.ctx, float(self.th["keypoint_score_threshold"])
         xyzs = xyzs.contiguous()
         cost_sum, cost_n = ctx.reproject_cost(xyzs, ukpts, n_persons=n_persons, keypoint_score_threshold=thr)
-        det_of, _ = match_detections(cost_sum, cost_n, gate_px)
+        det_of = self._match(cost_sum, cost_n, gate_px, one_to_one)[0]
         return ctx.refine_joints(xyzs, ukpts, det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr, iters=iters,
                                  score_weights=score_weights, diagnostics=True)
 
-    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None):
+    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None, one_to_one=False):
         """run() without its reprojection keys."""
         dsp = despike_args(despike)
         import torch
@@ -166,7 +190,7 @@ class TrackPipeline:
                 tracked = np.minimum(cnt, int(cnt[0]) if F else 0).astype(np.int32)
         xyzs = tri["xyzs"]
         if rfn:
-            xyzs, refine_cost, refine_codes = self._refine(xyzs, n_persons, rfn)
+            xyzs, refine_cost, refine_codes = self._refine(xyzs, n_persons, rfn, one_to_one)
         th = self.th
         fzrd =(float(th["smooth_f"]), float(th["smooth_z"]), float(th["smooth_r"]), float(th["smooth_delta_time"]))
         fill_gaps = int(fill_gaps)

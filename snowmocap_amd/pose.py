@@ -230,6 +230,10 @@ class _LibrarySteps:
     def cost(self, xyzs, kpts, n_persons, thr):
         return self.ctx.reproject_cost(xyzs, kpts, n_persons=n_persons, keypoint_score_threshold=thr)
 
+    def assign(self, cost_sum, cost_n, gate_px, min_joints):
+        from .reproject import assign_detections
+        return assign_detections(self.ctx, cost_sum, cost_n, gate_px, min_joints)
+
     def pixels(self, xyzs):
         return self.ctx.reproject(xyzs, dtype=np.float64)
 
@@ -256,6 +260,10 @@ class _ReferenceSteps:
         from .reproject import reprojection_cost_reference
         return reprojection_cost_reference(*self.rig, xyzs, kpts, n_persons=n_persons, keypoint_score_threshold=thr)
 
+    def assign(self, cost_sum, cost_n, gate_px, min_joints):
+        from .reproject import assign_detections_reference
+        return assign_detections_reference(cost_sum, cost_n, gate_px, min_joints)[0]
+
     def pixels(self, xyzs):
         from .reproject import reproject_reference
         return reproject_reference(*self.rig, xyzs)
@@ -269,7 +277,8 @@ class _ReferenceSteps:
 
 
 def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.DLT, params=None, persons=None, gate_px=12.0,
-               min_joints=8, joint_iters=4, camera_iters=8, min_obs=64, score_weights=False, triangulate=None, reference=False):
+               min_joints=8, joint_iters=4, camera_iters=8, min_obs=64, score_weights=False, triangulate=None, reference=False,
+               one_to_one=False):
     """Block-coordinate bundle adjustment of the extrinsics: `rounds` times triangulate on the current rig, match the detections to the
     3D persons (reprojection_cost + match_detections, gate_px), refine the joints (refine_joints, joint_iters), refine the free cameras
     (refine_cameras, camera_iters, min_obs), and build a new context from the result.  Host arrays: kpts [F, C, Pmax, kn, 3] on the
@@ -285,6 +294,9 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
     by 4 cm, its ray pairs fall outside distance_threshold or form a second cluster, and on the two-person recipe the alternation
     did not repair it (EXPERIMENTS.md).  triangulate(K, R, t, kpts, n_persons) -> xyzs [F, P, kn, 4]
     replaces the BatchTriangulator; reference=True runs every other step by its NumPy rule (no GPU; needs `triangulate`).
+    one_to_one=True: the matching step is the optimal one-to-one assignment (reproject.assign_detections, k_assign; with reference=True
+    its NumPy rule assign_detections_reference) instead of match_detections, with the same gate_px and min_joints; gate_px must
+    then not exceed 1e150, since staying unmatched costs gate_px^2 (ValueError before any work).
 
     -> (R [C, 3, 3], t [C, 3], history): history[r] = dict(overflow_frames: the frames in which the library's triangulation found
     more clusters than `persons` and dropped some (0 with the caller's `triangulate`), view_rms [C]: each camera's RMS pixel residual over its matched views
@@ -309,6 +321,9 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
     if params is None:
         params = dict(keypoint_num=kn, center_point_index=min(18, kn - 1))
     thr = float(params.get("keypoint_score_threshold", 0.5)) if isinstance(params, dict) else float(params.keypoint_score_threshold)
+    if one_to_one:
+        from .reproject import assign_gate
+        assign_gate(gate_px)
     if reference and triangulate is None:
         raise ValueError("refine_rig: reference=True needs `triangulate` (the library's triangulation runs on the GPU)")
     steps = _ReferenceSteps(triangulate) if reference else _LibrarySteps(method, params, P)
@@ -319,7 +334,10 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
 
     def measure(xyzs):
         cs, cn = steps.cost(xyzs, kpts, n_persons, thr)
-        det_of, _ = match_detections(np.asarray(cs), np.asarray(cn), gate_px, min_joints)
+        if one_to_one:
+            det_of = np.asarray(steps.assign(np.asarray(cs), np.asarray(cn), gate_px, min_joints))
+        else:
+            det_of, _ = match_detections(np.asarray(cs), np.asarray(cn), gate_px, min_joints)
         resid = view_residuals(steps.pixels(xyzs), kpts, det_of, thr)[0]                   # [F, C, P, kn], NaN where nothing counts
         r2 = np.moveaxis(np.asarray(resid) ** 2, 1, 0).reshape(C, -1)
         with np.errstate(all="ignore"):

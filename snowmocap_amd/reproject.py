@@ -5,7 +5,8 @@ NumPy, plain operations in its order (no fused multiply-add, the cost summed in 
 k_reproject_cost (snowmocap_amd/csrc/snowtri_reproject.hpp) are tested against.  `reproject` and `reprojection_cost` run the
 kernels.  `match_detections` and `view_residuals` are the few lines of tensor code on top: which detection of camera c belongs to
 3D person p, and how far each of its joints lies from the projection.  They take NumPy arrays, or torch tensors on their own
-device without a host round trip.
+device without a host round trip.  `assign_detections` is match_detections' one-to-one counterpart: the optimal gated assignment per
+(frame, camera), run by the kernel k_assign (snowmocap_amd/csrc/snowtri_assign.hpp), which equals `assign_detections_reference` bit for bit.
 """
 from __future__ import annotations
 
@@ -155,6 +156,124 @@ def match_detections(cost_sum, cost_n, gate_px, min_joints=8):
     return det_of, same.sum(axis=-1) > 1
 
 
+def assign_gate(gate_px):
+    """The gate of the one-to-one assignment, checked -> float.  match_detections reads an infinite gate as "no gate"; here staying
+    unmatched COSTS gate_px^2, and the rule needs that cost, and the duals summed from it, finite: a gate_px above 1e150 is refused."""
+    if not float(gate_px) >= 0.0:
+        raise ValueError("gate_px must be >= 0 and not NaN")
+    if not float(gate_px) <= 1e150:
+        raise ValueError("gate_px must not exceed 1e150 (staying unmatched costs gate_px^2, which must stay finite; match_detections takes an infinite gate)")
+    return float(gate_px)
+
+
+def _assign_args(cost_sum, cost_n, gate_px, min_joints):
+    """The checks assign_detections and its reference share, in match_detections' words -> (gate_px, min_joints)."""
+    if int(min_joints) != min_joints or int(min_joints) < 1:
+        raise ValueError("min_joints must be >= 1")
+    assign_gate(gate_px)
+    if tuple(cost_sum.shape) != tuple(cost_n.shape) or len(cost_sum.shape) != 4:
+        raise ValueError("cost_sum and cost_n must both be [F, C, P, Pmax]")
+    if int(cost_sum.shape[2]) < 1 or int(cost_sum.shape[3]) < 1 or int(cost_sum.shape[2]) + int(cost_sum.shape[3]) > 64:
+        raise ValueError("assign_detections needs P >= 1, Pmax >= 1 and P + Pmax <= 64")
+    return float(gate_px), int(min_joints)
+
+
+def _assign_one(a, P, Pmax):
+    """Rule 3 on one augmented matrix a [P, Pmax + P] -> the row of every column (-1: none).  The column scan of a step is written
+    on whole NumPy rows: the same IEEE operation per column as the scalar loop, and argmin returns the FIRST least element, which is
+    what the strict `minv[j] < delta` of a scan in increasing j keeps."""
+    m = Pmax + P
+    inf = np.inf
+    u, v = np.zeros(P), np.zeros(m)
+    row_of = np.full(m, -1, dtype=np.int64)
+    for i in range(P):
+        minv = np.full(m, inf)
+        way = np.full(m, -1, dtype=np.int64)
+        used = np.zeros(m, dtype=bool)
+        j0, i0 = -1, i                                     # -1: the virtual column that holds row i
+        while True:
+            if j0 >= 0:
+                used[j0] = True
+            cur = (a[i0] - u[i0]) - v
+            low = ~used & (cur < minv)
+            minv[low] = cur[low]
+            way[low] = j0
+            j1 = int(np.argmin(np.where(used, inf, minv)))
+            delta = minv[j1]
+            if used[j1] or not delta < inf:                # (no finite column outside the tree: unreachable with a finite gate2 --
+                j0 = -1                                    # row i's own dummy is one; the row is then left unmatched, as in k_assign)
+                break
+            rows = row_of[used]                            # the tree's rows: those of the used columns, and row i
+            u[rows] = u[rows] + delta
+            u[i] = u[i] + delta
+            v[used] = v[used] - delta
+            minv[~used] = minv[~used] - delta
+            j0 = j1
+            if row_of[j0] < 0:
+                break
+            i0 = int(row_of[j0])
+        while j0 >= 0:
+            j1 = int(way[j0])
+            row_of[j0] = row_of[j1] if j1 >= 0 else i
+            j0 = j1
+    return row_of
+
+
+def assign_detections_reference(cost_sum, cost_n, gate_px, min_joints=8):
+    """The rule of include/snowtri.h ("Assignment") in NumPy: cost_sum, cost_n [F, C, P, Pmax] (reprojection_cost's) ->
+    det_of [F, C, P] int64 (the detection of person p, or -1), person_of [F, C, Pmax] int64 (the person that took detection q, or
+    -1) and total [F, C] float64.  Per (f, c): mean = cost_sum / cost_n, admissible iff cost_n >= min_joints, not NaN and
+    -inf < mean <= gate_px^2 (match_detections' per-pair condition), +inf otherwise; one dummy column per person at gate_px^2 (staying
+    unmatched); then the shortest-augmenting-path method with rows inserted in order, cur = (a[i0][j] - u[i0]) - v[j], both
+    comparisons strict (ties to the lowest column).  The result is a minimum-sum ONE-TO-ONE matching, and the one k_assign returns
+    bit for bit; total adds the matched means in increasing p."""
+    gate_px, min_joints = _assign_args(cost_sum, cost_n, gate_px, min_joints)
+    gate2 = gate_px * gate_px
+    cs, cn = np.asarray(cost_sum, dtype=np.float64), np.asarray(cost_n)
+    F, C, P, Pmax = cs.shape
+    with np.errstate(all="ignore"):
+        mean = cs / cn.astype(np.float64)
+        ok = (cn >= min_joints) & ~np.isnan(mean) & (mean <= gate2) & (mean > -np.inf)
+    mean = np.where(ok, mean, np.inf)
+    det_of = np.full((F, C, P), -1, dtype=np.int64)
+    person_of = np.full((F, C, Pmax), -1, dtype=np.int64)
+    total = np.zeros((F, C))
+    a = np.full((P, Pmax + P), np.inf)
+    a[np.arange(P), Pmax + np.arange(P)] = gate2
+    for f in range(F):
+        for c in range(C):
+            a[:, :Pmax] = mean[f, c]
+            row_of = _assign_one(a, P, Pmax)
+            acc = 0.0
+            for q in range(Pmax):
+                if row_of[q] >= 0:
+                    det_of[f, c, row_of[q]] = q
+                    person_of[f, c, q] = row_of[q]
+            for p in range(P):
+                if det_of[f, c, p] >= 0:
+                    acc = acc + mean[f, c, p, det_of[f, c, p]]
+            total[f, c] = acc
+    return det_of, person_of, total
+
+
+def assign_detections(ctx, cost_sum, cost_n, gate_px, min_joints=8, with_person_of=False, with_total=False, stream=None):
+    """k_assign through a context (Context.assign_detections; any context, the rig is not used): cost_sum, cost_n [F, C, P, Pmax] ->
+    det_of [F, C, P] in match_detections' dtype (int64), so it drops into view_residuals, refine_joints and refine_cameras unchanged
+    -- but ONE-TO-ONE: no two persons of an (f, c) hold the same detection, and a person is left at -1 when its only detections
+    inside the gate went to persons they fit better.  with_person_of: also person_of [F, C, Pmax] int64 (-1: a detection nobody
+    claimed), with_total: also total [F, C] float64; a tuple in that order.  NumPy arrays, or CUDA tensors without a host round trip."""
+    _assign_args(cost_sum, cost_n, gate_px, min_joints)
+    if _is_tensor(cost_sum):
+        import torch
+        cost_sum, cost_n, wide = cost_sum.to(torch.float64).contiguous(), cost_n.to(torch.int32).contiguous(), lambda a: a.to(torch.int64)
+    else:
+        wide = lambda a: a.astype(np.int64)    # noqa: E731
+    out = ctx.assign_detections(cost_sum, cost_n, gate_px, min_joints, with_person_of=with_person_of, with_total=with_total, stream=stream)
+    if not (with_person_of or with_total):
+        return wide(out)
+    return tuple(wide(a) if i < 1 + bool(with_person_of) else a for i, a in enumerate(out))
+
+
 def view_residuals(pix, kpts, det_of, keypoint_score_threshold):
     """pix [F, C, P, kn, 3] (reproject's output), kpts [F, C, Pmax, kn, 3], det_of [F, C, P] (match_detections) ->
     resid [F, C, P, kn] float64: the pixel distance between the projection of joint (p, j) and joint j of the detection person p was
@@ -197,5 +316,6 @@ def view_residuals(pix, kpts, det_of, keypoint_score_threshold):
     return resid, rms, n
 
 
-__all__ = ["reproject_reference", "reprojection_cost_reference", "reproject", "reprojection_cost", "match_detections", "view_residuals"]
+__all__ = ["reproject_reference", "reprojection_cost_reference", "reproject", "reprojection_cost", "match_detections", "view_residuals",
+           "assign_detections", "assign_detections_reference"]
 _ = _lib   # (the wrappers go through _lib.Context)
