@@ -771,6 +771,50 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
                            int64_t *n_obs /* [C] or NULL */, uint8_t *codes /* [C] or NULL */, double *normal /* [C][28] or NULL */,
                            int memspace, void *stream);
 
+/* Matched triangulation: the robust N-view DLT of 3D person p over the detections that det_of names (no reference counterpart).
+ * The matching chain -- snowtri_reproject_cost, snowtri_assign_detections -- ends in det_of[f][c][p], the detection of camera c that
+ * belongs to person p; this entry triangulates from that answer, so that a person is fused from EVERY view that saw it, with
+ * SNOWTRI_DLT_ROBUST's leave-one-out gate on each joint, and its `views` output is the mask snowtri_refine_joints and
+ * snowtri_refine_cameras take.  Inputs: kpts [F][C][Pmax][kn][3] ON THE UNDISTORTED FRAME, n_persons [F][C] or NULL, det_of
+ * [F][C][P] or NULL.  The rule, per frame f, person p < P and joint j < kn:
+ *   1. Camera c LISTS person p iff q = det_of[f][c][p] satisfies 0 <= q < n_persons[f][c] -- the first condition of rule 1 of
+ *      "Refinement", word for word: det_of NULL means q = p, which requires P <= Pmax; n_persons NULL means Pmax everywhere; an
+ *      n_persons above Pmax counts as Pmax.  Its observation is then (u_c, v_c, s_c) = kpts[f][c][q][j]; a camera that does not
+ *      list the person has the observation (0, 0, 0) and is in no set below.
+ *   2. The record is what rules 1-4 of snowtri_triangulate_robust give on these C observations, with "camera c lists person p" in
+ *      the place of n_persons[f][c] > 0: the start set S = { c listed : not (s_c < keypoint_score_threshold) }; |S| < 2 gives the
+ *      record (0, 0, 0, 0), views = 0, resid = 0; the same rig-frame DLT, the same leave-one-out loop with reproj_threshold_px and
+ *      max_drops, the same NaN and tie behaviour (there is NO finite-pixel condition: as there, a non-finite pixel of a listed
+ *      camera reaches the solve); joint score = mean of s_c over the final S; views = bit mask of the final S; resid = the RMS pixel
+ *      residual over it.  out_pscore[f][p] = the mean of the kn joint scores.
+ * Two persons may name the same detection and then get the same record: one-to-one is the matcher's business.  Every (f, p) slot
+ * is written; there are no count or flags outputs, P is the caller's.  snowmocap_amd/matched.py::triangulate_matched_reference is
+ * this rule in NumPy (it gathers per person and calls triangulate_robust_reference).  The kernel (k_dlt_matched,
+ * snowmocap_amd/csrc/snowtri_matched.hpp: one lane per (f, p, j), the tile's det_of / n_persons resolved once into LDS) runs
+ * k_dlt_robust's own item -- one device function, robust_item, serves both -- so person p's xyzs, pscore, views and resid equal
+ * snowtri_triangulate_robust's on that person's gathered [F][C][1][kn][3] keypoints (n_persons = listed) BIT FOR BIT, and agree with
+ * the NumPy rule as that entry does.  A person's bits depend on its own observations, the rig and the settings only: not on F, P,
+ * Pmax, its slot, its neighbours, the order of a camera's list, or how a batch is cut into calls.
+ *   out_xyzs [F][P][kn][4] and out_pscore [F][P] (may be NULL) of out_dtype, out_views [F][P][kn] uint32 (may be NULL), out_resid
+ *   [F][P][kn] of out_dtype (may be NULL); a NULL output costs nothing and nothing is written for it.
+ * Refusals (SNOWTRI_ERR_BAD_ARG, snowtri_last_error() names the argument; nothing is enqueued or written): a NULL context, an
+ * unknown dtype or memspace, F < 0, P, kn or Pmax < 1, fewer than 2 or more than 8 cameras, a reproj_threshold_px or max_drops that
+ * snowtri_ctx_set_robust refuses, a NaN keypoint_score_threshold, det_of == NULL with P > Pmax, a NULL kpts or out_xyzs, a device
+ * pointer that is not aligned (out_xyzs: 16 bytes, every other array: its element), the size limits of snowtri_refine_joints,
+ * one frame's P * kn joint scores (8 bytes each) that do not fit the LDS of a CU beside the kernel's tables.  F == 0 is
+ * SNOWTRI_OK and looks at no pointer.  SNOWTRI_DEVICE: asynchronous on `stream`, no host read, no allocation, no internal stream.
+ * SNOWTRI_HOST: staged and synchronous.
+ * snowtri_last_kernel_names reports k_dlt_matched<...> after the call; with snowtri_set_timing on, snowtri_last_kernel_ms gives its
+ * time in kernel_ms[0] (kernel_ms[1] is 0).
+ * NOT offered: more than 8 cameras; matching against the previous frame's persons; seeding new persons from the detections nobody
+ * claimed (person_of of snowtri_assign_detections). */
+int snowtri_triangulate_matched(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, int32_t Pmax, const void *kpts, int kpts_dtype,
+                                const int32_t *n_persons /* [F][C] or NULL */, const int32_t *det_of /* [F][C][P] or NULL */,
+                                double keypoint_score_threshold, double reproj_threshold_px, int32_t max_drops,
+                                void *out_xyzs /* [F][P][kn][4] */, void *out_pscore /* [F][P] or NULL */, int out_dtype,
+                                uint32_t *out_views /* [F][P][kn] or NULL */, void *out_resid /* [F][P][kn] or NULL */, int memspace,
+                                void *stream);
+
 /* Measurement aid: HIP-event time (ms) of the kernels launched by the LAST
  * snowtri_triangulate_condense call on this context, measured on the stream they ran on
  * (blocks until they finish).  kernel_ms[0] = dominant fused kernel, [1] = everything else. */

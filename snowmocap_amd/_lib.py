@@ -147,6 +147,8 @@ _SIGNATURES = {
                                              ct.c_int, _c_p]),
     "snowtri_refine_joints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                          ct.c_double, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_triangulate_matched": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, ct.c_double,
+                                               ct.c_double, ct.c_int32, _c_p, _c_p, ct.c_int, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_pose_sweep_records": (ct.c_int, []),
     "snowtri_refine_cameras": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                           ct.c_double, ct.c_uint32, ct.c_int32, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
@@ -568,6 +570,41 @@ class Context:
                                            ptr(rep["codes"]), ptr(rep["normal"]), *space.tail())
         self._reproject_status(rc, "snowtri_refine_cameras")
         return (R, t, rep) if diagnostics else (R, t)
+
+    def triangulate_matched(self, kpts, det_of=None, n_persons=None, keypoint_score_threshold=0.0, reproj_threshold_px=6.0, max_drops=1,
+                            dtype=None, diagnostics=False, stream=None):
+        """The robust N-view DLT of 3D person p over the detections det_of names (include/snowtri.h, "Matched triangulation";
+        k_dlt_matched): kpts [F, C, Pmax, kn, 3] on the undistorted frame (float32 / float64), det_of [F, C, P] (match_detections'
+        int64 is handed on as int32; -1: none; None: detection p, P = Pmax), n_persons [F, C] int32 or None; reproj_threshold_px and
+        max_drops as for DLT_ROBUST.  Host arrays, or contiguous CUDA tensors (all of them) used in place and asynchronously on
+        `stream`.  dtype: of the outputs, float32 or float64 (default: that of kpts).
+        -> (xyzs [F, P, kn, 4], pscore [F, P]), or (xyzs, pscore, views [F, P, kn] uint32 / torch int32, resid [F, P, kn] px) with
+        diagnostics=True.  A person's outputs equal DLT_ROBUST's on its gathered keypoints bit for bit."""
+        space = Space("Context.triangulate_matched", kpts, n_persons, det_of, stream=stream)
+        if len(kpts.shape) != 5 or int(kpts.shape[1]) != self.C or int(kpts.shape[4]) != 3:
+            raise ValueError(f"kpts must be [F, C={self.C}, Pmax, kn, 3] (got shape {tuple(kpts.shape)})")
+        kpts, kcode = space.floats(kpts, "keypoints")
+        F, _, Pmax, kn, _ = (int(v) for v in kpts.shape)
+        if n_persons is not None:
+            n_persons = space.ints(n_persons, (F, self.C), "n_persons")
+        P = Pmax
+        if det_of is not None:
+            if len(det_of.shape) != 3:
+                raise ValueError(f"det_of must be [F={F}, C={self.C}, P] (got shape {tuple(det_of.shape)})")
+            P = int(det_of.shape[2])
+            if space.device is not None and det_of.dtype == space.torch.int64:
+                det_of = det_of.to(space.torch.int32).contiguous()
+            det_of = space.ints(det_of, (F, self.C, P), "det_of")
+        ocode = kcode if dtype is None else _float_code(dtype)
+        kind = "float32" if ocode == F32 else "float64"
+        xyzs, pscore = space.empty((F, P, kn, 4), kind), space.empty((F, P), kind)
+        views = space.empty((F, P, kn), "flags") if diagnostics else None
+        resid = space.empty((F, P, kn), kind) if diagnostics else None
+        rc = self.L.snowtri_triangulate_matched(self.handle, F, P, kn, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of),
+                                                float(keypoint_score_threshold), float(reproj_threshold_px), int(max_drops), ptr(xyzs),
+                                                ptr(pscore), ocode, ptr(views), ptr(resid), *space.tail())
+        self._reproject_status(rc, "snowtri_triangulate_matched")
+        return (xyzs, pscore, views, resid) if diagnostics else (xyzs, pscore)
 
     def set_timing(self, enabled=True, attach=False):
         """attach: single-kernel calls carry the event pair on their dispatch (the kernel's own begin / end) instead of being bracketed."""

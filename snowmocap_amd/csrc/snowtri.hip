@@ -29,6 +29,7 @@
 #include "snowtri_assoc.hpp"
 #include "snowtri_dlt_lean.hpp"
 #include "snowtri_robust.hpp"
+#include "snowtri_matched.hpp"
 #include "snowtri_smooth.hpp"
 #include "snowtri_blender.hpp"
 #include "snowtri_undistort.hpp"
@@ -3394,3 +3395,94 @@ extern "C" int snowtri_triangulate_robust(snowtri_ctx *ctx, int64_t F, int32_t J
                       out_count, out_flags, memspace, stream, 0u, &rb);
 }
 
+
+// ------------------------------------------------------------------------------- matched triangulation
+namespace {
+
+// k_dlt_matched (snowtri_matched.hpp), one workgroup per tile of T frames.  A tile holds T * P single-person frames, and those are
+// sized as launch_dlt_robust sizes its tile: enough to fill the chip for a small batch, at most kRobustMaxTile of them (a tile of
+// 16 frames x 2 persons measured 1.23 x k_dlt_robust on the pre-gathered frames: 667 workgroups on 512 slots are two uneven rounds)
+// and at most 32 KB of joint scores in the LDS stash (two workgroups share a CU); a frame whose P * kn scores are more than that is
+// a tile of its own, up to the 160 KB of a CU (the P matrices, the frame's det_of table and the scores share them).  Results do
+// not depend on T.  -> 0: one frame does not fit.
+int matched_tile_frames(int64_t F, int C, int P, int kn, int num_cus) {
+    const int64_t resident = (int64_t)num_cus * kRobustWaves, per_frame = 8 * (int64_t)P * kn;
+    const int64_t rows = std::min<int64_t>(kRobustMaxTile, (F * P + resident - 1) / resident);   // (F * P <= F * P * kn: checked by the caller)
+    int64_t T = std::max<int64_t>(1, rows / P);
+    T = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(32 * 1024) / per_frame));
+    if (per_frame > (int64_t)160 * 1024 || matched_lds_bytes(C, (int)T, P, kn) > (size_t)160 * 1024) return 0;
+    return (int)T;
+}
+
+}  // namespace
+
+extern "C" int snowtri_triangulate_matched(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, int32_t Pmax, const void *kpts, int kpts_dtype,
+                                           const int32_t *n_persons, const int32_t *det_of, double keypoint_score_threshold,
+                                           double reproj_threshold_px, int32_t max_drops, void *out_xyzs, void *out_pscore, int out_dtype,
+                                           uint32_t *out_views, void *out_resid, int memspace, void *stream) {
+    const Refuse refuse{"snowtri_triangulate_matched"};
+    if (!ctx) return refuse("null context");
+    if ((kpts_dtype != SNOWTRI_F32 && kpts_dtype != SNOWTRI_F64) || (out_dtype != SNOWTRI_F32 && out_dtype != SNOWTRI_F64)) return refuse("unknown dtype");
+    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
+    if (F < 0 || P < 1 || kn < 1) return refuse("F < 0, P < 1 or kn < 1");
+    if (ctx->C < 2 || ctx->C > kRobustMaxCams) return refuse("the robust DLT takes 2 to 8 cameras");
+    if (!(reproj_threshold_px >= 0.0)) return refuse("reproj_threshold_px must be >= 0 (+inf allowed), not negative or NaN");
+    if (max_drops < 0 || max_drops > kRobustMaxDrops) return refuse("max_drops must be in [0, 6]");
+    if (F > 0 && !out_xyzs) return refuse("null array (out_xyzs)");
+    // Pmax, the NaN threshold, det_of == NULL with P > Pmax, the size limits, null kpts, the alignment of the inputs: as the refinement
+    // entries check them (the records of this call are its OUTPUT: out_xyzs stands where they take xyzs)
+    ObservedInputs in;
+    if (int rc = in.check(refuse, ctx, F, P, kn, out_xyzs, out_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, nullptr, keypoint_score_threshold, 1,
+                          0u, 0u, memspace))
+        return rc;
+    if (F == 0) return SNOWTRI_OK;
+    const size_t osz = dtype_size(out_dtype);
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)out_xyzs) & 15u) || ((((uintptr_t)out_pscore) | ((uintptr_t)out_resid)) & (osz - 1)) || (((uintptr_t)out_views) & 3u)))
+        return refuse("out_xyzs must be aligned to 16 bytes, out_pscore, out_views and out_resid to their element size");
+    const int C = ctx->C, T = matched_tile_frames(F, C, P, kn, ctx->num_cus);
+    if (T < 1) return refuse("P * kn joint scores of one frame and the kernel's tables must fit the LDS of a CU");
+    const int64_t tiles = (F + T - 1) / T;
+    if (tiles > 0x7fffffffll) return refuse("more than 2^31 - 1 tiles");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const void *dk = kpts;
+    const int32_t *dnp = n_persons, *ddet = det_of;
+    void *d_xyzs = out_xyzs, *d_ps = out_pscore, *d_resid = out_resid;
+    uint32_t *d_views = out_views;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dk, in.k_bytes);
+    sg.in(&dnp, in.np_bytes);
+    sg.in(&ddet, in.det_bytes);
+    sg.out(&d_xyzs, in.x_bytes);
+    sg.out(&d_ps, osz * (size_t)F * P);
+    sg.out(&d_views, in.views_bytes);
+    sg.out(&d_resid, osz * (size_t)in.n_rec);
+    if (int rc = sg.begin()) return rc;
+    const size_t lds = matched_lds_bytes(C, T, P, kn);
+    const double tau2 = reproj_threshold_px * reproj_threshold_px;
+    int rc = SNOWTRI_ERR_BAD_ARG;   // (a build without this camera count: the kernel-development builds)
+    if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0], st));   // snowtri_set_timing: the kernel between the pair snowtri_last_kernel_ms reads
+    with_cameras<2, kRobustMaxCams>(C, [&](auto cc) {
+        with_float_pair(kpts_dtype, out_dtype, [&](auto tk, auto to) {
+            constexpr int CC = decltype(cc)::value;
+            using TK = decltype(tk);
+            using TO = decltype(to);
+            rc = raise_lds_or_fail(ctx, (const void *)k_dlt_matched<CC, TK, TO>, lds);
+            if (rc) return;
+            hipLaunchKernelGGL((k_dlt_matched<CC, TK, TO>), dim3((unsigned)tiles), dim3(kBlock), lds, st, F, (int)P, (int)Pmax, (int)kn, T, ctx->rig(),
+                               (const TK *)dk, dnp, ddet, keypoint_score_threshold, tau2, (int)max_drops, (TO *)d_xyzs, (TO *)d_ps, d_views, (TO *)d_resid);
+            static const std::string name = kernel_name("k_dlt_matched", {std::to_string(CC), type_name<TK>(), type_name<TO>()});
+            ctx->last_kernels = name.c_str();
+        });
+    });
+    if (rc) return rc == SNOWTRI_ERR_BAD_ARG ? refuse("this build has no k_dlt_matched for the context's camera count") : rc;
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) {
+        HIP_TRY(hipEventRecord(ctx->ev[1], st));
+        HIP_TRY(hipEventRecord(ctx->ev[2], st));   // (no second phase: the pair (2, 3) is empty)
+        HIP_TRY(hipEventRecord(ctx->ev[3], st));
+        ctx->ev_valid = true;
+        ctx->ev_stream = st;
+    }
+    return sg.end();
+}

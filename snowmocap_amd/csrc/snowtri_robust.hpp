@@ -9,7 +9,8 @@
 // over the candidate camera is then wave-uniform, a candidate's subset is a bit mask (the rows of A^T A are re-accumulated
 // from the registers with weights 0 / 1), and lanes that do not try the candidate run the solve with `live` = false.  Every
 // select is per lane, so a settled lane keeps its answer whatever its wave-mates still do (the discipline of
-// dlt_inverse_iteration); the wave votes inside dlt_solve only decide how long the wave goes on.
+// dlt_inverse_iteration); the wave votes inside dlt_solve only decide how long the wave goes on.  That item is robust_item below,
+// which k_dlt_matched (snowtri_matched.hpp) calls on other observations.
 //
 // Frame: k_fused_single's -- a workgroup owns a tile of T frames, the joint scores go through an LDS stash, one barrier, then
 // the frames' mean scores (person score), count = 1, flags = FASTPATH as the DLT kernels write them.  A tile is one
@@ -28,6 +29,92 @@ constexpr int kRobustMaxTile = 16;    // frames per workgroup
 // [P[C][12] + the rig frame | stash [T][kn] fp64 | detection mask per frame]
 __host__ __device__ constexpr size_t robust_lds_bytes(int C, int T, int kn) {
     return (((size_t)96 * C + 8 * kDltFrame + (size_t)8 * T * kn + (size_t)4 * T) + 15) & ~(size_t)15;
+}
+
+// The item both robust kernels run (k_dlt_robust here, k_dlt_matched in snowtri_matched.hpp): rules 2 and 3 on a lane's C observations.
+// In: S = the start set (0 for a lane past the end), cnt = |S|, ok = cnt >= 2, Pl = P[C][12] in LDS.  Out: S and cnt of the final set,
+// (x, y, z) = its point in the rig's frame, sum = the total of its squared pixel residuals.  The wave must enter with every lane.
+template <int C, typename TIn>
+__device__ __forceinline__ void robust_item(const Kp3<TIn> (&obs)[C], const double *Pl, double tau2, int max_drops, bool ok, uint32_t &S, int &cnt,
+                                            double &x, double &y, double &z, double &sum) {
+#pragma clang fp contract(off)   // comparisons decide here: no result may depend on which inlined copy computed it (see dlt_item)
+    // solve(Tm): X = the DLT point of the views in Tm, m = max, sum = total of their squared pixel residuals (m is NaN if one is)
+    auto solve = [&](uint32_t Tm, bool act, double &x, double &y, double &z, double &m, double &sum) {
+#pragma clang fp contract(off)
+        double A[4][4];
+        asm volatile("" ::: "memory");   // (P is read from LDS where a camera's rows are formed: hoisted it is 12 C doubles)
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            __builtin_amdgcn_sched_barrier(0);   // a camera's twelve LDS reads stay with its observation (register budget)
+            const double w = ((Tm >> c) & 1u) ? 1.0 : 0.0;
+            if (c == 0)
+                dlt_add_observation<true, true>(A, Pl + 12 * c, (double)obs[c].u, (double)obs[c].v, w);
+            else
+                dlt_add_observation<true, false>(A, Pl + 12 * c, (double)obs[c].u, (double)obs[c].v, w);
+        }
+        double e[4];
+        dlt_solve(A, act, e);
+        const double r = dlt_recip(e[3]);
+        x = e[0] * r;
+        y = e[1] * r;
+        z = e[2] * r;
+        m = 0.0;
+        sum = 0.0;
+        bool isnan_ = false;
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            __builtin_amdgcn_sched_barrier(0);
+            const double *P = Pl + 12 * c;
+            const double p0 = fma(P[0], x, fma(P[1], y, fma(P[2], z, P[3])));
+            const double p1 = fma(P[4], x, fma(P[5], y, fma(P[6], z, P[7])));
+            const double p2 = fma(P[8], x, fma(P[9], y, fma(P[10], z, P[11])));
+            const double ip = dlt_recip(p2);
+            const double du = p0 * ip - (double)obs[c].u, dv = p1 * ip - (double)obs[c].v;
+            const double r2 = du * du + dv * dv;
+            const bool in = (Tm >> c) & 1u;
+            const double r2c = in ? r2 : 0.0;
+            isnan_ = isnan_ || (in && r2 != r2);
+            m = r2c > m ? r2c : m;
+            sum += r2c;
+        }
+        m = isnan_ ? __builtin_nan("") : m;
+    };
+
+    double m;
+    solve(S, ok, x, y, z, m, sum);
+    int d = 0;
+    bool need = ok && cnt >= 3 && d < max_drops && m > tau2;
+    while (__any(need)) {
+        // leave-one-out: the subset whose worst residual is smallest wins; ties go to the lowest camera, a NaN never beats a number
+        double bx = x, by = y, bz = z, bm = m, bsum = sum;
+        int bc = -1;
+#pragma unroll 1
+        for (int c = 0; c < C; c++) {
+            const bool cand = need && ((S >> c) & 1u);
+            if (!__any(cand)) continue;
+            double cx, cy, cz, cm, csum;
+            solve(cand ? (S & ~(1u << c)) : 0u, cand, cx, cy, cz, cm, csum);
+            const bool win = cand && (bc < 0 || cm < bm || (bm != bm && cm == cm));
+            bx = win ? cx : bx;
+            by = win ? cy : by;
+            bz = win ? cz : bz;
+            bm = win ? cm : bm;
+            bsum = win ? csum : bsum;
+            bc = win ? c : bc;
+        }
+        SNOWTRI_DEV_CHECK(!need || (bc >= 0 && bc < C && ((S >> bc) & 1u)), 62);
+        // a lane that is not in the round keeps what it has
+        S = need ? (S & ~(1u << (bc & 7))) : S;
+        x = need ? bx : x;
+        y = need ? by : y;
+        z = need ? bz : z;
+        m = need ? bm : m;
+        sum = need ? bsum : sum;
+        cnt -= need ? 1 : 0;
+        d += need ? 1 : 0;
+        need = need && cnt >= 3 && d < max_drops && m > tau2;
+    }
 }
 
 template <int C, typename TIn, typename TOut>
@@ -85,83 +172,8 @@ __global__ __launch_bounds__(kBlock, kRobustWaves) void k_dlt_robust(int64_t F, 
         int cnt = __popc(S);
         const bool ok = cnt >= 2;
 
-        // solve(Tm): X = the DLT point of the views in Tm, m = max, sum = total of their squared pixel residuals (m is NaN if one is)
-        auto solve = [&](uint32_t Tm, bool act, double &x, double &y, double &z, double &m, double &sum) {
-#pragma clang fp contract(off)
-            double A[4][4];
-            asm volatile("" ::: "memory");   // (P is read from LDS where a camera's rows are formed: hoisted it is 12 C doubles)
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                __builtin_amdgcn_sched_barrier(0);   // a camera's twelve LDS reads stay with its observation (register budget)
-                const double w = ((Tm >> c) & 1u) ? 1.0 : 0.0;
-                if (c == 0)
-                    dlt_add_observation<true, true>(A, Pl + 12 * c, (double)obs[c].u, (double)obs[c].v, w);
-                else
-                    dlt_add_observation<true, false>(A, Pl + 12 * c, (double)obs[c].u, (double)obs[c].v, w);
-            }
-            double e[4];
-            dlt_solve(A, act, e);
-            const double r = dlt_recip(e[3]);
-            x = e[0] * r;
-            y = e[1] * r;
-            z = e[2] * r;
-            m = 0.0;
-            sum = 0.0;
-            bool isnan_ = false;
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                __builtin_amdgcn_sched_barrier(0);
-                const double *P = Pl + 12 * c;
-                const double p0 = fma(P[0], x, fma(P[1], y, fma(P[2], z, P[3])));
-                const double p1 = fma(P[4], x, fma(P[5], y, fma(P[6], z, P[7])));
-                const double p2 = fma(P[8], x, fma(P[9], y, fma(P[10], z, P[11])));
-                const double ip = dlt_recip(p2);
-                const double du = p0 * ip - (double)obs[c].u, dv = p1 * ip - (double)obs[c].v;
-                const double r2 = du * du + dv * dv;
-                const bool in = (Tm >> c) & 1u;
-                const double r2c = in ? r2 : 0.0;
-                isnan_ = isnan_ || (in && r2 != r2);
-                m = r2c > m ? r2c : m;
-                sum += r2c;
-            }
-            m = isnan_ ? __builtin_nan("") : m;
-        };
-
-        double x, y, z, m, sum;
-        solve(S, ok, x, y, z, m, sum);
-        int d = 0;
-        bool need = ok && cnt >= 3 && d < max_drops && m > tau2;
-        while (__any(need)) {
-            // leave-one-out: the subset whose worst residual is smallest wins; ties go to the lowest camera, a NaN never beats a number
-            double bx = x, by = y, bz = z, bm = m, bsum = sum;
-            int bc = -1;
-#pragma unroll 1
-            for (int c = 0; c < C; c++) {
-                const bool cand = need && ((S >> c) & 1u);
-                if (!__any(cand)) continue;
-                double cx, cy, cz, cm, csum;
-                solve(cand ? (S & ~(1u << c)) : 0u, cand, cx, cy, cz, cm, csum);
-                const bool win = cand && (bc < 0 || cm < bm || (bm != bm && cm == cm));
-                bx = win ? cx : bx;
-                by = win ? cy : by;
-                bz = win ? cz : bz;
-                bm = win ? cm : bm;
-                bsum = win ? csum : bsum;
-                bc = win ? c : bc;
-            }
-            SNOWTRI_DEV_CHECK(!need || (bc >= 0 && bc < C && ((S >> bc) & 1u)), 62);
-            // a lane that is not in the round keeps what it has
-            S = need ? (S & ~(1u << (bc & 7))) : S;
-            x = need ? bx : x;
-            y = need ? by : y;
-            z = need ? bz : z;
-            m = need ? bm : m;
-            sum = need ? bsum : sum;
-            cnt -= need ? 1 : 0;
-            d += need ? 1 : 0;
-            need = need && cnt >= 3 && d < max_drops && m > tau2;
-        }
+        double x, y, z, sum;
+        robust_item<C, TIn>(obs, Pl, tau2, max_drops, ok, S, cnt, x, y, z, sum);
 
         double ssum = 0.0;
 #pragma unroll

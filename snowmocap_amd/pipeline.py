@@ -41,7 +41,7 @@ class TrackPipeline:
         self.bt.close()
 
     def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0, despike=None,
-            reproject=None, refine=None, one_to_one=False):
+            reproject=None, refine=None, one_to_one=False, retriangulate=None):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -100,17 +100,30 @@ class TrackPipeline:
         assignment per frame and camera with the same gate, at most one person per detection) instead of match_detections.  A person
         whose only detections inside the gate went to persons they fit better is then unmatched in that view (det_of -1) instead of
         sharing one; with reproject=, shared -- still computed from det_of by the same expression -- is all False and person_of
-        [F, C, Pmax] is added (the person that took detection q, -1: a detection nobody claimed).  It needs reproject or refine
-        (ValueError otherwise), and gates of at most 1e150 px: staying unmatched costs gate_px^2, so the infinite gate that
-        match_detections reads as "no gate" is refused.  False (the default): nothing changes."""
-        if one_to_one and reproject is None and refine is None:
-            raise ValueError("one_to_one=True needs reproject= or refine=: it chooses how their matching step pairs persons and detections")
+        [F, C, Pmax] is added (the person that took detection q, -1: a detection nobody claimed).  It needs reproject, refine
+        or retriangulate (ValueError otherwise), and gates of at most 1e150 px: staying unmatched costs gate_px^2, so the infinite gate that
+        match_detections reads as "no gate" is refused.  False (the default): nothing changes.
+        retriangulate=gate_px or (gate_px, reproj_threshold_px, max_drops) (the last two default to 6.0 and 1): every person is
+        triangulated again from ALL the views that show it, right after the first triangulation and before refine=.  Three steps on
+        the UNDISTORTED keypoints: reprojection_cost of the first pass's persons, the matching step above with gate_px (one_to_one is
+        honoured, and is legal with retriangulate= alone), matched.triangulate_matched (k_dlt_matched: DLT_ROBUST's rule on the
+        detections det_of names).  A joint record the second pass made from at least 2 views replaces the first pass's; every other
+        record keeps the first pass's bits, so no joint is lost; count and flags are the first pass's.  Adds retri_views [F, P, kn]
+        (int32 bit mask of the cameras used, 0: the record was kept) and retri_resid [F, P, kn] (RMS px, 0 where kept), both in the
+        triangulation's list order.  With refine= as well the refinement reuses this det_of (its own gate_px is then not used) and
+        is given retri_views as its `views`, all ones where the record was kept.  None (the default): off, nothing changes and no
+        key is added."""
+        from .matched import retriangulate_args
+        rtr = retriangulate_args(retriangulate)
+        if one_to_one and reproject is None and refine is None and rtr is None:
+            raise ValueError("one_to_one=True needs reproject=, refine= or retriangulate=: it chooses how their matching step pairs persons "
+                             "and detections")
         one_to_one, rfn = bool(one_to_one), refine_args(refine)
         if one_to_one:                                     # before any work: the assignment needs a finite gate (<= 1e150)
             from .reproject import assign_gate
-            for gate in ([reproject] if reproject is not None else []) + ([rfn[1]] if rfn else []):
+            for gate in ([reproject] if reproject is not None else []) + ([rfn[1]] if rfn else []) + ([rtr[0]] if rtr else []):
                 assign_gate(gate)
-        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn, one_to_one)
+        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn, one_to_one, rtr)
         if reproject is not None:
             self._add_reprojection(res, kpts, n_persons, float(reproject), one_to_one)
         return res
@@ -148,21 +161,44 @@ class TrackPipeline:
         pix = ctx.reproject(xyzs, raw=raw, dtype=torch.float64)
         _, res["view_rms"], res["view_n"] = view_residuals(pix, kpts, res["det_of"], thr)
 
-    def _refine(self, xyzs, n_persons, rfn, one_to_one=False):
-        """run(refine=...): the triangulated records against the undistorted keypoints of the call that made them
-        -> (refined records, cost, codes)."""
-        iters, gate_px, score_weights = rfn
+    def _undistorted(self):
+        """The undistorted keypoints of the last triangulation, cut to the joints it kept (the first kn of a detection)."""
         ukpts = self.bt.last_undistorted_kpts
-        if int(ukpts.shape[3]) != self.kn:                # the joints the triangulation kept are the first kn of a detection
+        if int(ukpts.shape[3]) != self.kn:
             ukpts = ukpts[:, :, :, :self.kn].contiguous()
+        return ukpts
+
+    def _retriangulate(self, xyzs, n_persons, rtr, one_to_one=False):
+        """run(retriangulate=...): the first pass's records against the undistorted keypoints of the call that made them
+        -> (merged records, retri_views, retri_resid, det_of)."""
+        import torch
+        gate_px, tau, max_drops = rtr
+        ukpts = self._undistorted()
         ctx, thr = self.bt.ctx, float(self.th["keypoint_score_threshold"])
         xyzs = xyzs.contiguous()
         cost_sum, cost_n = ctx.reproject_cost(xyzs, ukpts, n_persons=n_persons, keypoint_score_threshold=thr)
         det_of = self._match(cost_sum, cost_n, gate_px, one_to_one)[0]
-        return ctx.refine_joints(xyzs, ukpts, det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr, iters=iters,
+        again, _, views, resid = ctx.triangulate_matched(ukpts, det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr,
+                                                         reproj_threshold_px=tau, max_drops=max_drops, dtype=xyzs.dtype, diagnostics=True)
+        return torch.where((views != 0)[..., None], again, xyzs), views, resid, det_of
+
+    def _refine(self, xyzs, n_persons, rfn, one_to_one=False, matched=None):
+        """run(refine=...): the triangulated records against the undistorted keypoints of the call that made them
+        -> (refined records, cost, codes).  matched: (det_of, retri_views) of run(retriangulate=...), used instead of a matching step."""
+        import torch
+        iters, gate_px, score_weights = rfn
+        ukpts = self._undistorted()
+        ctx, thr = self.bt.ctx, float(self.th["keypoint_score_threshold"])
+        xyzs = xyzs.contiguous()
+        if matched is None:
+            cost_sum, cost_n = ctx.reproject_cost(xyzs, ukpts, n_persons=n_persons, keypoint_score_threshold=thr)
+            det_of, views = self._match(cost_sum, cost_n, gate_px, one_to_one)[0], None
+        else:
+            det_of, views = matched[0], torch.where(matched[1] != 0, matched[1], -1).contiguous()   # a kept record: every camera
+        return ctx.refine_joints(xyzs, ukpts, det_of=det_of, n_persons=n_persons, views=views, keypoint_score_threshold=thr, iters=iters,
                                  score_weights=score_weights, diagnostics=True)
 
-    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None, one_to_one=False):
+    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None, one_to_one=False, rtr=None):
         """run() without its reprojection keys."""
         dsp = despike_args(despike)
         import torch
@@ -188,9 +224,12 @@ class TrackPipeline:
                 if F and int(cnt[0]) > self.P:
                     raise ValueError(f"frame 0 resolved to {int(cnt[0])} persons, the track has {self.P} slots (n_persons_out)")
                 tracked = np.minimum(cnt, int(cnt[0]) if F else 0).astype(np.int32)
-        xyzs = tri["xyzs"]
+        xyzs, matched = tri["xyzs"], None
+        if rtr:
+            xyzs, retri_views, retri_resid, det_of = self._retriangulate(xyzs, n_persons, rtr, one_to_one)
+            matched = (det_of, retri_views)
         if rfn:
-            xyzs, refine_cost, refine_codes = self._refine(xyzs, n_persons, rfn, one_to_one)
+            xyzs, refine_cost, refine_codes = self._refine(xyzs, n_persons, rfn, one_to_one, matched)
         th = self.th
         fzrd =(float(th["smooth_f"]), float(th["smooth_z"]), float(th["smooth_r"]), float(th["smooth_delta_time"]))
         fill_gaps = int(fill_gaps)
@@ -275,6 +314,8 @@ class TrackPipeline:
                 res["xyzs_despiked"], res["spike_codes"] = desp, scodes
             if rfn:
                 res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
+            if rtr:
+                res["retri_views"], res["retri_resid"] = retri_views, retri_resid
             return res
         if tracked is None:
             src = xyzs
@@ -312,6 +353,8 @@ class TrackPipeline:
             res["xyzs_despiked"], res["spike_codes"] = desp, scodes
         if rfn:
             res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
+        if rtr:
+            res["retri_views"], res["retri_resid"] = retri_views, retri_resid
         return res
 
     @staticmethod

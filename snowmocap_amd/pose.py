@@ -237,6 +237,10 @@ class _LibrarySteps:
     def pixels(self, xyzs):
         return self.ctx.reproject(xyzs, dtype=np.float64)
 
+    def matched(self, kpts, det_of, n_persons, thr):
+        return self.ctx.triangulate_matched(kpts, det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr, dtype=np.float64,
+                                            diagnostics=True)
+
     def joints(self, xyzs, kpts, **kw):
         return self.ctx.refine_joints(xyzs, kpts, **kw)
 
@@ -268,6 +272,11 @@ class _ReferenceSteps:
         from .reproject import reproject_reference
         return reproject_reference(*self.rig, xyzs)
 
+    def matched(self, kpts, det_of, n_persons, thr):
+        from .matched import triangulate_matched_reference
+        ref = triangulate_matched_reference(*self.rig, kpts, det_of, n_persons, thr)
+        return ref["xyzs"], ref["pscore"], ref["views"], ref["resid"]
+
     def joints(self, xyzs, kpts, **kw):
         from .refine import refine_joints_reference
         return refine_joints_reference(*self.rig, xyzs, kpts, **kw)[0]
@@ -278,7 +287,7 @@ class _ReferenceSteps:
 
 def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.DLT, params=None, persons=None, gate_px=12.0,
                min_joints=8, joint_iters=4, camera_iters=8, min_obs=64, score_weights=False, triangulate=None, reference=False,
-               one_to_one=False):
+               one_to_one=False, retriangulate=False):
     """Block-coordinate bundle adjustment of the extrinsics: `rounds` times triangulate on the current rig, match the detections to the
     3D persons (reprojection_cost + match_detections, gate_px), refine the joints (refine_joints, joint_iters), refine the free cameras
     (refine_cameras, camera_iters, min_obs), and build a new context from the result.  Host arrays: kpts [F, C, Pmax, kn, 3] on the
@@ -297,6 +306,13 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
     one_to_one=True: the matching step is the optimal one-to-one assignment (reproject.assign_detections, k_assign; with reference=True
     its NumPy rule assign_detections_reference) instead of match_detections, with the same gate_px and min_joints; gate_px must
     then not exceed 1e150, since staying unmatched costs gate_px^2 (ValueError before any work).
+    retriangulate=True: each round triangulates every person again from the round's det_of before refine_joints
+    (matched.triangulate_matched, k_dlt_matched, with the robust defaults 6.0 px and 1 drop; with reference=True its NumPy rule
+    triangulate_matched_reference), so a person is fused from every view the matcher gave it, not only from those the first
+    triangulation associated.  A joint the second pass made from at least 2 views replaces the first pass's record, every other
+    record is kept (matched.merge_records), and the views mask -- all ones on a kept record -- is passed on to refine_joints and
+    refine_cameras.  It does NOT repair the two-person recipe above (measured: the same view RMS per round with and without, the
+    first triangulation has already split the persons: EXPERIMENTS.md round 28).  False (the default): nothing changes.
 
     -> (R [C, 3, 3], t [C, 3], history): history[r] = dict(overflow_frames: the frames in which the library's triangulation found
     more clusters than `persons` and dropped some (0 with the caller's `triangulate`), view_rms [C]: each camera's RMS pixel residual over its matched views
@@ -354,6 +370,11 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
                 history.append(dict(overflow_frames=steps.overflow_frames, view_rms=view_rms))
                 break
             kw = dict(det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr, score_weights=score_weights)
+            if retriangulate:
+                from .matched import merge_records
+                again, _, views, _ = steps.matched(kpts, det_of, n_persons, thr)
+                xyzs, kw["views"] = merge_records(xyzs, np.asarray(again, dtype=np.float64), views)
+                xyzs = np.ascontiguousarray(xyzs)
             xyzs = steps.joints(xyzs, kpts, iters=joint_iters, **kw)
             R, t, rep = steps.cameras(xyzs, kpts, free=mask, min_obs=min_obs, iters=camera_iters, **kw)
             R, t = np.array(R, dtype=np.float64), np.array(t, dtype=np.float64)
