@@ -806,14 +806,80 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
  * SNOWTRI_HOST: staged and synchronous.
  * snowtri_last_kernel_names reports k_dlt_matched<...> after the call; with snowtri_set_timing on, snowtri_last_kernel_ms gives its
  * time in kernel_ms[0] (kernel_ms[1] is 0).
- * NOT offered: more than 8 cameras; matching against the previous frame's persons; seeding new persons from the detections nobody
- * claimed (person_of of snowtri_assign_detections). */
+ * NOT offered: more than 8 cameras; matching against the previous frame's persons.  (Seeding new persons from the detections nobody
+ * claimed, person_of of snowtri_assign_detections, is "Seeding" below.) */
 int snowtri_triangulate_matched(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, int32_t Pmax, const void *kpts, int kpts_dtype,
                                 const int32_t *n_persons /* [F][C] or NULL */, const int32_t *det_of /* [F][C][P] or NULL */,
                                 double keypoint_score_threshold, double reproj_threshold_px, int32_t max_drops,
                                 void *out_xyzs /* [F][P][kn][4] */, void *out_pscore /* [F][P] or NULL */, int out_dtype,
                                 uint32_t *out_views /* [F][P][kn] or NULL */, void *out_resid /* [F][P][kn] or NULL */, int memspace,
                                 void *stream);
+
+/* Seeding: 3D persons from the detections nobody claimed (no reference counterpart).  The matching chain improves the persons the
+ * first triangulation found; a detection no person took (person_of[f][c][q] == -1 of snowtri_assign_detections) is a candidate for a
+ * person it missed.  Two entries: the PAIR COST of every two detections of two cameras, and the GROUPING of a frame's free detections
+ * into seeds, sets of mutually close detections of different cameras, written in the layout of det_of so that
+ * snowtri_triangulate_matched triangulates them unchanged.  With claimed == NULL every detection is free and the two calls are an
+ * association of their own, in ray space.
+ *
+ * snowtri_pair_cost.  kpts [F][C][Pmax][kn][3] on the undistorted frame, n_persons [F][C] or NULL (Pmax everywhere; a value above
+ * Pmax counts as Pmax), claimed [F][C][Pmax] or NULL: claimed >= 0 means the detection is taken (person_of consumed unchanged).
+ * Outputs pair_sum (float64) and pair_n (int32) [F][NP][Pmax][Pmax], NP = C (C - 1) / 2, camera pairs k = (a < b) in the reference's
+ * loop order (the order of the candidate slots); entry [f][k][q][r] belongs to detection q of camera a and detection r of camera b.
+ * The rule, in fp64, per joint j:
+ *   1. the ray h_c = M_c (u, v, 1), M_c = R_c K_c^-1 as snowtri_ctx_ray_matrices returns it;
+ *   2. n = h_a x h_b, nn = n . n, w = (t_b - t_a) . n, d2 = w * w / nn: the squared distance between the two LINES, the square of
+ *      the skew-ray method's distance.  No midpoint, no square root, no cheirality test;
+ *   3. the joint COUNTS iff both detections count by the words of snowtri_reproject_cost (q < n_persons, not score < threshold,
+ *      finite u and v), nn > 0 (parallel rays do not count) and d2 is finite;
+ *   4. pair_n = the number of counting joints, pair_sum = the sum of their d2 (world units squared), 0 when pair_n is 0;
+ *   5. a pair with a claimed member, or a member behind n_persons, is (0, 0) and its keypoints are not read.
+ * As for snowtri_reproject_cost an item's sum is formed in an order that depends on kn alone -- not on F, Pmax, the item's place in
+ * the launch or how a batch is cut into calls -- and the kernel (snowmocap_amd/csrc/snowtri_seed.hpp, k_pair_cost) writes its
+ * products as fused multiply-adds: it agrees with snowmocap_amd/seed.py::pair_cost_reference to rounding, not bit for bit; pair_n
+ * agrees exactly.
+ * Refusals (SNOWTRI_ERR_BAD_ARG, snowtri_last_error() names the argument; nothing is enqueued or written): a NULL context, an unknown
+ * dtype or memspace, F < 0, kn or Pmax < 1, fewer than 2 or more than 8 cameras, kn > 256, a NaN keypoint_score_threshold, a NULL
+ * kpts, pair_sum or pair_n, a device pointer that is not aligned to its element size, F * NP > 2^31 - 1 (the grid), more than 2^48
+ * costs or keypoints.  F == 0 is SNOWTRI_OK and looks at no pointer.  SNOWTRI_DEVICE: asynchronous on `stream`, no host read, no
+ * allocation, no internal stream.  SNOWTRI_HOST: staged and synchronous.  With snowtri_set_timing on, snowtri_last_kernel_ms gives
+ * the kernel's time in kernel_ms[0] (kernel_ms[1] is 0); the same holds for snowtri_seed_persons.
+ *
+ * snowtri_seed_persons.  One frame's NODES are x = c * Pmax + q, C * Pmax <= 64 (the lanes of one wave).  gate is an RMS line
+ * distance in world units, gate2 = gate * gate; S is the number of seed slots.  The rule, per frame:
+ *   1. node (c, q) is FREE iff q < n_persons[f][c] and claimed[f][c][q] < 0 (NULL: Pmax, nothing claimed);
+ *   2. the edge between nodes of different cameras weighs mean = pair_sum / pair_n, one correctly rounded division; it is ADMISSIBLE
+ *      iff pair_n >= min_joints, the mean is not NaN and mean <= gate2.  Every other edge, and every edge inside a camera, is +inf
+ *      ("finite" below: less than +inf);
+ *   3. until S seeds are emitted: among the edges between two free nodes take the one of smallest weight, ties to the lowest (x, y)
+ *      with x < y, lexicographic; if none is finite, stop;
+ *   4. M = {x, y}, then grow M: a candidate z is a free node outside M in a camera M does not hold with finite edges to ALL members
+ *      (M stays a clique: two persons are never chained together through a third view); take the z whose LARGEST edge to a member
+ *      is smallest, ties to the lowest node; stop when there is no candidate;
+ *   5. |M| < min_views: no seed; the starting edge (x, y) becomes +inf for the rest of this frame, its members stay free, go to 3
+ *      (every turn removes an edge or at least two free nodes, so the loop ends);
+ *   6. otherwise seed s = n_seeds++ gets seed_det_of[f][c][s] = q for its member in camera c, -1 in every other camera, and its
+ *      members are no longer free;
+ *   7. slots at or behind n_seeds[f] hold -1.
+ * flags[f] (optional) has SNOWTRI_SEED_FLAG_FULL iff the frame stopped at S seeds while step 3 still found a finite edge.
+ * After the one division there are only comparisons: EVERY OUTPUT, flags included, EQUALS snowmocap_amd/seed.py::
+ * seed_persons_reference BIT FOR BIT on the same pair_sum / pair_n (the kernel, k_seed_group, finds each minimum by a butterfly on
+ * a totally ordered tuple, exact in any order).  A frame's output depends on its own inputs and the settings only.
+ * Refusals: an unknown memspace, F < 0, Pmax < 1, S outside 1..64, min_joints < 1, a gate that is negative, NaN or above 1e150, a
+ * NULL context, a context of fewer than 2 cameras (the context is needed for C alone), C * Pmax > 64, min_views outside 2..C, a NULL
+ * pair_sum, pair_n, seed_det_of or n_seeds, a device pointer that is not aligned to its element size, F > 2^31 - 1.  F == 0 is
+ * SNOWTRI_OK and looks at no pointer.  HOST / DEVICE as above.
+ * NOT offered: more than 8 cameras in snowtri_pair_cost, C * Pmax > 64, seeding across time (a seed knows nothing of the frame
+ * before it). */
+#define SNOWTRI_SEED_FLAG_FULL 1u
+int snowtri_pair_cost(snowtri_ctx *ctx, int64_t F, int32_t kn, int32_t Pmax, const void *kpts, int kpts_dtype,
+                      const int32_t *n_persons /* [F][C] or NULL */, const int32_t *claimed /* [F][C][Pmax] or NULL */,
+                      double keypoint_score_threshold, double *pair_sum /* [F][NP][Pmax][Pmax] */, int32_t *pair_n, int memspace,
+                      void *stream);
+int snowtri_seed_persons(snowtri_ctx *ctx, int64_t F, int32_t Pmax, const double *pair_sum, const int32_t *pair_n,
+                         const int32_t *n_persons /* [F][C] or NULL */, const int32_t *claimed /* [F][C][Pmax] or NULL */, double gate,
+                         int32_t min_joints, int32_t min_views, int32_t S, int32_t *seed_det_of /* [F][C][S] */,
+                         int32_t *n_seeds /* [F] */, uint32_t *flags /* [F] or NULL */, int memspace, void *stream);
 
 /* Measurement aid: HIP-event time (ms) of the kernels launched by the LAST
  * snowtri_triangulate_condense call on this context, measured on the stream they ran on

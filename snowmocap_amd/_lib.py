@@ -26,6 +26,7 @@ REFINE_SCORE_WEIGHTS = 1       # snowtri_refine_joints: flags -- a view weighs i
 REFINE_MISSING, REFINE_FEW_VIEWS, REFINE_KEPT, REFINE_MOVED = 0, 1, 2, 3   # ... and its codes
 POSE_FIXED, POSE_FEW_OBS, POSE_KEPT, POSE_MOVED = 0, 1, 2, 3   # snowtri_refine_cameras: codes
 POSE_SWEEP_RECORDS = 1024 * 256   # ... and the records one sweep of k_pose_normal's grid covers (snowtri_pose_sweep_records)
+SEED_FLAG_FULL = 1             # snowtri_seed_persons: flags -- the frame stopped at S seeds with a finite edge between free nodes left
 CALL_NO_ZERO_FILL = 1         # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
 TEST_LIB_PATH = os.path.join(_HERE, "libsnowtri_dbg.so")   # -DSNOWTRI_DEBUG_BOUNDS -DSNOWTRI_TEST_KNOBS (tests only: use_library)
 
@@ -149,6 +150,9 @@ _SIGNATURES = {
                                          ct.c_double, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_triangulate_matched": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, ct.c_double,
                                                ct.c_double, ct.c_int32, _c_p, _c_p, ct.c_int, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_pair_cost": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, ct.c_double, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_seed_persons": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, _c_p, _c_p, _c_p, _c_p, ct.c_double, ct.c_int32, ct.c_int32, ct.c_int32,
+                                        _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_pose_sweep_records": (ct.c_int, []),
     "snowtri_refine_cameras": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                           ct.c_double, ct.c_uint32, ct.c_int32, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
@@ -605,6 +609,67 @@ class Context:
                                                 ptr(pscore), ocode, ptr(views), ptr(resid), *space.tail())
         self._reproject_status(rc, "snowtri_triangulate_matched")
         return (xyzs, pscore, views, resid) if diagnostics else (xyzs, pscore)
+
+    def pair_cost(self, kpts, n_persons=None, claimed=None, keypoint_score_threshold=0.0, stream=None):
+        """The squared line distance of every pair of detections of two cameras (include/snowtri.h, "Seeding"; k_pair_cost): kpts
+        [F, C, Pmax, kn, 3] on the undistorted frame (float32 / float64), n_persons [F, C] int32 or None, claimed [F, C, Pmax] int32
+        or None (>= 0: the detection is taken -- assign_detections' person_of; its int64 is handed on as int32) ->
+        (pair_sum [F, NP, Pmax, Pmax] float64, world units squared, pair_n int32), NP = C (C - 1) / 2 camera pairs (a < b) in the
+        reference's loop order.  Host arrays, or contiguous CUDA tensors (all of them) used in place and asynchronously on `stream`."""
+        space = Space("Context.pair_cost", kpts, n_persons, claimed, stream=stream)
+        if len(kpts.shape) != 5 or int(kpts.shape[1]) != self.C or int(kpts.shape[4]) != 3:
+            raise ValueError(f"kpts must be [F, C={self.C}, Pmax, kn, 3] (got shape {tuple(kpts.shape)})")
+        kpts, kcode = space.floats(kpts, "keypoints")
+        F, _, Pmax, kn, _ = (int(v) for v in kpts.shape)
+        n_persons, claimed = self._seed_lists(space, n_persons, claimed, F, Pmax)
+        NP = self.C * (self.C - 1) // 2
+        ps, pn = space.empty((F, NP, Pmax, Pmax), "float64"), space.empty((F, NP, Pmax, Pmax), "int32")
+        rc = self.L.snowtri_pair_cost(self.handle, F, kn, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(claimed), float(keypoint_score_threshold),
+                                      ptr(ps), ptr(pn), *space.tail())
+        self._reproject_status(rc, "snowtri_pair_cost")
+        return ps, pn
+
+    def _seed_lists(self, space, n_persons, claimed, F, Pmax):
+        """n_persons [F, C] and claimed [F, C, Pmax] of the seeding entries, checked in `space` (None stays None)."""
+        if n_persons is not None:
+            n_persons = space.ints(n_persons, (F, self.C), "n_persons")
+        if claimed is not None:
+            if space.device is not None and claimed.dtype == space.torch.int64:
+                claimed = claimed.to(space.torch.int32).contiguous()
+            claimed = space.ints(claimed, (F, self.C, Pmax), "claimed")
+        return n_persons, claimed
+
+    def seed_persons(self, pair_sum, pair_n, n_persons=None, claimed=None, S=None, gate=0.05, min_joints=8, min_views=3, with_flags=False,
+                     stream=None):
+        """A frame's free detections grouped into seeds (include/snowtri.h, "Seeding"; k_seed_group): pair_sum [F, NP, Pmax, Pmax]
+        float64 and pair_n int32 as pair_cost returns them (C * Pmax <= 64), n_persons, claimed as for pair_cost, S seed slots
+        (1..64; default min(64, C * Pmax // min_views)), gate an RMS line distance in world units ->
+        (seed_det_of [F, C, S] int32 in the layout of det_of, n_seeds [F] int32), with_flags: also flags [F] (SEED_FLAG_FULL).
+        Host arrays, or contiguous CUDA tensors (all of them).  Every output equals seed.seed_persons_reference bit for bit."""
+        space = Space("Context.seed_persons", pair_sum, pair_n, n_persons, claimed, stream=stream)
+        NP = self.C * (self.C - 1) // 2
+        if len(pair_sum.shape) != 4 or int(pair_sum.shape[1]) != NP or int(pair_sum.shape[2]) != int(pair_sum.shape[3]) or \
+                tuple(pair_sum.shape) != tuple(pair_n.shape):
+            raise ValueError(f"pair_sum and pair_n must both be [F, NP={NP}, Pmax, Pmax] (got shapes {tuple(pair_sum.shape)}, {tuple(pair_n.shape)})")
+        if space.device is None:
+            pair_sum = np.ascontiguousarray(pair_sum, dtype=np.float64)
+        elif pair_sum.dtype != space.torch.float64 or not space._resident(pair_sum):
+            raise ValueError("pair_sum given to Context.seed_persons must be a contiguous float64 CUDA tensor")
+        pair_n = space.ints(pair_n, pair_sum.shape, "pair_n")
+        F, Pmax = int(pair_sum.shape[0]), int(pair_sum.shape[2])
+        n_persons, claimed = self._seed_lists(space, n_persons, claimed, F, Pmax)
+        if int(min_joints) != min_joints or int(min_views) != min_views:
+            raise ValueError("min_joints and min_views must be integers")
+        if S is None:
+            S = max(1, min(64, self.C * Pmax // max(2, int(min_views))))
+        if int(S) != S:
+            raise ValueError("S must be an integer in 1..64")
+        seed_det_of, n_seeds = space.empty((F, self.C, int(S)), "int32"), space.empty((F,), "int32")
+        flags = space.empty((F,), "flags") if with_flags else None
+        rc = self.L.snowtri_seed_persons(self.handle, F, Pmax, ptr(pair_sum), ptr(pair_n), ptr(n_persons), ptr(claimed), float(gate),
+                                         int(min_joints), int(min_views), int(S), ptr(seed_det_of), ptr(n_seeds), ptr(flags), *space.tail())
+        self._reproject_status(rc, "snowtri_seed_persons")
+        return (seed_det_of, n_seeds, flags) if with_flags else (seed_det_of, n_seeds)
 
     def set_timing(self, enabled=True, attach=False):
         """attach: single-kernel calls carry the event pair on their dispatch (the kernel's own begin / end) instead of being bracketed."""

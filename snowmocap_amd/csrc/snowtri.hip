@@ -35,6 +35,7 @@
 #include "snowtri_undistort.hpp"
 #include "snowtri_reproject.hpp"
 #include "snowtri_assign.hpp"
+#include "snowtri_seed.hpp"
 #include "snowtri_refine.hpp"
 #include "snowtri_pose.hpp"
 #include "snowtri_track.hpp"
@@ -2196,6 +2197,122 @@ int snowtri_assign_detections(snowtri_ctx *ctx, int64_t n, int32_t P, int32_t Pm
     else if (W == 16) launch(std::integral_constant<int, 16>());
     else if (W == 32) launch(std::integral_constant<int, 32>());
     else launch(std::integral_constant<int, 64>());
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) {
+        HIP_TRY(hipEventRecord(ctx->ev[1], st));
+        HIP_TRY(hipEventRecord(ctx->ev[2], st));   // (no second phase: the pair (2, 3) is empty)
+        HIP_TRY(hipEventRecord(ctx->ev[3], st));
+        ctx->ev_valid = true;
+        ctx->ev_stream = st;
+    }
+    return sg.end();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------- seeding
+extern "C" {
+
+int snowtri_pair_cost(snowtri_ctx *ctx, int64_t F, int32_t kn, int32_t Pmax, const void *kpts, int kpts_dtype, const int32_t *n_persons,
+                      const int32_t *claimed, double keypoint_score_threshold, double *pair_sum, int32_t *pair_n, int memspace, void *stream) {
+    const Refuse refuse{"snowtri_pair_cost"};
+    if (!ctx) return refuse("null context");
+    if (kpts_dtype != SNOWTRI_F32 && kpts_dtype != SNOWTRI_F64) return refuse("unknown dtype");
+    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
+    if (F < 0 || kn < 1) return refuse("F < 0 or kn < 1");
+    if (Pmax < 1) return refuse("Pmax < 1");
+    if (ctx->C < 2 || ctx->C > kSeedMaxCams) return refuse("the pair cost takes 2 to 8 cameras");
+    if (kn > kSeedMaxJoints) return refuse("kn must not exceed 256 joints (four per lane of the wave that owns a detection)");
+    if (keypoint_score_threshold != keypoint_score_threshold) return refuse("keypoint_score_threshold is NaN");
+    if (F == 0) return SNOWTRI_OK;   // (looks at no pointer)
+    // one workgroup per (frame, camera pair) on a one-dimensional grid; 64-bit element offsets
+    const int C = ctx->C, NP = ctx->npairs;
+    const int64_t pp = (int64_t)Pmax * Pmax;
+    if (F > (int64_t)0x7fffffff / NP) return refuse("F * C (C - 1) / 2 must not exceed 2^31 - 1 workgroups");
+    if (pp > ((int64_t)1 << 48) / (F * NP) || (int64_t)Pmax * kn > ((int64_t)1 << 48) / (F * C))
+        return refuse("F * NP * Pmax * Pmax must not exceed 2^48 costs, F * C * Pmax * kn 2^48 keypoints");
+    if (!kpts || !pair_sum || !pair_n) return refuse("null array (kpts, pair_sum or pair_n)");
+    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)kpts) & (dtype_size(kpts_dtype) - 1)) || (((uintptr_t)pair_sum) & 7u) ||
+                                       ((((uintptr_t)pair_n) | ((uintptr_t)n_persons) | ((uintptr_t)claimed)) & 3u)))
+        return refuse("kpts, n_persons, claimed, pair_sum and pair_n must be aligned to their element size");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_wg = F * NP, n_cost = n_wg * pp;
+    const void *dk = kpts;
+    const int32_t *dnp = n_persons, *dcl = claimed;
+    double *ds = pair_sum;
+    int32_t *dn = pair_n;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&dk, dtype_size(kpts_dtype) * 3 * (size_t)F * C * Pmax * kn);
+    sg.in(&dnp, sizeof(int32_t) * (size_t)F * C);
+    sg.in(&dcl, sizeof(int32_t) * (size_t)F * C * Pmax);
+    sg.out(&ds, sizeof(double) * (size_t)n_cost);
+    sg.out(&dn, sizeof(int32_t) * (size_t)n_cost);
+    if (int rc = sg.begin()) return rc;
+    const int RT = seed_tile_dets(Pmax, kn), waves = std::min<int>(kSeedMaxWaves, Pmax);
+    const size_t lds = sizeof(double) * 3 * (size_t)RT * kn;
+    if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0], st));   // snowtri_set_timing: the kernel between the pair snowtri_last_kernel_ms reads
+    if (kpts_dtype == SNOWTRI_F32)
+        hipLaunchKernelGGL((k_pair_cost<float>), dim3((unsigned)n_wg), dim3(64 * waves), lds, st, n_wg, C, NP, (int)Pmax, (int)kn, RT,
+                           keypoint_score_threshold, ctx->rig(), (const float *)dk, dnp, dcl, ds, dn);
+    else
+        hipLaunchKernelGGL((k_pair_cost<double>), dim3((unsigned)n_wg), dim3(64 * waves), lds, st, n_wg, C, NP, (int)Pmax, (int)kn, RT,
+                           keypoint_score_threshold, ctx->rig(), (const double *)dk, dnp, dcl, ds, dn);
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) {
+        HIP_TRY(hipEventRecord(ctx->ev[1], st));
+        HIP_TRY(hipEventRecord(ctx->ev[2], st));   // (no second phase: the pair (2, 3) is empty)
+        HIP_TRY(hipEventRecord(ctx->ev[3], st));
+        ctx->ev_valid = true;
+        ctx->ev_stream = st;
+    }
+    return sg.end();
+}
+
+int snowtri_seed_persons(snowtri_ctx *ctx, int64_t F, int32_t Pmax, const double *pair_sum, const int32_t *pair_n, const int32_t *n_persons,
+                         const int32_t *claimed, double gate, int32_t min_joints, int32_t min_views, int32_t S, int32_t *seed_det_of,
+                         int32_t *n_seeds, uint32_t *flags, int memspace, void *stream) {
+    const Refuse refuse{"snowtri_seed_persons"};
+    // (the context is looked at after the arguments that need none)
+    if (memspace != SNOWTRI_HOST && memspace != SNOWTRI_DEVICE) return refuse("unknown memspace");
+    if (F < 0) return refuse("F < 0");
+    if (Pmax < 1) return refuse("Pmax < 1");
+    if (S < 1 || S > 64) return refuse("S must lie in 1..64");
+    if (min_joints < 1) return refuse("min_joints < 1");
+    if (!(gate >= 0.0)) return refuse("gate must be >= 0 and not NaN");
+    if (!(gate <= kSeedMaxGate)) return refuse("gate must not exceed 1e150 (the means are compared with gate * gate, which must stay finite)");
+    if (!ctx) return refuse("null context");
+    const int C = ctx->C;
+    if (C < 2) return refuse("the context needs at least 2 cameras");
+    if ((int64_t)C * Pmax > kSeedMaxNodes) return refuse("C * Pmax must not exceed 64 (the nodes of a frame are the lanes of one wave)");
+    if (min_views < 2 || min_views > C) return refuse("min_views must lie in 2..C");
+    if (F == 0) return SNOWTRI_OK;   // (looks at no pointer)
+    if (F > 0x7fffffffll) return refuse("F must not exceed 2^31 - 1 workgroups");
+    if (!pair_sum || !pair_n || !seed_det_of || !n_seeds) return refuse("null array (pair_sum, pair_n, seed_det_of or n_seeds)");
+    if (memspace == SNOWTRI_DEVICE &&
+        ((((uintptr_t)pair_sum) & 7u) || ((((uintptr_t)pair_n) | ((uintptr_t)n_persons) | ((uintptr_t)claimed) | ((uintptr_t)seed_det_of) |
+                                            ((uintptr_t)n_seeds) | ((uintptr_t)flags)) & 3u)))
+        return refuse("pair_sum, pair_n, n_persons, claimed, seed_det_of, n_seeds and flags must be aligned to their element size");
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int N = C * Pmax;
+    const size_t n_cost = (size_t)F * ctx->npairs * Pmax * Pmax;
+    const double *ds = pair_sum;
+    const int32_t *dn = pair_n, *dnp = n_persons, *dcl = claimed;
+    int32_t *dso = seed_det_of, *dns = n_seeds;
+    uint32_t *dfl = flags;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    sg.in(&ds, sizeof(double) * n_cost);
+    sg.in(&dn, sizeof(int32_t) * n_cost);
+    sg.in(&dnp, sizeof(int32_t) * (size_t)F * C);
+    sg.in(&dcl, sizeof(int32_t) * (size_t)F * C * Pmax);
+    sg.out(&dso, sizeof(int32_t) * (size_t)F * C * S);
+    sg.out(&dns, sizeof(int32_t) * (size_t)F);
+    sg.out(&dfl, sizeof(uint32_t) * (size_t)F);
+    if (int rc = sg.begin()) return rc;
+    if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0], st));
+    hipLaunchKernelGGL(k_seed_group, dim3((unsigned)F), dim3(64), sizeof(double) * (size_t)N * N, st, F, C, (int)Pmax, (int)S, gate * gate,
+                       (int)min_joints, (int)min_views, (const int32_t *)ctx->dpairs, ds, dn, dnp, dcl, dso, dns, dfl);
     HIP_TRY(hipGetLastError());
     if (ctx->timing) {
         HIP_TRY(hipEventRecord(ctx->ev[1], st));

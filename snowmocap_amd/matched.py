@@ -13,7 +13,7 @@ camera that does not list the person has the observation (0, 0, 0) and is in no 
 and then get the same record: one-to-one is the matcher's business.
 
 Left out on purpose: ShardedTrackPipeline, more than 8 cameras, matching against the previous frame's persons (tracking by
-reprojection), seeding new persons from person_of's unclaimed detections.
+reprojection).  (Seeding new persons from person_of's unclaimed detections: snowmocap_amd/seed.py.)
 """
 from __future__ import annotations
 

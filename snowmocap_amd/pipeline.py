@@ -41,7 +41,7 @@ class TrackPipeline:
         self.bt.close()
 
     def run(self, kpts, n_persons=None, check=True, ragged="reference", track_gate=0.3, track_max_missed=8, fill_gaps=0, despike=None,
-            reproject=None, refine=None, one_to_one=False, retriangulate=None):
+            reproject=None, refine=None, one_to_one=False, retriangulate=None, seed=None):
         """kpts [F, C, Pmax, J, 3] (NumPy or CUDA tensor; raw-frame pixels if D was given) ->
         dict of CUDA tensors: xyzs [F, P, kn, 4] (triangulated), smoothed [F, P, kn, 4], points [F, P, 24, 4],
         valid [F, P, 24], points_smoothed [F, P, 24, 4], count [F], flags [F], tracked [F] (P = n_persons_out slots).
@@ -112,9 +112,24 @@ class TrackPipeline:
         (int32 bit mask of the cameras used, 0: the record was kept) and retri_resid [F, P, kn] (RMS px, 0 where kept), both in the
         triangulation's list order.  With refine= as well the refinement reuses this det_of (its own gate_px is then not used) and
         is given retri_views as its `views`, all ones where the record was kept.  None (the default): off, nothing changes and no
-        key is added."""
+        key is added.
+        seed=gate or (gate, min_views, min_joints) (the last two default to 3 and 8): persons the first pass MISSED are seeded from
+        the detections nobody claimed, right after the retriangulation merge and before refine=.  It needs retriangulate= together
+        with one_to_one=True (ValueError otherwise, before any work): that matching step is where person_of on the undistorted
+        keypoints comes from.  seed.triangulate_seeded (k_pair_cost, k_seed_group, k_dlt_matched) runs with claimed = person_of,
+        S = n_persons_out slots, gate an RMS line distance in world units, and the retriangulation's reproj_threshold_px and
+        max_drops; seed i < min(n_seeds[f], n_persons_out - count[f]) is written to slot count[f] + i of xyzs -- a slot that holds
+        zeros otherwise, so no measured record is lost -- and count[f] is raised by that number; flags stay the first pass's.
+        Everything downstream (the ragged rules, tracking, despiking, filling, the filters) takes the raised count.  Adds seeded
+        [F, P] (bool) and seed_det_of [F, C, P] (the detections of a seeded slot, -1 everywhere else); retri_views / retri_resid of a
+        seeded slot are the seed triangulation's, and refine= sees the seed's det_of and views mask there.  A slot that is not seeded
+        keeps its bits.  None (the default): off, nothing changes and no key is added."""
         from .matched import retriangulate_args
+        from .seed import seed_option
         rtr = retriangulate_args(retriangulate)
+        sdo = seed_option(seed)
+        if sdo and not (rtr and one_to_one):
+            raise ValueError("seed= needs retriangulate= together with one_to_one=True: their matching step says which detections nobody claimed")
         if one_to_one and reproject is None and refine is None and rtr is None:
             raise ValueError("one_to_one=True needs reproject=, refine= or retriangulate=: it chooses how their matching step pairs persons "
                              "and detections")
@@ -123,7 +138,7 @@ class TrackPipeline:
             from .reproject import assign_gate
             for gate in ([reproject] if reproject is not None else []) + ([rfn[1]] if rfn else []) + ([rtr[0]] if rtr else []):
                 assign_gate(gate)
-        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn, one_to_one, rtr)
+        res = self._run(kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn, one_to_one, rtr, sdo)
         if reproject is not None:
             self._add_reprojection(res, kpts, n_persons, float(reproject), one_to_one)
         return res
@@ -170,17 +185,42 @@ class TrackPipeline:
 
     def _retriangulate(self, xyzs, n_persons, rtr, one_to_one=False):
         """run(retriangulate=...): the first pass's records against the undistorted keypoints of the call that made them
-        -> (merged records, retri_views, retri_resid, det_of)."""
+        -> (merged records, retri_views, retri_resid, det_of, person_of: assign_detections' with one_to_one, else None)."""
         import torch
         gate_px, tau, max_drops = rtr
         ukpts = self._undistorted()
         ctx, thr = self.bt.ctx, float(self.th["keypoint_score_threshold"])
         xyzs = xyzs.contiguous()
         cost_sum, cost_n = ctx.reproject_cost(xyzs, ukpts, n_persons=n_persons, keypoint_score_threshold=thr)
-        det_of = self._match(cost_sum, cost_n, gate_px, one_to_one)[0]
+        det_of, _, person_of = self._match(cost_sum, cost_n, gate_px, one_to_one)
         again, _, views, resid = ctx.triangulate_matched(ukpts, det_of=det_of, n_persons=n_persons, keypoint_score_threshold=thr,
                                                          reproj_threshold_px=tau, max_drops=max_drops, dtype=xyzs.dtype, diagnostics=True)
-        return torch.where((views != 0)[..., None], again, xyzs), views, resid, det_of
+        return torch.where((views != 0)[..., None], again, xyzs), views, resid, det_of, person_of
+
+    def _seed(self, xyzs, count, n_persons, person_of, rtr, sdo, retri_views, retri_resid, det_of):
+        """run(seed=...): persons seeded from the detections person_of left unclaimed, written behind the first pass's persons
+        -> (records, retri_views, retri_resid, det_of, the raised count, seeded [F, P], seed_det_of [F, C, P])."""
+        import torch
+        from .seed import triangulate_seeded
+        gate, min_views, min_joints = sdo
+        P, ctx, thr = self.P, self.bt.ctx, float(self.th["keypoint_score_threshold"])
+        sd = triangulate_seeded(ctx, self._undistorted(), n_persons=n_persons, claimed=person_of, S=P, gate=gate, min_views=min_views,
+                                min_joints=min_joints, keypoint_score_threshold=thr, reproj_threshold_px=rtr[1], max_drops=rtr[2],
+                                diagnostics=True, dtype=xyzs.dtype)
+        first = count.to(torch.int64).clamp(min=0, max=P)                                    # the slots the first pass holds
+        taken = torch.minimum(sd["n_seeds"].to(torch.int64), P - first)
+        i = torch.arange(P, device=xyzs.device)[None, :] - first[:, None]                    # slot -> seed index
+        seeded = (i >= 0) & (i < taken[:, None])
+        src = i.clamp(min=0, max=P - 1)
+        per_joint = lambda a: torch.gather(a, 1, src[:, :, None].expand(-1, -1, a.shape[2]))   # noqa: E731
+        seed_det = torch.gather(sd["seed_det_of"].to(det_of.dtype), 2, src[:, None, :].expand(-1, det_of.shape[1], -1))
+        xyzs = torch.where(seeded[:, :, None, None], torch.gather(sd["xyzs"], 1, src[:, :, None, None].expand(-1, -1, *xyzs.shape[2:])), xyzs)
+        retri_views = torch.where(seeded[:, :, None], per_joint(sd["views"]), retri_views)
+        retri_resid = torch.where(seeded[:, :, None], per_joint(sd["resid"]), retri_resid)
+        det_of = torch.where(seeded[:, None, :], seed_det, det_of)
+        seed_det_of = torch.where(seeded[:, None, :], seed_det, -1).to(torch.int32)
+        return xyzs.contiguous(), retri_views.contiguous(), retri_resid.contiguous(), det_of.contiguous(), \
+            (count + taken.to(count.dtype)).contiguous(), seeded, seed_det_of
 
     def _refine(self, xyzs, n_persons, rfn, one_to_one=False, matched=None):
         """run(refine=...): the triangulated records against the undistorted keypoints of the call that made them
@@ -198,7 +238,8 @@ class TrackPipeline:
         return ctx.refine_joints(xyzs, ukpts, det_of=det_of, n_persons=n_persons, views=views, keypoint_score_threshold=thr, iters=iters,
                                  score_weights=score_weights, diagnostics=True)
 
-    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None, one_to_one=False, rtr=None):
+    def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None, one_to_one=False, rtr=None,
+             sdo=None):
         """run() without its reprojection keys."""
         dsp = despike_args(despike)
         import torch
@@ -211,9 +252,16 @@ class TrackPipeline:
         L, h = self.bt.ctx.L, self.bt.ctx.handle
         st = _lib.ptr(torch.cuda.current_stream(dev).cuda_stream)
         tri = self.bt.run_torch(kpts, n_persons)
+        xyzs, matched, count = tri["xyzs"], None, tri["count"]
+        if rtr:
+            xyzs, retri_views, retri_resid, det_of, person_of = self._retriangulate(xyzs, n_persons, rtr, one_to_one)
+            if sdo:                                      # (the checks below read the raised count)
+                xyzs, retri_views, retri_resid, det_of, count, seeded, seed_det_of = self._seed(xyzs, count, n_persons, person_of, rtr, sdo,
+                                                                                                 retri_views, retri_resid, det_of)
+            matched = (det_of, retri_views)
         tracked = None                                   # None: every slot of every frame
         if check:
-            cnt = tri["count"].cpu().numpy()
+            cnt = count.cpu().numpy()
             flg = tri["flags"].cpu().numpy()
             if (flg & _lib.FLAG_SINGULAR).any():    # the reference's np.linalg.inv raises (triangulation.py:26)
                 raise np.linalg.LinAlgError(f"Singular matrix (frame {int(np.argmax((flg & _lib.FLAG_SINGULAR) != 0))})")
@@ -224,10 +272,6 @@ class TrackPipeline:
                 if F and int(cnt[0]) > self.P:
                     raise ValueError(f"frame 0 resolved to {int(cnt[0])} persons, the track has {self.P} slots (n_persons_out)")
                 tracked = np.minimum(cnt, int(cnt[0]) if F else 0).astype(np.int32)
-        xyzs, matched = tri["xyzs"], None
-        if rtr:
-            xyzs, retri_views, retri_resid, det_of = self._retriangulate(xyzs, n_persons, rtr, one_to_one)
-            matched = (det_of, retri_views)
         if rfn:
             xyzs, refine_cost, refine_codes = self._refine(xyzs, n_persons, rfn, one_to_one, matched)
         th = self.th
@@ -286,7 +330,7 @@ class TrackPipeline:
         if ragged == "track":
             from .tracking import PersonTracker, bridge_track_ids
             trk_out = PersonTracker(self.bt.ctx, S=self.P, center_point_index=self.bt.params.center_point_index, gate=track_gate,
-                                    max_missed=track_max_missed).run_torch(xyzs, tri["count"], gather=True, carry=False)
+                                    max_missed=track_max_missed).run_torch(xyzs, count, gather=True, carry=False)
             listed, xyzs = xyzs, trk_out["xyzs_tracked"]
             tid = trk_out["track_id"].cpu().numpy()                          # the host decides which frames a track covers
             if fill_gaps:
@@ -301,7 +345,7 @@ class TrackPipeline:
                 for one in np.unique(tid[:, i][tid[:, i] >= 0]):
                     filter_rows(xyzs, torch.from_numpy(np.nonzero(tid[:, i] == one)[0]).to(dev), i, sm, pts_s, filled, codes, desp, scodes)
             present = trk_out["person_of"] >= 0
-            res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"], flags=tri["flags"],
+            res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=count, flags=tri["flags"],
                        tracked=present.sum(dim=1).to(torch.int32), present=present, track_id=trk_out["track_id"],
                        slot_of=trk_out["slot_of"], track_flags=trk_out["flags"], xyzs_listed=listed)
             if fill_gaps:
@@ -316,6 +360,8 @@ class TrackPipeline:
                 res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
             if rtr:
                 res["retri_views"], res["retri_resid"] = retri_views, retri_resid
+            if sdo:
+                res["seeded"], res["seed_det_of"] = seeded, seed_det_of
             return res
         if tracked is None:
             src = xyzs
@@ -345,7 +391,7 @@ class TrackPipeline:
             pts_s = torch.zeros_like(pts)
             for i in range(int(tracked[0]) if F else 0):
                 filter_rows(xyzs, torch.nonzero(trk > i).view(-1), i, sm, pts_s, filled, codes, desp, scodes)
-        res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=tri["count"],
+        res = dict(xyzs=xyzs, smoothed=sm, points=pts, valid=val, points_smoothed=pts_s, count=count,
                    flags=tri["flags"], tracked=trk)
         if fill_gaps:
             res["xyzs_filled"], res["fill"] = filled, codes
@@ -355,6 +401,8 @@ class TrackPipeline:
             res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
         if rtr:
             res["retri_views"], res["retri_resid"] = retri_views, retri_resid
+        if sdo:
+            res["seeded"], res["seed_det_of"] = seeded, seed_det_of
         return res
 
     @staticmethod
