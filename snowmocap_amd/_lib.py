@@ -148,6 +148,8 @@ _SIGNATURES = {
                                              ct.c_int, _c_p]),
     "snowtri_refine_joints": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                          ct.c_double, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_refine_joints_ex": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
+                                            ct.c_double, ct.c_int32, ct.c_uint32, ct.c_double, _c_p, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_triangulate_matched": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, ct.c_double,
                                                ct.c_double, ct.c_int32, _c_p, _c_p, ct.c_int, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_pair_cost": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, ct.c_double, _c_p, _c_p, ct.c_int, _c_p]),
@@ -157,6 +159,9 @@ _SIGNATURES = {
     "snowtri_refine_cameras": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                           ct.c_double, ct.c_uint32, ct.c_int32, ct.c_int32, ct.c_uint32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                           ct.c_int, _c_p]),
+    "snowtri_refine_cameras_ex": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
+                                             ct.c_double, ct.c_uint32, ct.c_int32, ct.c_int32, ct.c_uint32, ct.c_double, _c_p, _c_p, _c_p, _c_p,
+                                             _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_last_kernel_ms": (ct.c_int, [_c_p, ct.POINTER(ct.c_float * 2)]),
     "snowtri_set_timing": (ct.c_int, [_c_p, ct.c_int]),
     "snowtri_timing_collect": (ct.c_int, [_c_p, _c_p, ct.c_int32]),
@@ -499,6 +504,16 @@ class Context:
         out = (det_of,) + ((person_of,) if with_person_of else ()) + ((total,) if with_total else ())
         return out if len(out) > 1 else det_of
 
+    @staticmethod
+    def _huber(huber_px):
+        """huber_px -> None (the squared loss: None or 0) or delta > 0, checked: finite, >= 0 and at most 1e150."""
+        if huber_px is None:
+            return None
+        d = float(huber_px)
+        if not (d >= 0.0 and d <= 1e150):
+            raise ValueError(f"huber_px must be finite, >= 0 and at most 1e150 (got {huber_px!r})")
+        return d if d > 0.0 else None
+
     def _refine_in(self, space, xyzs, kpts, n_persons, det_of, views, iters):
         """The inputs refine_joints and refine_cameras share, checked in `space` ->
         (xyzs, its dtype code, F, P, kn, kpts, its dtype code, Pmax, n_persons, det_of, views)."""
@@ -525,7 +540,7 @@ class Context:
         return xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views
 
     def refine_joints(self, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, iters=4,
-                      score_weights=False, diagnostics=False, out=None, stream=None):
+                      score_weights=False, diagnostics=False, out=None, stream=None, huber_px=None):
         """Joint records xyzs [F, P, kn, 4] moved to a local minimum of their reprojection error against the detections kpts
         [F, C, Pmax, kn, 3] on the undistorted frame (include/snowtri.h, "Refinement"; at most `iters` Gauss-Newton steps, a record's
         cost never rises, scores untouched).  det_of [F, C, P]: the detection of camera c that shows person p (match_detections'
@@ -534,7 +549,11 @@ class Context:
         its observation's score instead of 1.  Host arrays, or contiguous CUDA tensors (all of them) used in place and
         asynchronously on `stream`.  out: xyzs itself refines in place (default: a new array).
         -> the refined records, or (records, cost [F, P, kn, 2] float64: E before and after, codes [F, P, kn] uint8: REFINE_*)
-        with diagnostics=True."""
+        with diagnostics=True.  huber_px (delta > 0 in pixels; None or 0: the squared loss, today's entry and today's results): the
+        Huber loss of include/snowtri.h, "Refinement", ROBUST LOSS (snowtri_refine_joints_ex); with diagnostics=True a fourth result,
+        outliers [F, P, kn] (uint32, int32 in torch): bit c = camera c is a view of the record and in the linear regime at the
+        output point.  views & ~outliers is an inlier mask; fewer than two bits in it mark a record its inliers do not fix."""
+        huber_px = self._huber(huber_px)
         space = Space("Context.refine_joints", xyzs, kpts, n_persons, det_of, views, stream=stream)
         xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views = self._refine_in(space, xyzs, kpts, n_persons, det_of, views, iters)
         if out is None:
@@ -543,6 +562,14 @@ class Context:
             raise ValueError("out must be None (a new array) or xyzs itself (in place)")
         cost = space.empty((F, P, kn, 2), "float64") if diagnostics else None
         codes = space.empty((F, P, kn), "uint8") if diagnostics else None
+        if huber_px is not None:
+            outliers = space.empty((F, P, kn), "flags") if diagnostics else None
+            rc = self.L.snowtri_refine_joints_ex(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of),
+                                                 ptr(views), float(keypoint_score_threshold), int(iters),
+                                                 REFINE_SCORE_WEIGHTS if score_weights else 0, huber_px, ptr(out), ptr(cost), ptr(codes),
+                                                 ptr(outliers), *space.tail())
+            self._reproject_status(rc, "snowtri_refine_joints_ex")
+            return (out, cost, codes, outliers) if diagnostics else out
         rc = self.L.snowtri_refine_joints(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of), ptr(views),
                                           float(keypoint_score_threshold), int(iters), REFINE_SCORE_WEIGHTS if score_weights else 0, ptr(out),
                                           ptr(cost), ptr(codes), *space.tail())
@@ -550,7 +577,7 @@ class Context:
         return (out, cost, codes) if diagnostics else out
 
     def refine_cameras(self, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None, min_obs=64,
-                       iters=8, score_weights=False, diagnostics=False, stream=None):
+                       iters=8, score_weights=False, diagnostics=False, stream=None, huber_px=None):
         """The rig's poses moved to a local minimum of every free camera's reprojection error against the detections kpts
         [F, C, Pmax, kn, 3] on the undistorted frame, the joint records xyzs [F, P, kn, 4] held fixed (include/snowtri.h, "Camera pose
         refinement"; at most `iters` Gauss-Newton steps on six parameters per camera, a camera's cost never rises).  det_of, n_persons,
@@ -559,7 +586,10 @@ class Context:
         arrays, or contiguous CUDA tensors (all of them) used in place and asynchronously on `stream`; ONE call in flight per context.
         THE CONTEXT'S RIG IS NOT CHANGED: build a new Context from what is returned.
         -> (R [C, 3, 3], t [C, 3]) float64, or (R, t, report) with diagnostics=True: report = dict(cost [C, 2]: E before and after,
-        n_obs [C] int64, codes [C] uint8: POSE_*, normal [C, 28]: E, g[6], H[21] at the input pose)."""
+        n_obs [C] int64, codes [C] uint8: POSE_*, normal [C, 28]: E, g[6], H[21] at the input pose).  huber_px (delta > 0 in pixels;
+        None or 0: the squared loss, today's entry and no new key): the Huber loss ("Camera pose refinement", ROBUST LOSS;
+        snowtri_refine_cameras_ex), and the report gains n_outliers [C] int64: the observations in the linear regime at the output pose."""
+        huber_px = self._huber(huber_px)
         space = Space("Context.refine_cameras", xyzs, kpts, n_persons, det_of, views, stream=stream)
         xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views = self._refine_in(space, xyzs, kpts, n_persons, det_of, views, iters)
         if int(min_obs) != min_obs:
@@ -568,6 +598,16 @@ class Context:
         R, t = space.empty((self.C, 3, 3), "float64"), space.empty((self.C, 3), "float64")
         rep = dict(cost=space.empty((self.C, 2), "float64"), n_obs=space.empty((self.C,), "int64"), codes=space.empty((self.C,), "uint8"),
                    normal=space.empty((self.C, 28), "float64")) if diagnostics else dict(cost=None, n_obs=None, codes=None, normal=None)
+        if huber_px is not None:
+            if diagnostics:
+                rep["n_outliers"] = space.empty((self.C,), "int64")
+            rc = self.L.snowtri_refine_cameras_ex(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of),
+                                                  ptr(views), float(keypoint_score_threshold), mask, int(min_obs), int(iters),
+                                                  REFINE_SCORE_WEIGHTS if score_weights else 0, huber_px, ptr(R), ptr(t), ptr(rep["cost"]),
+                                                  ptr(rep["n_obs"]), ptr(rep["codes"]), ptr(rep["normal"]), ptr(rep.get("n_outliers")),
+                                                  *space.tail())
+            self._reproject_status(rc, "snowtri_refine_cameras_ex")
+            return (R, t, rep) if diagnostics else (R, t)
         rc = self.L.snowtri_refine_cameras(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of), ptr(views),
                                            float(keypoint_score_threshold), mask, int(min_obs), int(iters),
                                            REFINE_SCORE_WEIGHTS if score_weights else 0, ptr(R), ptr(t), ptr(rep["cost"]), ptr(rep["n_obs"]),

@@ -139,7 +139,7 @@ class CameraGroup:
         rig's moved to a local minimum of every free camera's reprojection error of the joint records xyzs [F, P, kn, 4] against
         the detections kpts [F, C, Pmax, kn, 3] on the UNDISTORTED frame; K, D and everything else are copied.  This group is left
         untouched.  kwargs: those of pose.refine_cameras (det_of, n_persons, views, keypoint_score_threshold, free, min_obs, iters,
-        score_weights); with diagnostics=True -> (group, report).  Host arrays, like the other methods of the group."""
+        score_weights, huber_px: the Huber loss, and report["n_outliers"]); with diagnostics=True -> (group, report).  Host arrays, like the other methods of the group."""
         diagnostics = bool(kwargs.pop("diagnostics", False))
         R, t, report = self.native_context().refine_cameras(np.asarray(xyzs), np.asarray(kpts), diagnostics=True, **kwargs)
         n = self.camera_num

@@ -2378,41 +2378,95 @@ struct ObservedInputs {
     }
 };
 
+constexpr double kHuberMaxPx = 1e150;   // delta * delta must stay finite (the bound of snowtri_assign_detections' gate)
+
+// huber_px of the two _ex entries -> 0, or the status of a refusal; hc: the loss' constants, formed once here in fp64
+// (all 0 for huber_px == 0, the squared loss).
+int huber_check(const Refuse &refuse, double huber_px, HuberConst &hc) {
+    if (!(huber_px >= 0.0)) return refuse("huber_px must be >= 0 and not NaN");
+    if (!(huber_px <= kHuberMaxPx)) return refuse("huber_px must not exceed 1e150 (huber_px * huber_px must stay finite)");
+    hc.d = huber_px;
+    hc.two_d = 2.0 * huber_px;
+    hc.dd = huber_px * huber_px;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+namespace {
+int refine_joints_impl(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+                       const void *kpts, int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                       double keypoint_score_threshold, int32_t iters, uint32_t flags, double huber_px, void *out_xyzs, double *cost,
+                       uint8_t *codes, uint32_t *outliers, int memspace, void *stream);
+}
 
 int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
                           int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
                           double keypoint_score_threshold, int32_t iters, uint32_t flags, void *out_xyzs, double *cost, uint8_t *codes,
                           int memspace, void *stream) {
-    const char *who = "snowtri_refine_joints";
+    return refine_joints_impl("snowtri_refine_joints", ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views,
+                              keypoint_score_threshold, iters, flags, 0.0, out_xyzs, cost, codes, nullptr, memspace, stream);
+}
+
+int snowtri_refine_joints_ex(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
+                             int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                             double keypoint_score_threshold, int32_t iters, uint32_t flags, double huber_px, void *out_xyzs, double *cost,
+                             uint8_t *codes, uint32_t *outliers, int memspace, void *stream) {
+    return refine_joints_impl("snowtri_refine_joints_ex", ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views,
+                              keypoint_score_threshold, iters, flags, huber_px, out_xyzs, cost, codes, outliers, memspace, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int refine_joints_impl(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+                       const void *kpts, int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                       double keypoint_score_threshold, int32_t iters, uint32_t flags, double huber_px, void *out_xyzs, double *cost,
+                       uint8_t *codes, uint32_t *outliers, int memspace, void *stream) {
     if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, 0u, kpts_dtype, memspace)) return rc;
     const Refuse refuse{who};
+    HuberConst hc{};
+    if (int rc = huber_check(refuse, huber_px, hc)) return rc;
     ObservedInputs in;
     if (int rc = in.check(refuse, ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views, keypoint_score_threshold, iters,
                           flags, SNOWTRI_REFINE_SCORE_WEIGHTS, memspace))
         return rc;
     if (F == 0) return SNOWTRI_OK;
     if (!out_xyzs) return refuse("null array (out_xyzs)");
-    if (memspace == SNOWTRI_DEVICE && ((((uintptr_t)out_xyzs) & (dtype_size(xyz_dtype) - 1)) || (((uintptr_t)cost) & 7u)))
-        return refuse("out_xyzs and cost must be aligned to their element size");
+    if (memspace == SNOWTRI_DEVICE &&
+        ((((uintptr_t)out_xyzs) & (dtype_size(xyz_dtype) - 1)) || (((uintptr_t)cost) & 7u) || (((uintptr_t)outliers) & 3u)))
+        return refuse("out_xyzs, cost and outliers must be aligned to their element size");
     // a lane reads its record and writes it at the same place: out_xyzs == xyzs is that; any other overlap lets one lane's store
     // reach another lane's load
     if (out_xyzs != xyzs && (uintptr_t)xyzs < (uintptr_t)out_xyzs + in.x_bytes && (uintptr_t)out_xyzs < (uintptr_t)xyzs + in.x_bytes)
         return refuse("out_xyzs must be xyzs itself or not overlap it");
+    // outliers is written by the lane that read record i: it must not reach any lane's record, in xyzs or in out_xyzs
+    const size_t o_bytes = sizeof(uint32_t) * (size_t)in.n_rec;
+    auto overlaps = [](const void *a, size_t na, const void *b, size_t nb) {
+        return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+    };
+    if (outliers && (overlaps(outliers, o_bytes, xyzs, in.x_bytes) || overlaps(outliers, o_bytes, out_xyzs, in.x_bytes)))
+        return refuse("outliers must not overlap xyzs or out_xyzs");
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n_rec = in.n_rec;
     void *d_out = out_xyzs;
     double *d_cost = cost;
     uint8_t *d_codes = codes;
+    uint32_t *d_outl = outliers;
+    const bool huber = huber_px > 0.0;
     Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
     in.stage(sg);
     sg.out(&d_out, in.x_bytes);
     sg.out(&d_cost, sizeof(double) * 2 * (size_t)n_rec);
     sg.out(&d_codes, (size_t)n_rec);
+    sg.out(&d_outl, o_bytes);
     if (int rc = sg.begin()) return rc;
+    // the squared loss (huber_px == 0) has no view in the linear regime: its kernel writes no outliers, they are zeros
+    if (!huber && d_outl) HIP_TRY(hipMemsetAsync(d_outl, 0, o_bytes, st));
     // (a DEVICE call with out_xyzs == xyzs passes one pointer twice: the kernel declares neither of the two restrict)
     const dim3 grid((unsigned)((n_rec + kRefineBlock - 1) / kRefineBlock));
     const int C = ctx->C;
@@ -2420,9 +2474,10 @@ int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, co
         with_float_pair(xyz_dtype, kpts_dtype, [&](auto tx, auto tk) {
             using TX = decltype(tx);
             using TK = decltype(tk);
-            hipLaunchKernelGGL((k_refine<decltype(ct)::value, TX, TK>), grid, dim3(kRefineBlock), 0, st, n_rec, C, (int)P, (int)Pmax, (int)kn,
-                               keypoint_score_threshold, (int)iters, flags, (const double *)ctx->dProj, (const TX *)in.dx, (const TK *)in.dk,
-                               in.dnp, in.ddet, in.dviews, (TX *)d_out, d_cost, d_codes);
+            const auto kernel = huber ? k_refine<decltype(ct)::value, TX, TK, true> : k_refine<decltype(ct)::value, TX, TK, false>;
+            hipLaunchKernelGGL(kernel, grid, dim3(kRefineBlock), 0, st, n_rec, C, (int)P, (int)Pmax, (int)kn, keypoint_score_threshold,
+                               (int)iters, flags, (const double *)ctx->dProj, (const TX *)in.dx, (const TK *)in.dk, in.dnp, in.ddet, in.dviews,
+                               (TX *)d_out, d_cost, d_codes, hc, huber ? d_outl : nullptr);
         });
     };
     if (C == 4) launch(std::integral_constant<int, 4>());
@@ -2432,9 +2487,17 @@ int snowtri_refine_joints(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, co
     return sg.end();
 }
 
-}  // extern "C"
+}  // namespace
 
 // ------------------------------------------------------------------------------- camera pose refinement
+namespace {
+int refine_cameras_impl(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+                        const void *kpts, int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                        double keypoint_score_threshold, uint32_t free_mask, int32_t min_obs, int32_t iters, uint32_t flags, double huber_px,
+                        double *R_out, double *t_out, double *cost, int64_t *n_obs, uint8_t *codes, double *normal, int64_t *n_outliers,
+                        int memspace, void *stream);
+}
+
 extern "C" {
 
 int snowtri_pose_sweep_records(void) { return kPoseGridCap * kPoseBlock; }
@@ -2443,9 +2506,38 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
                            int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
                            double keypoint_score_threshold, uint32_t free_mask, int32_t min_obs, int32_t iters, uint32_t flags, double *R_out,
                            double *t_out, double *cost, int64_t *n_obs, uint8_t *codes, double *normal, int memspace, void *stream) {
-    const char *who = "snowtri_refine_cameras";
+    return refine_cameras_impl("snowtri_refine_cameras", ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views,
+                               keypoint_score_threshold, free_mask, min_obs, iters, flags, 0.0, R_out, t_out, cost, n_obs, codes, normal, nullptr,
+                               memspace, stream);
+}
+
+int snowtri_refine_cameras_ex(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
+                              int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                              double keypoint_score_threshold, uint32_t free_mask, int32_t min_obs, int32_t iters, uint32_t flags,
+                              double huber_px, double *R_out, double *t_out, double *cost, int64_t *n_obs, uint8_t *codes, double *normal,
+                              int64_t *n_outliers, int memspace, void *stream) {
+    return refine_cameras_impl("snowtri_refine_cameras_ex", ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views,
+                               keypoint_score_threshold, free_mask, min_obs, iters, flags, huber_px, R_out, t_out, cost, n_obs, codes, normal,
+                               n_outliers, memspace, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int refine_cameras_impl(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+                        const void *kpts, int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                        double keypoint_score_threshold, uint32_t free_mask, int32_t min_obs, int32_t iters, uint32_t flags, double huber_px,
+                        double *R_out, double *t_out, double *cost, int64_t *n_obs, uint8_t *codes, double *normal, int64_t *n_outliers,
+                        int memspace, void *stream) {
     if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, 0u, kpts_dtype, memspace)) return rc;
     const Refuse refuse{who};
+    HuberConst hc{};
+    if (int rc = huber_check(refuse, huber_px, hc)) return rc;
+    const bool huber = huber_px > 0.0;
+#ifdef SNOWTRI_POSE_PER_RECORD
+    if (huber) return refuse("the per-record development kernel has no Huber instantiation");
+#endif
     ObservedInputs in;   // (F == 0 is work here: no input pointer is looked at, only k_pose_step runs, every pose is copied)
     if (int rc = in.check(refuse, ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views, keypoint_score_threshold, iters,
                           flags, SNOWTRI_REFINE_SCORE_WEIGHTS, memspace))
@@ -2453,15 +2545,16 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
     if (min_obs < 3) return refuse("min_obs must be at least 3 (six parameters, two equations per observation)");
     if (ctx->C < 32 && (free_mask >> ctx->C)) return refuse("free_mask has a bit at or above the number of cameras");
     if (!R_out || !t_out) return refuse("null array (R_out or t_out)");
-    if (memspace == SNOWTRI_DEVICE && (((uintptr_t)R_out | (uintptr_t)t_out | (uintptr_t)cost | (uintptr_t)n_obs | (uintptr_t)normal) & 7u))
-        return refuse("R_out, t_out, cost, n_obs and normal must be aligned to their element size");
+    if (memspace == SNOWTRI_DEVICE &&
+        (((uintptr_t)R_out | (uintptr_t)t_out | (uintptr_t)cost | (uintptr_t)n_obs | (uintptr_t)normal | (uintptr_t)n_outliers) & 7u))
+        return refuse("R_out, t_out, cost, n_obs, normal and n_outliers must be aligned to their element size");
     const int C = ctx->C;
     const int64_t n_rec = in.n_rec;
     ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     if (!ctx->pose_ws) HIP_TRY(hipMalloc(&ctx->pose_ws, sizeof(double) * pose_ws_doubles(C)));   // the first call on this context, and no later one
     double *dR = R_out, *dt = t_out, *d_cost = cost, *d_normal = normal;
-    int64_t *d_nobs = n_obs;
+    int64_t *d_nobs = n_obs, *d_noutl = n_outliers;
     uint8_t *d_codes = codes;
     Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
     in.stage(sg);
@@ -2471,6 +2564,7 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
     sg.out(&d_nobs, sizeof(int64_t) * (size_t)C);
     sg.out(&d_codes, (size_t)C);
     sg.out(&d_normal, sizeof(double) * 28 * (size_t)C);
+    sg.out(&d_noutl, sizeof(int64_t) * (size_t)C);
     if (int rc = sg.begin()) return rc;
     double *ws = ctx->pose_ws;
     const double *base = (const double *)ctx->dProj;
@@ -2486,21 +2580,23 @@ int snowtri_refine_cameras(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, c
 #ifdef SNOWTRI_POSE_PER_RECORD   // (a development build: the shape that lost, EXPERIMENTS.md round 22)
                 const auto kernel = k_pose_normal_rec<TX, TK>;
                 const dim3 grid((unsigned)G);
-#else
-                const auto kernel = k_pose_normal<TX, TK>;
-                const dim3 grid((unsigned)G, (unsigned)C);
-#endif
                 hipLaunchKernelGGL(kernel, grid, dim3(kPoseBlock), 0, st, n_rec, C, (int)P, (int)Pmax, (int)kn, keypoint_score_threshold, flags, base,
                                    trial, active, (const TX *)in.dx, (const TK *)in.dk, in.dnp, in.ddet, in.dviews, ws + pose_ws_partials(C));
+#else
+                const auto kernel = huber ? k_pose_normal<TX, TK, true> : k_pose_normal<TX, TK, false>;
+                const dim3 grid((unsigned)G, (unsigned)C);
+                hipLaunchKernelGGL(kernel, grid, dim3(kPoseBlock), 0, st, n_rec, C, (int)P, (int)Pmax, (int)kn, keypoint_score_threshold, flags, base,
+                                   trial, active, (const TX *)in.dx, (const TK *)in.dk, in.dnp, in.ddet, in.dviews, ws + pose_ws_partials(C), hc);
+#endif
             });
         hipLaunchKernelGGL(k_pose_step, dim3(1), dim3(kPoseStepBlock), 0, st, C, G, e, e == n_eval ? 1 : 0, free_mask, (int)min_obs, base, ws, dR, dt,
-                           d_cost, d_nobs, d_codes, d_normal);
+                           d_cost, d_nobs, d_codes, d_normal, d_noutl);
     }
     HIP_TRY(hipGetLastError());
     return sg.end();
 }
 
-}  // extern "C"
+}  // namespace
 
 // ------------------------------------------------------------------------------- fused A1..A4
 namespace {

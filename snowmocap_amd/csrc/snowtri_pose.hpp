@@ -20,6 +20,12 @@
 // Exp(omega) R, the next trial pose and the camera's flag; behind the last evaluation it writes the outputs.  Contraction is off in
 // the whole kernel: E(trial) < E and the pivots decide, and the solve is the NumPy rule's operation for operation.
 //
+// HUBER == true (include/snowtri.h, ROBUST LOSS; snowtri_refine_cameras_ex with huber_px > 0) is a second instantiation of
+// k_pose_normal: the loss of snowtri_refine.hpp's huber_terms per observation -- w rho in E, the IRLS weight w kappa in H and g, kappa
+// formed again in every evaluation -- and the count of the observations in the linear regime in slot 30 of the partial, which the
+// squared-loss instantiation leaves 0 as before.  k_pose_step keeps that count with the state of the pose it belongs to and writes
+// n_outliers behind the last evaluation.
+//
 // Every result is written with ordinary vector stores; no floating-point atomics anywhere.
 #pragma once
 #include "snowtri_refine.hpp"
@@ -28,10 +34,10 @@ namespace snowtri {
 
 constexpr int kPoseBlock = 256;
 constexpr int kPoseGridCap = 1024;       // blocks per camera: one sweep of the grid covers kPoseGridCap * 256 records
-constexpr int kPosePartial = 32;         // doubles per partial: E, g[6], H[21], n, invalid, two of padding
+constexpr int kPosePartial = 32;         // doubles per partial: E, g[6], H[21], n, invalid, linear-regime count (HUBER; else 0), padding
 constexpr int kPoseSegments = 32;        // k_pose_step adds a camera's partials in this many runs of consecutive blocks
 constexpr int kPoseStepBlock = 1024;
-constexpr int kPoseStateStride = 32;     // per camera: E, g[6], H[21] at the current pose, E at the input, n, code, padding
+constexpr int kPoseStateStride = 32;     // per camera: E, g[6], H[21] at the current pose, E at the input, n, code, linear-regime count
 enum : uint8_t { kPoseFixed = 0, kPoseFewObs = 1, kPoseKept = 2, kPoseMoved = 3 };
 
 // the context's workspace, in doubles: trial [C][kProjStride] | cur [C][kProjStride] | state [C][kPoseStateStride] |
@@ -45,8 +51,10 @@ __host__ __device__ inline size_t pose_ws_doubles(int C) { return pose_ws_partia
 
 // One observation's terms at the trial pose q: E in the rule's plain operations, the 2 x 6 Jacobian at delta = 0
 // (dpc / domega = R^T [d]x, dpc / dtau = -R^T), H (lower triangle, row by row) and g with fma.  -> valid at the trial pose.
+// HUBER: w rho in E, w kappa in H and g; lin: the observation is in the linear regime.
+template <bool HUBER>
 __device__ __forceinline__ bool pose_add_obs(double (&acc)[28], const double *__restrict__ q, double ou, double ov, double w, double X, double Y,
-                                             double Z) {
+                                             double Z, const HuberConst &hc, bool &lin) {
 #pragma clang fp contract(off)
     const double fx = q[12], sk = q[13], fy = q[15];
     const double d0 = X - q[9], d1 = Y - q[10], d2 = Z - q[11];
@@ -57,7 +65,15 @@ __device__ __forceinline__ bool pose_add_obs(double (&acc)[28], const double *__
     const double u = (fx * x + sk * y) + q[14], v = fy * y + q[16];
     const bool valid = pc2 > 0.0 && finite_f64(u) && finite_f64(v);
     const double ru = u - ou, rv = v - ov;
-    acc[0] = acc[0] + w * (ru * ru + rv * rv);
+    if constexpr (HUBER) {
+        double rho, kappa;
+        lin = huber_terms(hc, ru * ru + rv * rv, rho, kappa);
+        acc[0] = acc[0] + w * rho;
+        w = w * kappa;   // the IRLS weight
+    } else {
+        lin = false;
+        acc[0] = acc[0] + w * (ru * ru + rv * rv);
+    }
     // H and g only steer: fused multiply-adds from here on
     const double iz = 1.0 / pc2;
     double du[6], dv[6];
@@ -116,15 +132,16 @@ __device__ __forceinline__ bool pose_record(const TX *__restrict__ xyzs, int64_t
 
 // xyzs [F][P][kn][4], kpts [F][C][Pmax][kn][3], n_persons [F][C] or null, det_of [F][C][P] or null, views [F][P][kn] or null;
 // base: the input pose table (fixes the observation sets), trial: the table the sums are formed at, active [C] or null (null:
-// every camera) -> partials [G][C][kPosePartial]; n_rec = F * P * kn, G = gridDim.x, C = gridDim.y
-template <typename TX, typename TK>
+// every camera) -> partials [G][C][kPosePartial]; n_rec = F * P * kn, G = gridDim.x, C = gridDim.y.  HUBER: the loss hc
+template <typename TX, typename TK, bool HUBER = false>
 __global__ __launch_bounds__(kPoseBlock) void k_pose_normal(int64_t n_rec, int C, int P, int Pmax, int kn, double kthr, uint32_t flags,
                                                             const double *__restrict__ base, const double *__restrict__ trial,
                                                             const int32_t *__restrict__ active, const TX *__restrict__ xyzs,
                                                             const TK *__restrict__ kpts, const int32_t *__restrict__ n_persons,
                                                             const int32_t *__restrict__ det_of, const uint32_t *__restrict__ views,
-                                                            double *__restrict__ partials) {
+                                                            double *__restrict__ partials, HuberConst hc) {
     const int c = blockIdx.y;
+    SNOWTRI_DEV_CHECK(!HUBER || (hc.d > 0.0 && hc.dd > 0.0 && finite_f64(hc.dd)), 107);
     SNOWTRI_DEV_CHECK(c >= 0 && c < C && (int)gridDim.y == C && C <= kRefineMaxCams && (int)gridDim.x <= kPoseGridCap && Pmax >= 1 &&
                           (det_of || P <= Pmax), 102);
     if (active && !active[c]) return;   // (block-uniform: nobody waits at the barrier below)
@@ -135,6 +152,8 @@ __global__ __launch_bounds__(kPoseBlock) void k_pose_normal(int64_t n_rec, int C
 #pragma unroll
     for (int k = 0; k < 28; k++) acc[k] = 0.0;
     double n_in = 0.0, n_bad = 0.0;   // (counts as doubles: exact up to 2^53, and they travel with the sums)
+    [[maybe_unused]] double n_lin = 0.0;
+    constexpr int kSums = HUBER ? 31 : 30;   // what a block adds up: acc[28], n_in, n_bad and, with the loss, n_lin
     for (int64_t i = blockIdx.x * (int64_t)kPoseBlock + threadIdx.x; i < n_rec; i += (int64_t)gridDim.x * kPoseBlock) {
         int64_t f;
         int p, j;
@@ -143,17 +162,19 @@ __global__ __launch_bounds__(kPoseBlock) void k_pose_normal(int64_t n_rec, int C
         const uint32_t allowed = views ? views[i] : 0xffffffffu;
         const bool listed = refine_observation(kpts, n_persons, det_of, f, c, C, P, Pmax, kn, p, j, ou, ov, os);
         if (refine_admits(q0, measured, listed, ou, ov, os, kthr, allowed, c, X, Y, Z)) {   // k_refine's own rule 1
-            const bool valid = pose_add_obs(acc, q, ou, ov, score_w ? os : 1.0, X, Y, Z);
+            bool lin;
+            const bool valid = pose_add_obs<HUBER>(acc, q, ou, ov, score_w ? os : 1.0, X, Y, Z, hc, lin);
             n_in += 1.0;
             n_bad += valid ? 0.0 : 1.0;
+            if constexpr (HUBER) n_lin += lin ? 1.0 : 0.0;
         }
     }
     // the block's partial: a fixed butterfly over the wave, then the four waves in wave order
     __shared__ double lds[kPoseBlock / 64][kPosePartial];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < 30; k++) {
-        double v = k < 28 ? acc[k] : (k == 28 ? n_in : n_bad);
+    for (int k = 0; k < kSums; k++) {
+        double v = k < 28 ? acc[k] : (k == 28 ? n_in : k == 29 ? n_bad : n_lin);
 #pragma unroll
         for (int w = 32; w >= 1; w >>= 1) v += __shfl_xor(v, w, 64);
         if (lane == 0) lds[wave][k] = v;
@@ -162,7 +183,7 @@ __global__ __launch_bounds__(kPoseBlock) void k_pose_normal(int64_t n_rec, int C
     if (threadIdx.x < kPosePartial) {
         const int k = threadIdx.x;
         double v = 0.0;
-        if (k < 30) v = ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
+        if (k < kSums) v = ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
         partials[((size_t)blockIdx.x * C + c) * kPosePartial + k] = v;
     }
 }
@@ -206,7 +227,8 @@ __global__ __launch_bounds__(kPoseBlock) void k_pose_normal_rec(int64_t n_rec, i
             double n_in = 0.0, n_bad = 0.0;
             const bool listed = refine_observation(kpts, n_persons, det_of, f, c, C, P, Pmax, kn, p, j, ou, ov, os);
             if (live && refine_admits(base + (size_t)c * kProjStride, measured, listed, ou, ov, os, kthr, allowed, c, X, Y, Z)) {
-                const bool valid = pose_add_obs(term, trial + (size_t)c * kProjStride, ou, ov, score_w ? os : 1.0, X, Y, Z);
+                bool lin_;
+                const bool valid = pose_add_obs<false>(term, trial + (size_t)c * kProjStride, ou, ov, score_w ? os : 1.0, X, Y, Z, HuberConst{}, lin_);
                 n_in = 1.0;
                 n_bad = valid ? 0.0 : 1.0;
             }
@@ -294,7 +316,7 @@ __global__ __launch_bounds__(kPoseStepBlock) void k_pose_step(int C, int G, int 
                                                               const double *__restrict__ base, double *__restrict__ ws,
                                                               double *__restrict__ R_out, double *__restrict__ t_out, double *__restrict__ cost,
                                                               int64_t *__restrict__ n_obs, uint8_t *__restrict__ codes,
-                                                              double *__restrict__ normal) {
+                                                              double *__restrict__ normal, int64_t *__restrict__ n_outliers) {
 #pragma clang fp contract(off)
     __shared__ double seg_sum[kPoseSegments][kPosePartial];
     __shared__ double tot[kRefineMaxCams][kPosePartial];
@@ -340,6 +362,7 @@ __global__ __launch_bounds__(kPoseStepBlock) void k_pose_step(int C, int G, int 
         const bool is_free = (free_mask >> c) & 1u, few = sum[28] < (double)min_obs;
         st[28] = sum[0];
         st[29] = sum[28];
+        st[31] = sum[30];   // the observations in the linear regime at the pose the state is of (0 under the squared loss)
         st[30] = !is_free ? (double)kPoseFixed : few ? (double)kPoseFewObs : (double)kPoseKept;
         act = is_free && !few;
     } else if (active[c]) {
@@ -348,6 +371,7 @@ __global__ __launch_bounds__(kPoseStepBlock) void k_pose_step(int C, int G, int 
             for (int k = 0; k < 12; k++) cu[k] = tr[k];
             for (int k = 0; k < 28; k++) st[k] = sum[k];
             st[30] = (double)kPoseMoved;
+            st[31] = sum[30];
         }
         act = accept;
     } else
@@ -374,6 +398,7 @@ __global__ __launch_bounds__(kPoseStepBlock) void k_pose_step(int C, int G, int 
         }
         if (n_obs) n_obs[c] = (int64_t)st[29];
         if (codes) codes[c] = (uint8_t)code;
+        if (n_outliers) n_outliers[c] = still ? 0 : (int64_t)st[31];
     }
 }
 

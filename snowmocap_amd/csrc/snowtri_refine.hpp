@@ -23,6 +23,13 @@
 // pass that fixes the view set.  The iteration is a wave loop, while (__any(active)); every select is per lane, so a settled lane
 // keeps its bits whatever its wave-mates still do, and a record's output depends on its own record, its own observations and the
 // rig only.
+//
+// HUBER == true (include/snowtri.h, ROBUST LOSS; snowtri_refine_joints_ex with huber_px > 0) is a second instantiation of the same
+// kernel: per view s = ru ru + rv rv is compared with delta^2, a view beyond it adds (2 delta) sqrt(s) - delta^2 to E and weighs
+// delta / sqrt(s) of w in H and g (IRLS; kappa is formed again in every evaluation, nothing is held per view), and the evaluation
+// carries the mask of the views in the linear regime, which behind the last accepted step is the `outliers` word.  The sqrt is the
+// correctly rounded one and E stays in the rule's plain operations.  HUBER == false compiles to the instructions it did before the
+// switch existed (what the loss adds is under if constexpr).
 #pragma once
 #include "snowtri_reproject.hpp"
 
@@ -38,6 +45,22 @@ struct RefineEval {
     double E, h00, h10, h11, h20, h21, h22, g0, g1, g2;
     bool valid;   // every view of the set projects validly
 };
+
+// The loss' constants, formed once in fp64 on the host: delta, 2 delta, delta^2 (all 0 and unused under the squared loss).
+struct HuberConst {
+    double d, two_d, dd;
+};
+
+// ROBUST LOSS on one view's s = ru ru + rv rv, every operation rounded on its own: -> in the linear regime; rho and kappa.
+__device__ __forceinline__ bool huber_terms(const HuberConst &hc, double s, double &rho, double &kappa) {
+#pragma clang fp contract(off)
+    const bool lin = !(s <= hc.dd);
+    const double r = __dsqrt_rn(s);   // correctly rounded, as the NumPy rule's
+    const double t = hc.two_d * r;
+    rho = lin ? t - hc.dd : s;
+    kappa = lin ? hc.d / r : 1.0;
+    return lin;
+}
 
 // project_record's rules 1 and 3 on a measured record's point, kept open: -> pc2 > 0 and finite u, v.
 __device__ __forceinline__ bool refine_view(const double *__restrict__ q, double X, double Y, double Z, double &x, double &y, double &iz,
@@ -82,8 +105,11 @@ __device__ __forceinline__ bool refine_admits(const double *__restrict__ q, bool
 
 // One view's terms of E, H and g at X: w ((u - ou)^2 + (v - ov)^2), w J^T J, w J^T r with the 2 x 3 Jacobian
 // dx = (R^T row 0 - x R^T row 2) / pc2, dy likewise, du = fx dx + s dy, dv = fy dy.  in == false: exact zeros.
-__device__ __forceinline__ void refine_add_view(RefineEval &e, const double *__restrict__ q, bool in, double ou, double ov, double w, double X,
-                                                double Y, double Z) {
+// HUBER: w rho in E, w kappa in H and g; -> the view is in the linear regime (false under the squared loss and for in == false,
+// whose s is 0).
+template <bool HUBER>
+__device__ __forceinline__ bool refine_add_view(RefineEval &e, const double *__restrict__ q, bool in, double ou, double ov, double w, double X,
+                                                double Y, double Z, const HuberConst &hc) {
 #pragma clang fp contract(off)
     // THE COST IS THE RULE'S, OPERATION FOR OPERATION: E decides every step and is what the caller is told, so it is formed as
     // include/snowtri.h and refine_joints_reference write it -- every product, sum and quotient rounded on its own, in their order,
@@ -98,7 +124,15 @@ __device__ __forceinline__ void refine_add_view(RefineEval &e, const double *__r
     const double u = (fx * x + sk * y) + q[14], v = fy * y + q[16];
     e.valid = e.valid && ((pc2 > 0.0 && finite_f64(u) && finite_f64(v)) || !in);
     const double ru = in ? u - ou : 0.0, rv = in ? v - ov : 0.0;
-    e.E = e.E + w * (ru * ru + rv * rv);
+    bool lin = false;
+    if constexpr (HUBER) {
+        double rho, kappa;
+        lin = huber_terms(hc, ru * ru + rv * rv, rho, kappa);
+        e.E = e.E + w * rho;
+        w = w * kappa;   // the IRLS weight (w * 1.0 is w: the quadratic regime is the squared rule operation for operation)
+    } else {
+        e.E = e.E + w * (ru * ru + rv * rv);
+    }
     // H and g only steer: fused multiply-adds from here on
     const double iz = in ? 1.0 / pc2 : 0.0;
     x = in ? x : 0.0;
@@ -117,6 +151,7 @@ __device__ __forceinline__ void refine_add_view(RefineEval &e, const double *__r
     e.g0 = fma(wu0, ru, fma(wv0, rv, e.g0));
     e.g1 = fma(wu1, ru, fma(wv1, rv, e.g1));
     e.g2 = fma(wu2, ru, fma(wv2, rv, e.g2));
+    return lin;
 }
 
 // H d = -g by LDL^T; -> every pivot is finite and > 0 (d is meaningful only then).
@@ -140,13 +175,14 @@ __device__ __forceinline__ bool refine_solve(const RefineEval &e, double &s0, do
 }
 
 // xyzs / out [F][P][kn][4] (out may be xyzs itself), kpts [F][C][Pmax][kn][3], n_persons [F][C] or null, det_of [F][C][P] or null,
-// views [F][P][kn] or null -> out, cost [F][P][kn][2] or null, codes [F][P][kn] or null; n_rec = F * P * kn
-template <int CT, typename TX, typename TK>
+// views [F][P][kn] or null -> out, cost [F][P][kn][2] or null, codes [F][P][kn] or null; n_rec = F * P * kn.  HUBER: the loss hc
+// and -> outliers [F][P][kn] or null (bit c: camera c is a view and in the linear regime at the output point; 0 for a copied record)
+template <int CT, typename TX, typename TK, bool HUBER = false>
 __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, int P, int Pmax, int kn, double kthr, int iters, uint32_t flags,
                                                          const double *__restrict__ proj, const TX *xyzs, const TK *__restrict__ kpts,
                                                          const int32_t *__restrict__ n_persons, const int32_t *__restrict__ det_of,
                                                          const uint32_t *__restrict__ views, TX *out, double *__restrict__ cost,
-                                                         uint8_t *__restrict__ codes) {
+                                                         uint8_t *__restrict__ codes, HuberConst hc, uint32_t *__restrict__ outliers) {
 #pragma clang fp contract(off)   // comparisons decide here (E(X + d) < E(X), the pivots): nothing is left to the place of inlining
     static_assert(CT == 0 || (CT >= 2 && CT <= 8), "k_refine: observations in registers for up to eight cameras");
     constexpr int kRegs = CT > 0 ? CT : 1;
@@ -159,6 +195,7 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
     const int p = pj / kn, j = pj - p * kn;
     const int nc = CT > 0 ? CT : C;
     SNOWTRI_DEV_CHECK(f >= 0 && p >= 0 && p < P && j >= 0 && j < kn && (CT == 0 || CT == C) && C <= kRefineMaxCams && (det_of || P <= Pmax), 97);
+    SNOWTRI_DEV_CHECK(HUBER ? (hc.d > 0.0 && hc.dd > 0.0 && finite_f64(hc.dd)) : outliers == nullptr, 106);
     const Rec4<TX> r = reinterpret_cast<const Rec4<TX> *>(xyzs)[i];
     const double rx = (double)r.x, ry = (double)r.y, rz = (double)r.z, rs = (double)r.s;
     const bool measured = rs != 0.0 && finite_f64(rx) && finite_f64(ry) && finite_f64(rz) && finite_f64(rs);
@@ -202,15 +239,17 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
     V = few ? 0u : V;
     bool active = live && measured && !few;
 
-    auto evaluate = [&](double ex, double ey, double ez) -> RefineEval {
+    auto evaluate = [&](double ex, double ey, double ez, uint32_t &lin) -> RefineEval {
         RefineEval e = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, true};
+        lin = 0u;
         if constexpr (CT > 0) {
 #pragma unroll
             for (int c = 0; c < CT; c++) {
                 // a camera's seventeen constants are loaded (scalar loads, from the cache) where its terms are formed: hoisted out
                 // of the iteration they are 17 CT doubles held in, and spilled from, scalar registers
                 asm volatile("" ::: "memory");
-                refine_add_view(e, proj + (size_t)c * kProjStride, (V >> c) & 1u, ou[c], ov[c], ow[c], ex, ey, ez);
+                const bool l_ = refine_add_view<HUBER>(e, proj + (size_t)c * kProjStride, (V >> c) & 1u, ou[c], ov[c], ow[c], ex, ey, ez, hc);
+                if constexpr (HUBER) lin |= l_ ? (1u << c) : 0u;
             }
         } else {
 #pragma unroll 1
@@ -218,14 +257,17 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
                 double u_, v_, s_;
                 observation(c, u_, v_, s_);
                 const bool in = (V >> c) & 1u;
-                refine_add_view(e, proj + (size_t)c * kProjStride, in, in ? u_ : 0.0, in ? v_ : 0.0, in ? (score_w ? s_ : 1.0) : 0.0, ex, ey, ez);
+                const bool l_ = refine_add_view<HUBER>(e, proj + (size_t)c * kProjStride, in, in ? u_ : 0.0, in ? v_ : 0.0,
+                                                       in ? (score_w ? s_ : 1.0) : 0.0, ex, ey, ez, hc);
+                if constexpr (HUBER) lin |= l_ ? (1u << c) : 0u;
             }
         }
         return e;
     };
 
     // ---- rules 3 and 4
-    RefineEval cur = evaluate(X, Y, Z);
+    uint32_t cur_lin, nxt_lin;   // the views in the linear regime at the current point and at the trial (HUBER only)
+    RefineEval cur = evaluate(X, Y, Z, cur_lin);
     const double E0 = cur.E;
     bool moved = false;
     int it = 0;
@@ -234,7 +276,7 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
         const bool pd = refine_solve(cur, s0, s1, s2);
         const double tx = X + s0, ty = Y + s1, tz = Z + s2;
         const bool tryit = active && pd;
-        const RefineEval nxt = evaluate(tryit ? tx : X, tryit ? ty : Y, tryit ? tz : Z);
+        const RefineEval nxt = evaluate(tryit ? tx : X, tryit ? ty : Y, tryit ? tz : Z, nxt_lin);
         const bool accept = tryit && nxt.valid && nxt.E < cur.E;
         X = accept ? tx : X;
         Y = accept ? ty : Y;
@@ -249,6 +291,7 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
         cur.g0 = accept ? nxt.g0 : cur.g0;
         cur.g1 = accept ? nxt.g1 : cur.g1;
         cur.g2 = accept ? nxt.g2 : cur.g2;
+        if constexpr (HUBER) cur_lin = accept ? nxt_lin : cur_lin;
         moved = moved || accept;
         active = accept;
         ++it;
@@ -268,6 +311,8 @@ __global__ __launch_bounds__(kRefineBlock) void k_refine(int64_t n_rec, int C, i
         cost[2 * i + 1] = copied ? 0.0 : cur.E;
     }
     if (codes) codes[i] = !measured ? kRefineMissing : few ? kRefineFewViews : moved ? kRefineMoved : kRefineKept;
+    if constexpr (HUBER)
+        if (outliers) outliers[i] = copied ? 0u : (cur_lin & V);   // (a plain vector store)
 }
 
 }  // namespace snowtri

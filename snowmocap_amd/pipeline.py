@@ -96,6 +96,11 @@ class TrackPipeline:
         keypoint_score_threshold.  With D the triangulator's own undistorted copy of the keypoints is reused (no second k_undistort
         pass).  Adds refine_codes [F, P, kn] (uint8, refine.REFINE_*) and refine_cost [F, P, kn, 2] (px^2 before and after), both in
         the triangulation's list order.  None (the default): off, nothing changes and no key is added.
+        refine=(iters, gate_px, score_weights, huber_px) with huber_px > 0: the refinement minimises the Huber loss of
+        include/snowtri.h, "Refinement", ROBUST LOSS, instead of the squared error (delta = huber_px pixels: a view further off than
+        that pulls with a constant force, not a growing one), and refine_outliers [F, P, kn] (int32 bit mask: camera c is a view of
+        the record and beyond delta at the refined point) is added beside refine_codes, in the same order.  A huber_px of None or 0
+        is the triple: no bit changes and no key is added.
         one_to_one=True: the matching step of reproject= and of refine= is reproject.assign_detections (k_assign: the optimal
         assignment per frame and camera with the same gate, at most one person per detection) instead of match_detections.  A person
         whose only detections inside the gate went to persons they fit better is then unmatched in that view (det_of -1) instead of
@@ -224,9 +229,10 @@ class TrackPipeline:
 
     def _refine(self, xyzs, n_persons, rfn, one_to_one=False, matched=None):
         """run(refine=...): the triangulated records against the undistorted keypoints of the call that made them
-        -> (refined records, cost, codes).  matched: (det_of, retri_views) of run(retriangulate=...), used instead of a matching step."""
+        -> (refined records, cost, codes), and with a Huber loss (a fourth entry in rfn) the outliers mask as well.  matched: (det_of, retri_views) of run(retriangulate=...), used instead of a matching step."""
         import torch
-        iters, gate_px, score_weights = rfn
+        iters, gate_px, score_weights = rfn[:3]
+        huber_px = rfn[3] if len(rfn) > 3 else None
         ukpts = self._undistorted()
         ctx, thr = self.bt.ctx, float(self.th["keypoint_score_threshold"])
         xyzs = xyzs.contiguous()
@@ -236,7 +242,7 @@ class TrackPipeline:
         else:
             det_of, views = matched[0], torch.where(matched[1] != 0, matched[1], -1).contiguous()   # a kept record: every camera
         return ctx.refine_joints(xyzs, ukpts, det_of=det_of, n_persons=n_persons, views=views, keypoint_score_threshold=thr, iters=iters,
-                                 score_weights=score_weights, diagnostics=True)
+                                 score_weights=score_weights, diagnostics=True, huber_px=huber_px)
 
     def _run(self, kpts, n_persons, check, ragged, track_gate, track_max_missed, fill_gaps, despike, rfn=None, one_to_one=False, rtr=None,
              sdo=None):
@@ -273,7 +279,7 @@ class TrackPipeline:
                     raise ValueError(f"frame 0 resolved to {int(cnt[0])} persons, the track has {self.P} slots (n_persons_out)")
                 tracked = np.minimum(cnt, int(cnt[0]) if F else 0).astype(np.int32)
         if rfn:
-            xyzs, refine_cost, refine_codes = self._refine(xyzs, n_persons, rfn, one_to_one, matched)
+            xyzs, refine_cost, refine_codes, *refine_outliers = self._refine(xyzs, n_persons, rfn, one_to_one, matched)
         th = self.th
         fzrd =(float(th["smooth_f"]), float(th["smooth_z"]), float(th["smooth_r"]), float(th["smooth_delta_time"]))
         fill_gaps = int(fill_gaps)
@@ -358,6 +364,8 @@ class TrackPipeline:
                 res["xyzs_despiked"], res["spike_codes"] = desp, scodes
             if rfn:
                 res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
+                if refine_outliers:
+                    res["refine_outliers"] = refine_outliers[0]
             if rtr:
                 res["retri_views"], res["retri_resid"] = retri_views, retri_resid
             if sdo:
@@ -399,6 +407,8 @@ class TrackPipeline:
             res["xyzs_despiked"], res["spike_codes"] = desp, scodes
         if rfn:
             res["refine_cost"], res["refine_codes"] = refine_cost, refine_codes
+            if refine_outliers:
+                res["refine_outliers"] = refine_outliers[0]
         if rtr:
             res["retri_views"], res["retri_resid"] = retri_views, retri_resid
         if sdo:
