@@ -141,7 +141,8 @@ const char *snowtri_ctx_overrides(const snowtri_ctx *ctx);
  * 26 -> 20 us per call), without the caller creating streams or twin contexts.  The calls must be independent (distinct
  * output buffers; inputs ready on `stream` when the call is made).  Results become visible to the caller's stream at
  * snowtri_ctx_join(ctx, stream) -- `stream` then waits for every call issued since the last join -- or after
- * snowtri_ctx_synchronize.  SNOWTRI_HOST calls are synchronous and ignore the mode.
+ * snowtri_ctx_synchronize.  SNOWTRI_HOST calls are synchronous and ignore the mode.  An overlapped call whose `stream` is
+ * capturing a hipGraph is refused with SNOWTRI_ERR_BAD_ARG (GRAPH CAPTURE below).
  * Ordering rule: an overlapped call owns the scratch set of ITS internal stream (one set per stream, none of them the
  * caller's); every other entry point -- host calls, snowtri_triangulate / snowtri_condense_resident, device calls made
  * with the mode off -- works on the caller's own set, ordered by the stream it is given.  So entry points may be mixed
@@ -159,11 +160,37 @@ int snowtri_ctx_set_robust(snowtri_ctx *ctx, double reproj_threshold_px, int32_t
  * the chip at least twice (a segment holds >= 4 frames per CU) runs as two segments that alternate between the caller's stream
  * and ONE internal stream (fork / join events inside the call, results ordered behind `stream` as always): the latency-bound
  * kernels of one segment run beside the VALU-bound ones of the other (8 cameras x 4 persons: +8 %).  Outputs do not depend on
- * the cut (tested bit for bit).  segments = 1: the whole call stays on the caller's stream -- for a caller that captures the call
- * into a hipGraph on one stream, or profiles its kernels one at a time (scripts/pmc_multi.sh); segments = 2 .. 64: at least that
- * many segments (rounded up to an even count), small batches included; 0: the default policy again.  Not used in overlap mode
- * (whole calls alternate there). */
+ * the cut (tested bit for bit).  segments = 1: the whole call stays on the caller's stream -- for a caller that profiles its
+ * kernels one at a time (scripts/pmc_multi.sh), and what a capture of the call into a hipGraph on one stream would need (such a
+ * capture is NOT among the tested ones: GRAPH CAPTURE below); segments = 2 .. 64: at least that many segments (rounded up to an
+ * even count), small batches included; 0: the default policy again.  Not used in overlap mode (whole calls alternate there). */
 int snowtri_ctx_set_split(snowtri_ctx *ctx, int segments);
+
+/* GRAPH CAPTURE.  A SNOWTRI_DEVICE call whose entry says "asynchronous on `stream`, no host read, no allocation, no internal
+ * stream" may be captured into a hipGraph (hipStreamBeginCapture on `stream`, or torch.cuda.graph) and replayed: every per-call
+ * reset (counters, flags, tickets, the tracker's state) is a node of the graph, and launch shapes come from the call's shapes and
+ * the device, never from its data.  Replays give the bits of the eager call on the same inputs (tests/test_gpu_graph_capture.py).
+ * Captured and replayed there: snowtri_triangulate_condense[_ex] and snowtri_triangulate_robust on the single-launch routes (one
+ * detection per camera: k_fused_lean_coop, k_fused_lean, k_fused_single, k_dlt_coop, k_dlt_robust), snowtri_undistort_keypoints,
+ * snowtri_reproject, snowtri_reproject_cost, snowtri_assign_detections, snowtri_triangulate_matched, snowtri_pair_cost,
+ * snowtri_seed_persons, snowtri_refine_joints[_ex], snowtri_refine_cameras, snowtri_track_persons, snowtri_track_gather,
+ * snowtri_fill_joint_track, snowtri_despike_joint_track.  NOT verified, keep these calls outside a graph: the multi-person routes
+ * of the fused call (several detections per camera, or five and more cameras off the lean shapes: the streaming association and
+ * k_frame_recompute) and the smoothing entries (snowtri_smooth_track, snowtri_smooth_joint_track, snowtri_blender_points,
+ * snowtri_blender_smooth and the shard passes).  A graph of either kind ended the test process while the graph was destroyed;
+ * what the two share is a hipMemsetAsync node (the counter words, the scan's ticket and flags), and the cause is not established.
+ * Preconditions:
+ *   - ONE EAGER WARM-UP CALL with the same shapes, dtypes and options on the same context before the capture: scratch buffers,
+ *     the workspace of snowtri_refine_cameras, the coefficient table of snowtri_blender_smooth and the raised LDS limits are
+ *     created by the first call (hipMalloc, a blocking copy), which a capturing stream forbids;
+ *   - overlap mode off (snowtri_ctx_set_overlap(ctx, 1)): with n_streams >= 2 a call on a capturing stream is refused with
+ *     SNOWTRI_ERR_BAD_ARG before any other runtime call (the capture stays valid; snowtri_last_error() names overlap mode);
+ *   - timing off (snowtri_set_timing(ctx, 0)): the event pairs belong to the context, not to the graph;
+ *   - SNOWTRI_DEVICE only: a SNOWTRI_HOST call stages and synchronises.
+ * A graph holds POINTERS INTO THE CONTEXT'S SCRATCH: a later eager call on that context that grows the scratch (a larger shape)
+ * or snowtri_ctx_destroy ends the graph's life -- destroy the graph first, never replay it afterwards.
+ * ONE REPLAY PER CONTEXT may be in flight (replays on one stream are ordered; two graphs of one context on two streams share its
+ * scratch unordered).  The status a captured call returns is that of the capture, not of a replay. */
 
 /* Test hook (no reference counterpart): evaluates the fast reciprocal / reciprocal-square-root helpers
  * the throughput kernels use (v_rcp_f64 / v_rsq_f64 + Newton steps) on x[n]; host pointers. */
@@ -255,7 +282,8 @@ int snowtri_triangulate_condense(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int3
 /* The same call with flags (0 = exactly snowtri_triangulate_condense; an unknown bit is SNOWTRI_ERR_BAD_ARG).
  * SNOWTRI_CALL_NO_ZERO_FILL: the slots of persons >= out_count[f] -- out_xyzs[f][p >= count][.][.] and out_pscore[f][p >= count] --
  * are UNSPECIFIED after the call: the library does not spend HBM writes on them (whatever the caller's buffer held may still be
- * there, or zeros where a kernel writes them anyway).  The reference returns LISTS of out_count[f] persons
+ * there, or what a kernel writes there anyway: zeros, or -- the lean kernels in a frame that resolves to nobody -- the joint records
+ * they solved before the frame's count was known).  The reference returns LISTS of out_count[f] persons
  * (triangulation.py:154-160); the [F][Pout_max] padding is this ABI's artefact, and on a multi-person batch with a generous
  * Pout_max the zeros are most of what the call writes (BASELINE configs[2], 8 cameras x 4 persons resolving to ~5 persons per
  * frame, Pout_max 16: 234 MB of zeros beside 106 MB of results per 10 000 frames).  A caller that reads out_count[f] first --

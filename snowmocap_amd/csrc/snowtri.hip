@@ -82,6 +82,17 @@ struct DeviceGuard {
     DeviceGuard _device_guard(device);    \
     HIP_TRY(_device_guard.err)
 
+// Is the caller's stream recording a hipGraph?  (A stream whose status cannot be read counts as capturing: whatever the question
+// guards -- a query of the stream, a fork onto an internal one -- is then left undone.)
+static bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
 struct Scratch {
     void *p = nullptr;
     size_t cap = 0;
@@ -3473,8 +3484,14 @@ int fused_call(snowtri_ctx *ctx, int64_t F, int32_t Pmax, int32_t J, const void 
     int rc = validate_params(params, J, &prm, true);
     if (rc) return rc;
     prm.no_zero_fill = (call_flags & SNOWTRI_CALL_NO_ZERO_FILL) ? 1 : 0;
-    ENTER_DEVICE(ctx->device);
     hipStream_t st = (hipStream_t)stream;
+    // overlap mode queries the caller's stream and runs the call on an internal one: neither can go into a hipGraph that `stream`
+    // is recording.  Refused before any other runtime call, so the caller's capture stays valid.
+    if (memspace == SNOWTRI_DEVICE && ctx->overlap >= 2 && !explicit_rb && stream_is_capturing(st)) {
+        g_last_error = "overlap mode (snowtri_ctx_set_overlap >= 2) cannot be captured into a hipGraph: `stream` is capturing";
+        return SNOWTRI_ERR_BAD_ARG;
+    }
+    ENTER_DEVICE(ctx->device);
     ctx->cur = &ctx->sets[0];
     ctx->last_set = &ctx->sets[0];
     ctx->last_stream = false;
