@@ -181,7 +181,7 @@ int snowtri_ctx_set_split(snowtri_ctx *ctx, int segments);
  * what the two share is a hipMemsetAsync node (the counter words, the scan's ticket and flags), and the cause is not established.
  * Preconditions:
  *   - ONE EAGER WARM-UP CALL with the same shapes, dtypes and options on the same context before the capture: scratch buffers,
- *     the workspace of snowtri_refine_cameras, the coefficient table of snowtri_blender_smooth and the raised LDS limits are
+ *     the workspaces of snowtri_refine_cameras and snowtri_refine_cameras_k, the coefficient table of snowtri_blender_smooth and the raised LDS limits are
  *     created by the first call (hipMalloc, a blocking copy), which a capturing stream forbids;
  *   - overlap mode off (snowtri_ctx_set_overlap(ctx, 1)): with n_streams >= 2 a call on a capturing stream is refused with
  *     SNOWTRI_ERR_BAD_ARG before any other runtime call (the capture stays valid; snowtri_last_error() names overlap mode);
@@ -830,8 +830,48 @@ int snowtri_refine_joints_ex(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn,
  * travels with the partial sums (a count in a double, exact up to 2^53).  `normal` is E, g, H of the loss at the input pose.  Unlike
  * a `views` mask from SNOWTRI_DLT_ROBUST, whose leave-one-out gate removes exactly a nudged camera's views, the loss keeps every
  * observation and down-weights the far ones.  Refused as well: huber_px NaN, negative or above 1e150, a misaligned n_outliers.
- * NOT offered: intrinsics and lens coefficients; other losses (Cauchy, Tukey), an automatic delta, the Triggs second-order
- * correction; damping; points and cameras adjusted in one system; more than 32 cameras. */
+ * INTRINSICS (snowtri_refine_cameras_k): four more parameters per camera and two more inputs of this rule.  A chessboard K that is
+ * a percent or two off, or a lens refocused after calibration, is as common as a nudged tripod, and pose-only refinement of a
+ * camera whose K is wrong lowers its RMS by MOVING THE CAMERA.  Everything not named here stays word for word as stated above.
+ *   PARAMETERS, per camera, in this order: omega[3], tau[3], fx, fy, cx, cy.  The four intrinsics are additive: fx + d6, fy + d7,
+ *     cx + d8, cy + d9.  The skew K[0][1] and the last row of K are never changed.
+ *   intr_flags: SNOWTRI_INTR_FOCAL frees fx and fy, SNOWTRI_INTR_CENTRE frees cx and cy.  intr_mask: bit c says camera c's
+ *     intrinsics may move; it is independent of free_mask (the camera that holds the gauge of an alternation may still have its
+ *     intrinsics refined).  A camera's FREE SET is the six pose parameters if it is in free_mask, plus the flagged intrinsics if it
+ *     is in intr_mask: n = 0, 2, 4, 6, 8 or 10 parameters.
+ *   S_c is rule 1 unchanged, fixed once at the input pose and the input K.
+ *   JACOBIAN: the six pose columns of rule 3, and du/dfx = x, dv/dfx = 0; du/dfy = 0, dv/dfy = y; du/dcx = 1, dv/dcx = 0;
+ *     du/dcy = 0, dv/dcy = 1 (x = pc0 / pc2, y = pc1 / pc2).
+ *   NORMAL EQUATIONS: E, g[10], H[55] over all ten parameters whichever of them are free; H is the lower triangle of the 10 x 10
+ *     matrix row by row in the order above.  The loss of ROBUST LOSS applies as stated: w rho in E, w kappa in g and H.
+ *   A STEP: the rows and columns of the free set, in order; the same plain-operation LDL^T at size n, and a pivot that is not
+ *     finite or not > 0 ends the camera's iteration; the trial is Exp(omega) R, t + tau, fx + d6, fy + d7, cx + d8, cy + d9 (a
+ *     parameter outside the free set keeps its bits); it is ACCEPTED iff every observation of S_c is valid at it, its fx and fy are
+ *     finite and > 0, and E is strictly lower.  A rejected trial ends the iteration.
+ *   CODES: n = 0 is SNOWTRI_POSE_FIXED, n_c < min_obs SNOWTRI_POSE_FEW_OBS, otherwise KEPT or MOVED as in rule 5.
+ *   OUTPUTS: K_out [C][9] row-major, required when intr_flags != 0 (the context's K with fx, fy, cx, cy of a MOVED camera
+ *     replaced); R_out, t_out; cost, n_obs, codes, n_outliers as above; normal [C][66]: E, g[10], H[55] at the input.
+ * SUMMATION of this entry: a lane adds its records as stated under SUMMATION, the same butterfly over the wave and the four waves
+ * in order; then the blocks of a camera in 32 runs of consecutive blocks, each in block order, and the runs in order, slot by slot
+ * of the 72-double partial (three passes of 32 slots); no floating-point atomics.  It depends on (F, P, kn, C) alone: two runs give
+ * the same bits.  The sums of the six pose parameters are formed by the operations and in the order of snowtri_refine_cameras_ex.
+ * The entries of H that are structurally zero (fx.fy, fx.cy, fy.cx, cx.cy) are stored as 0.0, and cy.cy is cx.cx: both are sum w.
+ * CONSEQUENCES.  With intr_flags == 0 or intr_mask == 0 this entry is snowtri_refine_cameras_ex bit for bit on every output (of
+ * `normal` the 28 values of E, g[6] and the 6 x 6 block of H, which stand at 0, 1..6 and 11..31 of the 66), and K_out, if given, is
+ * the context's K.  A camera with its pose fixed and its intrinsics free returns R and t bit for bit; a camera outside intr_mask
+ * returns K bit for bit.  snowtri_refine_cameras and snowtri_refine_cameras_ex keep their signatures, kernels, workspace and bits.
+ * The intrinsics path has ITS OWN WORKSPACE (576 KB per camera), allocated by the first call of THIS entry on a context and by no
+ * later call; the workspace of the two entries above and its "first call only" behaviour are untouched.  ONE CALL IN FLIGHT PER
+ * CONTEXT, 2 (iters + 1) launches whatever the data does, SNOWTRI_DEVICE asynchronous with no host read.  THE CONTEXT'S OWN RIG IS
+ * NOT MODIFIED: build a new context from K_out, R_out, t_out.
+ * WHAT IT DOES NOT PROMISE.  Ten parameters need thousands of observations: the principal point and the rotation are strongly
+ * correlated (a shift of the centre and a small pan move the pixels almost alike), so with a few hundred noisy observations per
+ * camera the ten-parameter minimum is as far from the truth as a percent-level calibration error (EXPERIMENTS.md has the figures);
+ * free fewer parameters, hold the pose, or record longer.  With a lens (a distortion set on the context) the detections were
+ * undistorted with the OLD K and must be undistorted again from the raw frame once K has moved; nothing here does that.
+ * Refused as well: an unknown intr_flags bit, an intr_mask bit at or above C, intr_flags != 0 with a NULL K_out, a misaligned K_out.
+ * NOT offered: lens coefficients, the skew, a focal length shared between cameras; other losses (Cauchy, Tukey), an automatic
+ * delta, the Triggs second-order correction; damping; points and cameras adjusted in one system; more than 32 cameras. */
 #define SNOWTRI_POSE_FIXED 0
 #define SNOWTRI_POSE_FEW_OBS 1
 #define SNOWTRI_POSE_KEPT 2
@@ -851,6 +891,17 @@ int snowtri_refine_cameras_ex(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn
                               double huber_px, double *R_out /* [C][9] */, double *t_out /* [C][3] */, double *cost /* [C][2] or NULL */,
                               int64_t *n_obs /* [C] or NULL */, uint8_t *codes /* [C] or NULL */, double *normal /* [C][28] or NULL */,
                               int64_t *n_outliers /* [C] or NULL */, int memspace, void *stream);
+#define SNOWTRI_INTR_FOCAL 1u  /* intr_flags: fx and fy may move */
+#define SNOWTRI_INTR_CENTRE 2u /* intr_flags: cx and cy may move */
+int snowtri_refine_cameras_k(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax,
+                             const void *kpts, int kpts_dtype, const int32_t *n_persons /* [F][C] or NULL */,
+                             const int32_t *det_of /* [F][C][P] or NULL */, const uint32_t *views /* [F][P][kn] or NULL */,
+                             double keypoint_score_threshold, uint32_t free_mask, uint32_t intr_mask, uint32_t intr_flags,
+                             int32_t min_obs, int32_t iters, uint32_t flags, double huber_px,
+                             double *K_out /* [C][9]; may be NULL only with intr_flags == 0 */, double *R_out /* [C][9] */,
+                             double *t_out /* [C][3] */, double *cost /* [C][2] or NULL */, int64_t *n_obs /* [C] or NULL */,
+                             uint8_t *codes /* [C] or NULL */, double *normal /* [C][66] or NULL */,
+                             int64_t *n_outliers /* [C] or NULL */, int memspace, void *stream);
 
 /* Matched triangulation: the robust N-view DLT of 3D person p over the detections that det_of names (no reference counterpart).
  * The matching chain -- snowtri_reproject_cost, snowtri_assign_detections -- ends in det_of[f][c][p], the detection of camera c that

@@ -25,6 +25,7 @@ REPROJECT_RAW = 1              # snowtri_reproject / snowtri_reproject_cost: fla
 REFINE_SCORE_WEIGHTS = 1       # snowtri_refine_joints: flags -- a view weighs its observation's score
 REFINE_MISSING, REFINE_FEW_VIEWS, REFINE_KEPT, REFINE_MOVED = 0, 1, 2, 3   # ... and its codes
 POSE_FIXED, POSE_FEW_OBS, POSE_KEPT, POSE_MOVED = 0, 1, 2, 3   # snowtri_refine_cameras: codes
+INTR_FOCAL, INTR_CENTRE = 1, 2   # snowtri_refine_cameras_k: intr_flags
 POSE_SWEEP_RECORDS = 1024 * 256   # ... and the records one sweep of k_pose_normal's grid covers (snowtri_pose_sweep_records)
 SEED_FLAG_FULL = 1             # snowtri_seed_persons: flags -- the frame stopped at S seeds with a finite edge between free nodes left
 CALL_NO_ZERO_FILL = 1         # snowtri_triangulate_condense_ex: the slots behind out_count[f] are left unwritten
@@ -162,6 +163,9 @@ _SIGNATURES = {
     "snowtri_refine_cameras_ex": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
                                              ct.c_double, ct.c_uint32, ct.c_int32, ct.c_int32, ct.c_uint32, ct.c_double, _c_p, _c_p, _c_p, _c_p,
                                              _c_p, _c_p, _c_p, ct.c_int, _c_p]),
+    "snowtri_refine_cameras_k": (ct.c_int, [_c_p, ct.c_int64, ct.c_int32, ct.c_int32, _c_p, ct.c_int, ct.c_int32, _c_p, ct.c_int, _c_p, _c_p, _c_p,
+                                            ct.c_double, ct.c_uint32, ct.c_uint32, ct.c_uint32, ct.c_int32, ct.c_int32, ct.c_uint32, ct.c_double,
+                                            _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, ct.c_int, _c_p]),
     "snowtri_last_kernel_ms": (ct.c_int, [_c_p, ct.POINTER(ct.c_float * 2)]),
     "snowtri_set_timing": (ct.c_int, [_c_p, ct.c_int]),
     "snowtri_timing_collect": (ct.c_int, [_c_p, _c_p, ct.c_int32]),
@@ -577,7 +581,7 @@ class Context:
         return (out, cost, codes) if diagnostics else out
 
     def refine_cameras(self, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None, min_obs=64,
-                       iters=8, score_weights=False, diagnostics=False, stream=None, huber_px=None):
+                       iters=8, score_weights=False, diagnostics=False, stream=None, huber_px=None, intrinsics=None, intrinsics_free=None):
         """The rig's poses moved to a local minimum of every free camera's reprojection error against the detections kpts
         [F, C, Pmax, kn, 3] on the undistorted frame, the joint records xyzs [F, P, kn, 4] held fixed (include/snowtri.h, "Camera pose
         refinement"; at most `iters` Gauss-Newton steps on six parameters per camera, a camera's cost never rises).  det_of, n_persons,
@@ -588,7 +592,17 @@ class Context:
         -> (R [C, 3, 3], t [C, 3]) float64, or (R, t, report) with diagnostics=True: report = dict(cost [C, 2]: E before and after,
         n_obs [C] int64, codes [C] uint8: POSE_*, normal [C, 28]: E, g[6], H[21] at the input pose).  huber_px (delta > 0 in pixels;
         None or 0: the squared loss, today's entry and no new key): the Huber loss ("Camera pose refinement", ROBUST LOSS;
-        snowtri_refine_cameras_ex), and the report gains n_outliers [C] int64: the observations in the linear regime at the output pose."""
+        snowtri_refine_cameras_ex), and the report gains n_outliers [C] int64: the observations in the linear regime at the output pose.
+        intrinsics ("f": fx and fy, "c": cx and cy, "fc"; None, the default: the entries above, nothing changes): those intrinsics are
+        parameters too ("Camera pose refinement", INTRINSICS; snowtri_refine_cameras_k) -> (K [C, 3, 3], R, t) or (K, R, t, report)
+        with report["normal"] [C, 66] = E, g[10], H[55]; intrinsics_free: the cameras whose intrinsics may move, given like `free`
+        (None: all) and independent of it.  The first such call on a context allocates that path's own workspace."""
+        if intrinsics is not None:
+            if not isinstance(intrinsics, str) or intrinsics not in ("f", "c", "fc"):
+                raise ValueError(f'intrinsics must be None, "f", "c" or "fc" (got {intrinsics!r})')
+            return self._refine_cameras_k(xyzs, kpts, det_of, n_persons, views, keypoint_score_threshold, free, min_obs, iters, score_weights,
+                                          diagnostics, stream, huber_px, (INTR_FOCAL if "f" in intrinsics else 0) | (INTR_CENTRE if "c" in intrinsics else 0),
+                                          intrinsics_free)
         huber_px = self._huber(huber_px)
         space = Space("Context.refine_cameras", xyzs, kpts, n_persons, det_of, views, stream=stream)
         xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views = self._refine_in(space, xyzs, kpts, n_persons, det_of, views, iters)
@@ -614,6 +628,28 @@ class Context:
                                            ptr(rep["codes"]), ptr(rep["normal"]), *space.tail())
         self._reproject_status(rc, "snowtri_refine_cameras")
         return (R, t, rep) if diagnostics else (R, t)
+
+    def _refine_cameras_k(self, xyzs, kpts, det_of, n_persons, views, keypoint_score_threshold, free, min_obs, iters, score_weights, diagnostics,
+                          stream, huber_px, intr_flags, intrinsics_free):
+        """refine_cameras with intrinsics set: snowtri_refine_cameras_k."""
+        huber_px = self._huber(huber_px)
+        space = Space("Context.refine_cameras", xyzs, kpts, n_persons, det_of, views, stream=stream)
+        xyzs, code, F, P, kn, kpts, kcode, Pmax, n_persons, det_of, views = self._refine_in(space, xyzs, kpts, n_persons, det_of, views, iters)
+        if int(min_obs) != min_obs:
+            raise ValueError(f"min_obs must be an integer >= 3 (got {min_obs})")
+        mask, imask = free_mask(free, self.C), free_mask(intrinsics_free, self.C)
+        K, R, t = space.empty((self.C, 3, 3), "float64"), space.empty((self.C, 3, 3), "float64"), space.empty((self.C, 3), "float64")
+        rep = dict(cost=space.empty((self.C, 2), "float64"), n_obs=space.empty((self.C,), "int64"), codes=space.empty((self.C,), "uint8"),
+                   normal=space.empty((self.C, 66), "float64")) if diagnostics else dict(cost=None, n_obs=None, codes=None, normal=None)
+        if huber_px is not None and diagnostics:
+            rep["n_outliers"] = space.empty((self.C,), "int64")
+        rc = self.L.snowtri_refine_cameras_k(self.handle, F, P, kn, ptr(xyzs), code, Pmax, ptr(kpts), kcode, ptr(n_persons), ptr(det_of), ptr(views),
+                                             float(keypoint_score_threshold), mask, imask, int(intr_flags), int(min_obs), int(iters),
+                                             REFINE_SCORE_WEIGHTS if score_weights else 0, 0.0 if huber_px is None else huber_px, ptr(K), ptr(R),
+                                             ptr(t), ptr(rep["cost"]), ptr(rep["n_obs"]), ptr(rep["codes"]), ptr(rep["normal"]),
+                                             ptr(rep.get("n_outliers")), *space.tail())
+        self._reproject_status(rc, "snowtri_refine_cameras_k")
+        return (K, R, t, rep) if diagnostics else (K, R, t)
 
     def triangulate_matched(self, kpts, det_of=None, n_persons=None, keypoint_score_threshold=0.0, reproj_threshold_px=6.0, max_drops=1,
                             dtype=None, diagnostics=False, stream=None):

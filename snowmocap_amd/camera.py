@@ -139,9 +139,15 @@ class CameraGroup:
         rig's moved to a local minimum of every free camera's reprojection error of the joint records xyzs [F, P, kn, 4] against
         the detections kpts [F, C, Pmax, kn, 3] on the UNDISTORTED frame; K, D and everything else are copied.  This group is left
         untouched.  kwargs: those of pose.refine_cameras (det_of, n_persons, views, keypoint_score_threshold, free, min_obs, iters,
-        score_weights, huber_px: the Huber loss, and report["n_outliers"]); with diagnostics=True -> (group, report).  Host arrays, like the other methods of the group."""
+        score_weights, huber_px: the Huber loss, and report["n_outliers"]); with diagnostics=True -> (group, report).  Host arrays, like the other methods of the group.
+        intrinsics ("f", "c" or "fc", with intrinsics_free): fx, fy and / or cx, cy are refined too (INTRINSICS) and the new group
+        carries the new K; its D is copied, and belongs to detections undistorted with the old K."""
         diagnostics = bool(kwargs.pop("diagnostics", False))
-        R, t, report = self.native_context().refine_cameras(np.asarray(xyzs), np.asarray(kpts), diagnostics=True, **kwargs)
+        K = None
+        if kwargs.get("intrinsics") is not None:
+            K, R, t, report = self.native_context().refine_cameras(np.asarray(xyzs), np.asarray(kpts), diagnostics=True, **kwargs)
+        else:
+            R, t, report = self.native_context().refine_cameras(np.asarray(xyzs), np.asarray(kpts), diagnostics=True, **kwargs)
         n = self.camera_num
         info = self.camera_group_info_dict()
         group = CameraGroup(cap_ids=[], resolutions=[])
@@ -152,6 +158,8 @@ class CameraGroup:
         for i, cam in enumerate(group.cameras[:n]):       # (the context holds the first camera_num cameras)
             cam.R = np.array(R[i], dtype=np.float64).reshape(np.asarray(self.cameras[i].R).shape)
             cam.t = np.array(t[i], dtype=np.float64).reshape(np.asarray(self.cameras[i].t).shape)
+            if K is not None:
+                cam.K = np.array(K[i], dtype=np.float64).reshape(np.asarray(self.cameras[i].K).shape)
         return (group, report) if diagnostics else group
 
     def camera_group_info_dict(self):

@@ -38,6 +38,7 @@
 #include "snowtri_seed.hpp"
 #include "snowtri_refine.hpp"
 #include "snowtri_pose.hpp"
+#include "snowtri_pose_intr.hpp"
 #include "snowtri_track.hpp"
 #include "snowtri_fill.hpp"
 #include "snowtri_despike.hpp"
@@ -237,6 +238,7 @@ struct snowtri_ctx {
     Scratch &sums = sets[0].sums;             // candidate sums of k_candidate_sums [frames][Kc] + the frames k_associate left behind
     Scratch in, out, aux;
     double *pose_ws = nullptr;                // workspace of snowtri_refine_cameras (pose_ws_doubles(C)): allocated by the first call, by no later one
+    double *pose_kws = nullptr;               // ... and of snowtri_refine_cameras_k (pose_kws_doubles(C)), with the context's K in it: likewise
     Scratch track;                            // centres [F][Pout_max][4] fp64 of snowtri_track_persons (k_track_centres -> k_track_chain)
     hipEvent_t track_ev[3] = {nullptr, nullptr, nullptr};   // with timing on: before k_track_centres | between | behind k_track_chain
     bool track_ev_valid = false;
@@ -426,7 +428,7 @@ struct Staging {
         size_t bytes, off;
         Kind kind;
     };
-    static constexpr int kMaxArrays = 12;
+    static constexpr int kMaxArrays = 16;
     static constexpr size_t kSlack = 256;   // behind each block
     Scratch &ins, &outs;
     const bool host;
@@ -735,6 +737,7 @@ int snowtri_ctx_destroy(snowtri_ctx *ctx) {
     if (ctx->dLens) (void)hipFree(ctx->dLens);
     if (ctx->dProj) (void)hipFree(ctx->dProj);
     if (ctx->pose_ws) (void)hipFree(ctx->pose_ws);
+    if (ctx->pose_kws) (void)hipFree(ctx->pose_kws);
     if (ctx->dBlenderTab) (void)hipFree(ctx->dBlenderTab);
     for (auto &S : ctx->sets) {
         if (S.d_counters) (void)hipFree(S.d_counters);
@@ -2608,6 +2611,86 @@ int refine_cameras_impl(const char *who, snowtri_ctx *ctx, int64_t F, int32_t P,
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------- camera refinement with intrinsics
+extern "C" {
+
+int snowtri_refine_cameras_k(snowtri_ctx *ctx, int64_t F, int32_t P, int32_t kn, const void *xyzs, int xyz_dtype, int32_t Pmax, const void *kpts,
+                             int kpts_dtype, const int32_t *n_persons, const int32_t *det_of, const uint32_t *views,
+                             double keypoint_score_threshold, uint32_t free_mask, uint32_t intr_mask, uint32_t intr_flags, int32_t min_obs,
+                             int32_t iters, uint32_t flags, double huber_px, double *K_out, double *R_out, double *t_out, double *cost,
+                             int64_t *n_obs, uint8_t *codes, double *normal, int64_t *n_outliers, int memspace, void *stream) {
+    const char *who = "snowtri_refine_cameras_k";
+    if (int rc = reproject_args(who, ctx, F, P, kn, xyz_dtype, 0u, kpts_dtype, memspace)) return rc;
+    const Refuse refuse{who};
+    HuberConst hc{};
+    if (int rc = huber_check(refuse, huber_px, hc)) return rc;
+    const bool huber = huber_px > 0.0;
+    ObservedInputs in;   // (F == 0 is work here, as in snowtri_refine_cameras: only k_pose_step_k runs, every camera is copied)
+    if (int rc = in.check(refuse, ctx, F, P, kn, xyzs, xyz_dtype, Pmax, kpts, kpts_dtype, n_persons, det_of, views, keypoint_score_threshold, iters,
+                          flags, SNOWTRI_REFINE_SCORE_WEIGHTS, memspace))
+        return rc;
+    if (min_obs < 3) return refuse("min_obs must be at least 3 (six parameters, two equations per observation)");
+    if (ctx->C < 32 && (free_mask >> ctx->C)) return refuse("free_mask has a bit at or above the number of cameras");
+    if (intr_flags & ~(uint32_t)(SNOWTRI_INTR_FOCAL | SNOWTRI_INTR_CENTRE)) return refuse("intr_flags has an unknown flag bit");
+    if (ctx->C < 32 && (intr_mask >> ctx->C)) return refuse("intr_mask has a bit at or above the number of cameras");
+    if (!R_out || !t_out) return refuse("null array (R_out or t_out)");
+    if (intr_flags && !K_out) return refuse("null array (K_out is required when intr_flags != 0)");
+    if (memspace == SNOWTRI_DEVICE && (((uintptr_t)K_out | (uintptr_t)R_out | (uintptr_t)t_out | (uintptr_t)cost | (uintptr_t)n_obs |
+                                        (uintptr_t)normal | (uintptr_t)n_outliers) & 7u))
+        return refuse("K_out, R_out, t_out, cost, n_obs, normal and n_outliers must be aligned to their element size");
+    const int C = ctx->C;
+    const int64_t n_rec = in.n_rec;
+    ENTER_DEVICE(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (!ctx->pose_kws) {   // the first intrinsics call on this context, and no later one
+        double *p = nullptr;
+        HIP_TRY(hipMalloc(&p, sizeof(double) * pose_kws_doubles(C)));
+        if (hipMemcpy(p + pose_kws_K(C), ctx->hK.data(), sizeof(double) * 9 * (size_t)C, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(p);
+            g_last_error = "hipMemcpy of K into the intrinsics workspace failed";
+            return SNOWTRI_ERR_HIP;
+        }
+        ctx->pose_kws = p;
+    }
+    double *dK = K_out, *dR = R_out, *dt = t_out, *d_cost = cost, *d_normal = normal;
+    int64_t *d_nobs = n_obs, *d_noutl = n_outliers;
+    uint8_t *d_codes = codes;
+    Staging sg(ctx->in, ctx->out, memspace == SNOWTRI_HOST, st);
+    in.stage(sg);
+    sg.out(&dK, sizeof(double) * 9 * (size_t)C);
+    sg.out(&dR, sizeof(double) * 9 * (size_t)C);
+    sg.out(&dt, sizeof(double) * 3 * (size_t)C);
+    sg.out(&d_cost, sizeof(double) * 2 * (size_t)C);
+    sg.out(&d_nobs, sizeof(int64_t) * (size_t)C);
+    sg.out(&d_codes, (size_t)C);
+    sg.out(&d_normal, sizeof(double) * kPoseKNormal * (size_t)C);
+    sg.out(&d_noutl, sizeof(int64_t) * (size_t)C);
+    if (int rc = sg.begin()) return rc;
+    double *ws = ctx->pose_kws;
+    const double *base = (const double *)ctx->dProj;
+    const int G = n_rec ? grid_for(n_rec, kPoseBlock, kPoseGridCap) : 0;
+    const int n_eval = n_rec ? (int)iters : 0;   // evaluations behind the one at the input: 2 (iters + 1) launches whatever the data does
+    for (int e = 0; e <= n_eval; e++) {
+        const double *trial = e ? ws + pose_kws_trial(C) : base;
+        const int32_t *active = e ? reinterpret_cast<const int32_t *>(ws + pose_kws_active(C)) : nullptr;
+        if (G)
+            with_float_pair(xyz_dtype, kpts_dtype, [&](auto tx, auto tk) {
+                using TX = decltype(tx);
+                using TK = decltype(tk);
+                const auto kernel = huber ? k_pose_normal_k<TX, TK, true> : k_pose_normal_k<TX, TK, false>;
+                const dim3 grid((unsigned)G, (unsigned)C);
+                hipLaunchKernelGGL(kernel, grid, dim3(kPoseBlock), 0, st, n_rec, C, (int)P, (int)Pmax, (int)kn, keypoint_score_threshold, flags, base,
+                                   trial, active, (const TX *)in.dx, (const TK *)in.dk, in.dnp, in.ddet, in.dviews, ws + pose_kws_partials(C), hc);
+            });
+        hipLaunchKernelGGL(k_pose_step_k, dim3(1), dim3(kPoseStepBlock), 0, st, C, G, e, e == n_eval ? 1 : 0, free_mask, intr_mask, intr_flags,
+                           (int)min_obs, base, ws, dK, dR, dt, d_cost, d_nobs, d_codes, d_normal, d_noutl);
+    }
+    HIP_TRY(hipGetLastError());
+    return sg.end();
+}
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------- fused A1..A4
 namespace {

@@ -28,8 +28,21 @@ mask from DLT_ROBUST is no substitute here: its leave-one-out gate removes exact
 pose step needs; the loss keeps them and down-weights the far ones.  On pose_cases.case with 10 % of the detections moved by
 20-150 px the squared loss leaves the free cameras 2e-2 .. 4e-2 from the truth, delta = 3 px 1e-3 .. 3e-3 (tests/test_huber_host.py).
 
-Not offered: intrinsics and lens coefficients, other losses (Cauchy, Tukey), an automatic delta, damping, points and cameras
-adjusted in one system, ShardedTrackPipeline, more than 32 cameras.
+INTRINSICS (intrinsics="f", "c" or "fc"; None, the default: nothing changes anywhere).  A chessboard K a percent or two off, or a lens
+refocused after calibration, is as common as a nudged tripod, and pose-only refinement HIDES it: on the recipe with camera 3's pose
+true, its fx, fy 2 % high and its centre off by (8, -5) px, freeing only its pose brings its view RMS from 8.4 px to the noise by moving
+a correct camera by centimetres, and view_rms then reports a healthy rig (EXPERIMENTS.md has the table).  The keyword adds fx, fy ("f")
+and / or cx, cy ("c") to a camera's parameters (include/snowtri.h, INTRINSICS; snowtri_refine_cameras_k, k_pose_normal_k /
+k_pose_step_k): ten parameters omega, tau, fx, fy, cx, cy, the free ones solved for together, K returned beside R and t.
+intrinsics_free names the cameras whose intrinsics may move (None: all) and is independent of `free`: a camera that holds the gauge
+may still have its K refined.  THE LIMITS: ten parameters need thousands of observations -- the principal point and the rotation are
+strongly correlated (a shift of the centre and a small pan move the pixels almost alike), and with some 150 noisy observations per
+camera all ten end as far from the truth as they started; free fewer, hold the pose, or record longer.  Pose-only refinement of a camera
+whose K is wrong lowers its RMS by moving it.  With a lens (D != 0) the detections were undistorted with the OLD K and must be
+undistorted again from the raw frame once K has moved; refine_rig does not do that.
+
+Not offered: lens coefficients, the skew, a focal length shared between cameras, other losses (Cauchy, Tukey), an automatic delta,
+damping, points and cameras adjusted in one system, ShardedTrackPipeline, more than 32 cameras.
 """
 from __future__ import annotations
 
@@ -42,6 +55,8 @@ from .refine import _check_iters, check_huber, huber_terms, observation_sets, pr
 from .reproject import _rig
 
 H_INDEX = [(a, b) for a in range(6) for b in range(a + 1)]      # normal[7 + k] = H[a][b]: the lower triangle row by row
+H_INDEX_K = [(a, b) for a in range(10) for b in range(a + 1)]   # with intrinsics: normal[11 + k] = H[a][b] over omega, tau, fx, fy, cx, cy
+INTR_FOCAL, INTR_CENTRE = 1, 2                                   # SNOWTRI_INTR_FOCAL, SNOWTRI_INTR_CENTRE
 
 
 def _check_min_obs(min_obs):
@@ -167,14 +182,165 @@ def solve_normal(normal):
     return delta, pd
 
 
+def intrinsics_flags(intrinsics):
+    """intrinsics: None, "f", "c" or "fc" -> snowtri_refine_cameras_k's intr_flags (0 for None)."""
+    if intrinsics is None:
+        return 0
+    if not isinstance(intrinsics, str) or intrinsics not in ("f", "c", "fc"):
+        raise ValueError(f'intrinsics must be None, "f", "c" or "fc" (got {intrinsics!r})')
+    return (INTR_FOCAL if "f" in intrinsics else 0) | (INTR_CENTRE if "c" in intrinsics else 0)
+
+
+def free_set(pose_free, flags):
+    """The free parameters of a camera, in the rule's order: the pose if pose_free, fx fy with INTR_FOCAL, cx cy with INTR_CENTRE."""
+    return (list(range(6)) if pose_free else []) + ([6, 7] if flags & INTR_FOCAL else []) + ([8, 9] if flags & INTR_CENTRE else [])
+
+
+def normal_terms_k(Kc, Rc, tc, X, ou, ov, w, delta=None):
+    """normal_terms over ten parameters (INTRINSICS) -> terms [n, 66]: every observation's share of E, g[10], H[55], and valid [n]."""
+    x, y, _, u, v, ok = project_camera(Kc, Rc, tc, X)
+    du6, dv6 = pose_jacobian(Kc, Rc, tc, X)
+    one, zero = np.ones_like(x), np.zeros_like(x)
+    du = np.concatenate([du6, np.stack([x, zero, one, zero], axis=1)], axis=1)
+    dv = np.concatenate([dv6, np.stack([zero, y, zero, one], axis=1)], axis=1)
+    ru, rv = u - ou, v - ov
+    terms = np.empty((X.shape[0], 66))
+    if delta is None:
+        terms[:, 0] = w * (ru * ru + rv * rv)
+    else:
+        rho, kappa, _ = huber_terms(ru * ru + rv * rv, delta)
+        terms[:, 0] = w * rho
+        w = w * kappa
+    for a in range(10):
+        terms[:, 1 + a] = w * (du[:, a] * ru + dv[:, a] * rv)
+    for k, (a, b) in enumerate(H_INDEX_K):
+        terms[:, 11 + k] = w * (du[:, a] * du[:, b] + dv[:, a] * dv[:, b])
+    return terms, ok
+
+
+def evaluate_camera_k(Kc, Rc, tc, X, ou, ov, w, delta=None):
+    """-> normal [66] = E, g[10], H[55], the terms summed in record order, and whether every observation is valid there."""
+    terms, ok = normal_terms_k(Kc, Rc, tc, X, ou, ov, w, delta)
+    return _ordered_sum(terms), bool(ok.all())
+
+
+def solve_normal_k(normal, idx):
+    """H delta = -g over the rows and columns idx (the free set, in order) of normal [66], by solve_normal's LDL^T at size
+    n = len(idx) in plain operations -> delta [10] (0 outside idx), every pivot finite and > 0."""
+    n = len(idx)
+    H = np.zeros((10, 10))
+    for k, (a, b) in enumerate(H_INDEX_K):
+        H[a, b] = normal[11 + k]
+    g = normal[1:11]
+    L, piv, y, d = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n)
+    pd = True
+    with np.errstate(all="ignore"):
+        for a in range(n):
+            for b in range(a + 1):
+                s = H[idx[a], idx[b]]
+                for k in range(b):
+                    s = s - L[a, k] * (L[b, k] * piv[k])
+                if b < a:
+                    L[a, b] = s / piv[b]
+                else:
+                    piv[a] = s
+            pd = pd and bool(piv[a] > 0.0) and bool(np.isfinite(piv[a]))
+        for a in range(n):
+            s = -g[idx[a]]
+            for k in range(a):
+                s = s - L[a, k] * y[k]
+            y[a] = s
+        for a in range(n - 1, -1, -1):
+            s = y[a] / piv[a]
+            for k in range(a + 1, n):
+                s = s - L[k, a] * d[k]
+            d[a] = s
+    delta = np.zeros(10)
+    for a in range(n):
+        delta[idx[a]] = d[a]
+    return delta, pd
+
+
+def apply_delta_k(Kc, Rc, tc, delta, idx):
+    """The trial of INTRINSICS: (K, Exp(omega) R, t + tau) with fx + d6, fy + d7, cx + d8, cy + d9; a parameter outside idx keeps its
+    bits."""
+    Kn, Rn, tn = np.array(Kc, copy=True), Rc, tc
+    if 0 in idx:
+        Rn, tn = apply_delta(Rc, tc, delta[:6])
+    if 6 in idx:
+        Kn[0, 0], Kn[1, 1] = Kc[0, 0] + delta[6], Kc[1, 1] + delta[7]
+    if 8 in idx:
+        Kn[0, 2], Kn[1, 2] = Kc[0, 2] + delta[8], Kc[1, 2] + delta[9]
+    return Kn, Rn, tn
+
+
+def _refine_cameras_reference_k(K, R, t, xyzs, kpts, det_of, n_persons, views, keypoint_score_threshold, free, min_obs, iters, score_weights,
+                                return_sets, huber_px, flags, intrinsics_free):
+    """refine_cameras_reference with intrinsics set: the rule of INTRINSICS."""
+    K, R, t, _, C = _rig(K, R, t, None)
+    iters = _check_iters(iters)
+    hub = check_huber(huber_px)
+    min_obs = _check_min_obs(min_obs)
+    mask, imask = free_mask(free, C), free_mask(intrinsics_free, C)
+    X, S, obs = observation_sets(K, R, t, xyzs, kpts, det_of, n_persons, views, keypoint_score_threshold, score_weights)
+    K_out, R_out, t_out = np.array(K, dtype=np.float64, copy=True), np.array(R, copy=True), np.array(t, copy=True)
+    cost, n_obs = np.zeros((C, 2)), np.zeros(C, dtype=np.int64)
+    codes, normal, steps = np.zeros(C, dtype=np.uint8), np.zeros((C, 66)), np.zeros(C, dtype=np.int64)
+    n_outliers = np.zeros(C, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for c in range(C):
+            Xc, ou, ov, w = X[S[c]], obs[c, S[c], 0], obs[c, S[c], 1], obs[c, S[c], 2]
+            n_obs[c] = len(Xc)
+            Kc, Rc, tc = K_out[c].copy(), R[c], t[c]
+            cur, _ = evaluate_camera_k(Kc, Rc, tc, Xc, ou, ov, w, hub)
+            normal[c] = cur
+            idx = free_set((mask >> c) & 1, flags if (imask >> c) & 1 else 0)
+            if not idx:
+                codes[c] = POSE_FIXED
+                continue
+            if n_obs[c] < min_obs:
+                codes[c] = POSE_FEW_OBS
+                continue
+            codes[c] = POSE_KEPT
+            cost[c, 0] = cur[0]
+            for _ in range(iters):
+                delta, pd = solve_normal_k(cur, idx)
+                if not pd:
+                    break
+                Kt, Rt, tt = apply_delta_k(Kc, Rc, tc, delta, idx)
+                nxt, valid = evaluate_camera_k(Kt, Rt, tt, Xc, ou, ov, w, hub)
+                focal_ok = Kt[0, 0] > 0.0 and np.isfinite(Kt[0, 0]) and Kt[1, 1] > 0.0 and np.isfinite(Kt[1, 1])
+                if not (valid and focal_ok and nxt[0] < cur[0]):
+                    break
+                Kc, Rc, tc, cur = Kt, Rt, tt, nxt
+                codes[c] = POSE_MOVED
+                steps[c] += 1
+            cost[c, 1] = cur[0]
+            K_out[c], R_out[c], t_out[c] = Kc, Rc, tc
+            if hub is not None:
+                n_outliers[c] = int(linear_regime(Kc, Rc, tc, Xc, ou, ov, hub).sum())
+    report = dict(cost=cost, n_obs=n_obs, codes=codes, normal=normal, steps=steps)
+    if hub is not None:
+        report["n_outliers"] = n_outliers
+    return (K_out, R_out, t_out, report, S) if return_sets else (K_out, R_out, t_out, report)
+
+
 def refine_cameras_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None,
-                             min_obs=64, iters=8, score_weights=False, return_sets=False, huber_px=None):
+                             min_obs=64, iters=8, score_weights=False, return_sets=False, huber_px=None, intrinsics=None,
+                             intrinsics_free=None):
     """The rule in NumPy: xyzs [F, P, kn, 4], kpts [F, C, Pmax, kn, 3], det_of [F, C, P] or None, n_persons [F, C] or None, views
     [F, P, kn] or None; free: None (all), a bit mask, C booleans or camera indices ->
     (R [C, 3, 3], t [C, 3], report) with report = dict(cost [C, 2], n_obs [C] int64, codes [C] uint8, normal [C, 28], steps [C]: the
     steps accepted); with return_sets also S [C, N] bool, the observation sets.  huber_px (delta > 0; None or 0: the squared loss,
     and no new key): the Huber loss of ROBUST LOSS, and report["n_outliers"] [C] int64, the observations of S_c in the linear
-    regime at the output pose (0 for FIXED and FEW_OBS cameras)."""
+    regime at the output pose (0 for FIXED and FEW_OBS cameras).  intrinsics ("f": fx and fy, "c": cx and cy, "fc"; None, the
+    default: everything above, unchanged): the rule of INTRINSICS -> (K [C, 3, 3], R, t, report[, S]) with report["normal"] [C, 66] =
+    E, g[10], H[55] (H_INDEX_K) at the input; intrinsics_free: the cameras whose intrinsics may move -- None (all), a bit mask, C
+    booleans or camera indices -- independent of `free`."""
+    flags = intrinsics_flags(intrinsics)
+    if flags:
+        return _refine_cameras_reference_k(K, R, t, xyzs, kpts, det_of, n_persons, views, keypoint_score_threshold, free, min_obs, iters,
+                                           score_weights, return_sets, huber_px, flags, intrinsics_free)
     K, R, t, _, C = _rig(K, R, t, None)
     iters = _check_iters(iters)
     hub = check_huber(huber_px)
@@ -222,13 +388,16 @@ def refine_cameras_reference(K, R, t, xyzs, kpts, det_of=None, n_persons=None, v
 
 
 def refine_cameras(ctx, xyzs, kpts, det_of=None, n_persons=None, views=None, keypoint_score_threshold=0.0, free=None, min_obs=64, iters=8,
-                   score_weights=False, diagnostics=False, stream=None, huber_px=None):
+                   score_weights=False, diagnostics=False, stream=None, huber_px=None, intrinsics=None, intrinsics_free=None):
     """k_pose_normal / k_pose_step through the context of the rig (_lib.Context): Context.refine_cameras.  -> (R, t), or
     (R, t, report) with diagnostics=True; the context's own rig is not changed.  huber_px > 0: the Huber loss, and the report gains
-    n_outliers [C]."""
-    return ctx.refine_cameras(xyzs, kpts, det_of=det_of, n_persons=n_persons, views=views, keypoint_score_threshold=keypoint_score_threshold,
-                              free=free, min_obs=min_obs, iters=iters, score_weights=score_weights, diagnostics=diagnostics, stream=stream,
-                              huber_px=huber_px)
+    n_outliers [C].  intrinsics ("f", "c", "fc"; None: nothing changes): k_pose_normal_k / k_pose_step_k, -> (K, R, t) or
+    (K, R, t, report) with report["normal"] [C, 66]; intrinsics_free: the cameras whose intrinsics may move (None: all)."""
+    kw = dict(det_of=det_of, n_persons=n_persons, views=views, keypoint_score_threshold=keypoint_score_threshold, free=free, min_obs=min_obs,
+              iters=iters, score_weights=score_weights, diagnostics=diagnostics, stream=stream, huber_px=huber_px)
+    if intrinsics is not None:
+        kw.update(intrinsics=intrinsics, intrinsics_free=intrinsics_free)
+    return ctx.refine_cameras(xyzs, kpts, **kw)
 
 
 # ------------------------------------------------------------------------------------------------ the alternation
@@ -251,7 +420,7 @@ class _LibrarySteps:
         return res["xyzs"]
 
     def open(self, K, R, t):
-        self.ctx = _lib.Context(K, R, t)
+        self.K, self.ctx = K, _lib.Context(K, R, t)
 
     def close(self):
         self.ctx.close()
@@ -274,7 +443,8 @@ class _LibrarySteps:
         return self.ctx.refine_joints(xyzs, kpts, **kw)
 
     def cameras(self, xyzs, kpts, **kw):
-        return self.ctx.refine_cameras(xyzs, kpts, diagnostics=True, **kw)
+        out = self.ctx.refine_cameras(xyzs, kpts, diagnostics=True, **kw)
+        return out if len(out) == 4 else (self.K,) + tuple(out)
 
 
 class _ReferenceSteps:
@@ -311,12 +481,13 @@ class _ReferenceSteps:
         return refine_joints_reference(*self.rig, xyzs, kpts, **kw)[0]
 
     def cameras(self, xyzs, kpts, **kw):
-        return refine_cameras_reference(*self.rig, xyzs, kpts, **kw)
+        out = refine_cameras_reference(*self.rig, xyzs, kpts, **kw)
+        return out if len(out) == 4 else (self.rig[0],) + tuple(out)
 
 
 def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.DLT, params=None, persons=None, gate_px=12.0,
                min_joints=8, joint_iters=4, camera_iters=8, min_obs=64, score_weights=False, triangulate=None, reference=False,
-               one_to_one=False, retriangulate=False, huber_px=None):
+               one_to_one=False, retriangulate=False, huber_px=None, intrinsics=None, intrinsics_free=None):
     """Block-coordinate bundle adjustment of the extrinsics: `rounds` times triangulate on the current rig, match the detections to the
     3D persons (reprojection_cost + match_detections, gate_px), refine the joints (refine_joints, joint_iters), refine the free cameras
     (refine_cameras, camera_iters, min_obs), and build a new context from the result.  Host arrays: kpts [F, C, Pmax, kn, 3] on the
@@ -345,6 +516,11 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
     huber_px (delta > 0 in pixels; None or 0, the default: the squared loss, nothing changes): the Huber loss of ROBUST LOSS in both
     the joint step and the camera step of every round, in the library steps and the reference=True steps alike; finite, >= 0 and at
     most 1e150 (ValueError before any work).
+    intrinsics ("f": fx and fy, "c": cx and cy, "fc"; None, the default: nothing changes) and intrinsics_free (the cameras whose
+    intrinsics may move; None: all; independent of `free`, so the gauge camera's K may be refined): the camera step also solves for
+    those intrinsics (INTRINSICS above and in include/snowtri.h) and K is carried from round to round, in the library steps and the
+    reference=True steps alike; the result is then (K [C, 3, 3], R, t, history).  The detections stay the ones handed in: with a
+    lens they were undistorted with the old K and should be undistorted again from the raw frame once K has moved.
 
     -> (R [C, 3, 3], t [C, 3], history): history[r] = dict(overflow_frames: the frames in which the library's triangulation found
     more clusters than `persons` and dropped some (0 with the caller's `triangulate`), view_rms [C]: each camera's RMS pixel residual over its matched views
@@ -373,12 +549,14 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
         from .reproject import assign_gate
         assign_gate(gate_px)
     huber_px = check_huber(huber_px)
+    intr = intrinsics_flags(intrinsics)
+    imask = free_mask(intrinsics_free, C) if intr else 0
     if reference and triangulate is None:
         raise ValueError("refine_rig: reference=True needs `triangulate` (the library's triangulation runs on the GPU)")
     steps = _ReferenceSteps(triangulate) if reference else _LibrarySteps(method, params, P)
     if triangulate is not None:
         steps.triangulate = triangulate
-    R, t = np.array(R, copy=True), np.array(t, copy=True)
+    K, R, t = np.array(K, dtype=np.float64, copy=True), np.array(R, copy=True), np.array(t, copy=True)
     history = []
 
     def measure(xyzs):
@@ -411,12 +589,14 @@ def refine_rig(K, R, t, kpts, n_persons=None, free=None, rounds=2, method=_lib.D
                 xyzs, kw["views"] = merge_records(xyzs, np.asarray(again, dtype=np.float64), views)
                 xyzs = np.ascontiguousarray(xyzs)
             xyzs = steps.joints(xyzs, kpts, iters=joint_iters, **kw)
-            R, t, rep = steps.cameras(xyzs, kpts, free=mask, min_obs=min_obs, iters=camera_iters, **kw)
-            R, t = np.array(R, dtype=np.float64), np.array(t, dtype=np.float64)
+            if intr:
+                kw.update(intrinsics=intrinsics, intrinsics_free=imask)
+            Kn, R, t, rep = steps.cameras(xyzs, kpts, free=mask, min_obs=min_obs, iters=camera_iters, **kw)
+            K, R, t = np.array(Kn, dtype=np.float64), np.array(R, dtype=np.float64), np.array(t, dtype=np.float64)
             history.append(dict(overflow_frames=steps.overflow_frames, view_rms=view_rms, cost=np.array(rep["cost"]), n_obs=np.array(rep["n_obs"]), codes=np.array(rep["codes"])))
         finally:
             steps.close()
-    return R, t, history
+    return (K, R, t, history) if intr else (R, t, history)
 
 
 __all__ = ["refine_cameras", "refine_cameras_reference", "refine_rig", "POSE_FIXED", "POSE_FEW_OBS", "POSE_KEPT", "POSE_MOVED"]
